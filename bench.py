@@ -5,11 +5,18 @@ fused AdamW, LR step) of the te_llama counterpart on synthetic tokens and random
 decoder Linear and lm_head running the hand-written HIP FP8 path (cast+amax, scale update, MFMA GEMM).
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events around every FP8 GEMM launch of every
-second timed step (an event costs ~4.5 us of queue time: bracketing every kernel of every step slowed the step by 5 %,
-the GEMMs of every step by 3 %); `cpu_baseline` is the repo's own no-TE HF bf16 path timed on this host's CPU cores
-(rank 0, N = 1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline fields
+(`value` in tokens/s, `ms_per_step`, `final_loss`); nothing else runs inside or after the timed steps.  `--full` adds the
+diagnostics: `roofline`, `gemm_sites` and `hbm_kernels`, measured live with HIP events around the FP8 GEMM launches of every
+4th timed step and around the cast / attention launches of one timed step (an event costs ~4.5 us of queue time:
+bracketing every kernel of every step slowed the step by 5 %, the GEMMs of every step by 3 %), the in-kernel GEMM clock
+(`roofline.clock_ghz`, >= 1 s of extra launches per probed site), and `cpu_baseline`, the repo's own no-TE HF bf16 path
+timed on this host's CPU cores (rank 0, N = 1 only).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step handed back: DIR/loss.npy and, per parameter,
+DIR/param.<name>.npy (see dump_outputs).  Inputs are seeded, so two builds run with the same arguments compare array by array.
 """
 from __future__ import annotations
 
@@ -178,6 +185,27 @@ def pmc_traffic(by_tag):
         f"(profiles/{cands[-1]}); counts Infinity-Cache hits, i.e. L2-miss traffic; `avg_algorithmic_bytes_per_launch` covers the SAME launches")
 
 
+DUMP_SAMPLE = 16384  # elements kept per parameter: 64 KiB each, ~16 MB for the ~260 tensors of Llama-3.1-8B (cap: 64 MB)
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed step holds after the last one: its loss (loss.npy, [1]) and the trained parameters
+    (param.<name>.npy).  A parameter of more than DUMP_SAMPLE elements is written as the elements at DUMP_SAMPLE flat indices
+    drawn from a generator seeded by its name, the same on every run and build.  float32: exact for the fp32 loss and the bf16
+    parameters.  Rank 0 writes its own view (its loss; under a sharding wrapper, its shards)."""
+    import zlib
+    import numpy as np
+    from llm_fp8_amd import checkpoint
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    for name, p in checkpoint.unwrap(model).named_parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).integers(0, flat.numel(), DUMP_SAMPLE)
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, f"param.{name}.npy"), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -193,10 +221,18 @@ def main():
     ap.add_argument("--layers", type=int, default=None, help="debug only: fewer layers (result is then not the headline metric)")
     ap.add_argument("--route", default="fused", choices=["fused", "reference"],
                     help="reference = drive every decoder layer exactly as te_llama.py:76-81 does (public kwargs, plain residual adds)")
-    ap.add_argument("--cpu-baseline-extrapolate", action="store_true", help="also time the benchmarked model at 2 and 4 layers on the CPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the diagnostics: per-kernel HIP-event timing (roofline, gemm_sites, hbm_kernels), the GEMM "
+                         "clock probe and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss and a seeded sample of the trained parameters as DIR/*.npy")
+    ap.add_argument("--cpu-baseline-extrapolate", action="store_true", help="with --full: also time the benchmarked model at 2 and 4 layers on the CPU")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: no HIP events in the timed steps (no roofline)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    kernel_timing = args.full and not args.no_kernel_timing
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback for the FP8 path)")
@@ -236,11 +272,12 @@ def main():
     aux_step = 1 if args.steps > 1 else -1
     for i in range(args.warmup):
         train.train_step(model, batches[i % 4], opt, sched, cfg)
-    # inside the timed region only the FP8 GEMM launches are bracketed by HIP events (every event costs queue time)
+    # --full: inside the timed region only the FP8 GEMM launches are bracketed by HIP events (every event costs queue time);
+    # a plain run brackets nothing
     timer = KernelTimer(kinds=("gemm_fp8", "gemm_mxfp8"))
     sync()
     t0 = time.perf_counter()
-    if args.no_kernel_timing:
+    if not kernel_timing:
         for i in range(args.steps):
             loss = train.train_step(model, batches[i % 4], opt, sched, cfg)
     else:
@@ -260,6 +297,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
 
     if rank == 0:
         tokens = args.batch * args.seq * world * args.steps
@@ -279,7 +318,7 @@ def main():
                                           "--model llama-3.1-8b --batch 12 --sharding_mode fsdp_fp8"},
             "final_loss": loss_val,
         }
-        if not args.no_kernel_timing:
+        if kernel_timing:
             summ = timer.summarize()
             kind = "gemm_mxfp8" if args.scenario == "mxfp8" and "gemm_mxfp8" in summ else "gemm_fp8"
             g = summ.get(kind)
@@ -325,7 +364,7 @@ def main():
             out["hbm_kernels"] = hbm
             out["hbm_kernels_note"] = ("cast / quantise / attention kernels bracketed by HIP events during timed step 1 (of the timed region); "
                                        "PMC FETCH_SIZE / WRITE_SIZE of the same kernels: profiles/*_hbm_pmc_traffic.json")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del model, opt
             torch.cuda.empty_cache()
             out["cpu_baseline"] = cpu_baseline(args.model, extrapolate_bench_model=args.cpu_baseline_extrapolate)
