@@ -612,7 +612,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const uint16_t* __restrict_
     float add = 0.0f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) add += __expf(f[j] - nm);
-    ssum = ssum * __expf(m - nm) + add;
+    // a lane whose values so far are all -inf (masked vocabulary entries) keeps (m, ssum) = (-inf, 0): exp(-inf - -inf) is NaN
+    ssum = (nm == -INFINITY) ? 0.0f : ssum * __expf(m - nm) + add;
     m = nm;
   }
   // combine (m, ssum) across the wave, then across the 4 waves
@@ -630,7 +631,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const uint16_t* __restrict_
 #pragma unroll
     for (int w = 1; w < 4; ++w) {
       const float nm = fmaxf(M, s_m[w]);
-      S = S * __expf(M - nm) + s_s[w] * __expf(s_m[w] - nm);
+      S = (nm == -INFINITY) ? 0.0f : S * __expf(M - nm) + s_s[w] * __expf(s_m[w] - nm);  // waves 0 .. w all -inf / empty
       M = nm;
     }
     const float l = M + __logf(S);

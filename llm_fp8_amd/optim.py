@@ -35,8 +35,7 @@ class ClippedAdamW(torch.optim.Optimizer):
 
     TILE = 128  # a sink tensor's chunks are TILE x TILE tiles of the weight matrix (mi_adamw_cast_bf16_multi)
 
-    @staticmethod
-    def _sink_of(p):
+    def _sink_of(self, p):
         """(sink, row offset, rows) when the FP8 copies of this weight are kept current by the optimiser (module.WeightSink)."""
         if os.environ.get("LLM_FP8_AMD_NO_OPT_WCAST") == "1":  # the switch of module.weight_sinks_enabled: the forward casts
             return None
@@ -46,24 +45,21 @@ class ClippedAdamW(torch.optim.Optimizer):
             full, sr0, sn = sh
             fs = getattr(full, "_mi_fp8_sink", None)
             s = None if fs is None else (fs[0], fs[1] + sr0, sn)
-        if s is None or not p.is_contiguous() or p.dim() != 2 or not ClippedAdamW._aligned16(p):
+        if s is None or not p.is_contiguous() or p.dim() != 2 or not self._aligned16(p):
             return None
         sink, r0, n = s
         if n != p.shape[0] or sink.w8.shape[1] != p.shape[1] or p.shape[0] % 8 or p.shape[1] % 8:
             return None
         return s
 
-    @staticmethod
-    def _aligned16(p) -> bool:
+    def _aligned16(self, p) -> bool:
         """The tile path of the *_cast kernels issues 16-byte loads / stores on the parameter, its gradient and both moments
         unconditionally; a tensor at an odd storage offset (a loaded optimiser state, a `.grad` view) takes the flat path."""
-        if p.data_ptr() % 16:
-            return False
-        g = p.grad
-        return g is None or g.data_ptr() % 16 == 0
+        st = self.state.get(p, {})
+        others = (p.grad, st.get("exp_avg"), st.get("exp_avg_sq"))
+        return p.data_ptr() % 16 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in others)
 
-    @staticmethod
-    def _mx_sink_of(p):
+    def _mx_sink_of(self, p):
         """(sink, row offset, rows) when the MXFP8 copies of this weight are kept current by the optimiser (module.MXWeightSink)."""
         if os.environ.get("LLM_FP8_AMD_NO_OPT_WCAST") == "1":
             return None
@@ -73,7 +69,7 @@ class ClippedAdamW(torch.optim.Optimizer):
             full, sr0, sn = sh
             fs = getattr(full, "_mi_mx_sink", None)
             s = None if fs is None else (fs[0], fs[1] + sr0, sn)
-        if s is None or not p.is_contiguous() or p.dim() != 2 or not ClippedAdamW._aligned16(p):
+        if s is None or not p.is_contiguous() or p.dim() != 2 or not self._aligned16(p):
             return None
         sink, r0, n = s
         if n != p.shape[0] or sink.w8.shape[1] != p.shape[1] or p.shape[0] % 32 or p.shape[1] % 32 or r0 % 32:

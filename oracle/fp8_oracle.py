@@ -488,8 +488,9 @@ def rmsnorm_f32(x_bits: np.ndarray, gamma_bits: np.ndarray, eps: float):
     return (x * rstd[:, None] * g[None, :]).astype(np.float32), rstd.astype(np.float32)
 
 
-def rmsnorm_bwd_f32(dy_bits: np.ndarray, x_bits: np.ndarray, gamma_bits: np.ndarray, eps: float):
-    """(dx float32, dgamma float32) of y = x * rstd * gamma."""
+def rmsnorm_bwd_f32(dy_bits: np.ndarray, x_bits: np.ndarray, gamma_bits: np.ndarray, eps: float, dres_bits: np.ndarray = None):
+    """(dx float32, dgamma float32) of y = x * rstd * gamma; `dres` (bf16 bits, the gradient arriving over the residual
+    connection) is added to dx in float64."""
     dy = bf16_bits_to_f32(dy_bits).astype(np.float64)
     x = bf16_bits_to_f32(x_bits).astype(np.float64)
     g = bf16_bits_to_f32(gamma_bits).astype(np.float64)
@@ -498,7 +499,45 @@ def rmsnorm_bwd_f32(dy_bits: np.ndarray, x_bits: np.ndarray, gamma_bits: np.ndar
     wdy = dy * g[None, :]
     c = (wdy * xh).mean(axis=1)
     dx = rstd[:, None] * (wdy - xh * c[:, None])
+    if dres_bits is not None:
+        dx = dx + bf16_bits_to_f32(dres_bits).astype(np.float64)
     return dx.astype(np.float32), (dy * xh).sum(axis=0).astype(np.float32)
+
+
+def cross_entropy_f64(x_bits: np.ndarray, labels: np.ndarray, gscale: float = 1.0):
+    """Token cross-entropy of bf16 logits [T, V] in float64: (lse [T], loss [T], dlogits [T, V]).
+    loss = lse - x[label], dlogits = (softmax - onehot(label)) * gscale; a row whose label is outside [0, V) (-100 or >= V)
+    is ignored: loss 0, dlogits 0 (the convention of mi_ce_forward / mi_ce_backward)."""
+    x = bf16_bits_to_f32(x_bits).astype(np.float64)
+    T, V = x.shape
+    m = x.max(axis=1)
+    lse = m + np.log(np.exp(x - m[:, None]).sum(axis=1))
+    valid = (labels >= 0) & (labels < V)
+    lab = np.where(valid, labels, 0)
+    rows = np.arange(T)
+    loss = np.where(valid, lse - x[rows, lab], 0.0)
+    d = np.exp(x - lse[:, None])
+    d[rows[valid], lab[valid]] -= 1.0
+    d *= np.where(valid, gscale, 0.0)[:, None]
+    return lse, loss, d
+
+
+def adamw_step_f64(p_bits, g_bits, m_bits, v_bits, step: int, lr: float, beta1: float, beta2: float, eps: float,
+                   weight_decay: float, grad_scale: float = 1.0):
+    """One torch.optim.AdamW step in float64 from bf16 state (bits), rounded to bf16 at the end as the bf16 state layout of
+    optim.ClippedAdamW is: (p, exp_avg, exp_avg_sq) as float64 BEFORE that rounding.  Decoupled decay p *= 1 - lr * wd;
+    denom = sqrt(v) / sqrt(1 - beta2^step) + eps; p -= lr / (1 - beta1^step) * m / denom; g = grad_scale * grad (the clip
+    coefficient)."""
+    p = bf16_bits_to_f32(p_bits).astype(np.float64)
+    g = bf16_bits_to_f32(g_bits).astype(np.float64) * grad_scale
+    m = bf16_bits_to_f32(m_bits).astype(np.float64)
+    v = bf16_bits_to_f32(v_bits).astype(np.float64)
+    p = p * (1.0 - lr * weight_decay)
+    m = beta1 * m + (1.0 - beta1) * g
+    v = beta2 * v + (1.0 - beta2) * g * g
+    bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
+    p = p - (lr / bc1) * m / (np.sqrt(v) / np.sqrt(bc2) + eps)
+    return p, m, v
 
 
 def attention_f64(q_bits, k_bits, v_bits, scale: float, causal: bool = True):

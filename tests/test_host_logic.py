@@ -117,3 +117,19 @@ def test_padding_mask_never_reaches_hfs_mask_builder():
     assert torch.equal(with_mask, no_mask) and torch.equal(with_mask, plain)
     assert seen[0] is not None and seen[0].dim() == 4 and seen[0].numel() == 1  # the placeholder reached the decoder layers
     assert seen[2] is four_d or (seen[2].shape == four_d.shape)  # a caller's prepared 4-D mask is passed through untouched
+
+
+def test_rmsnorm_bwd_width_tests_cover_every_dispatcher_instance():
+    """tests/test_kernel_widths_gpu.py runs mi_rmsnorm_bwd at cols = 512 x NVEC for exactly the NVEC of the MI_RB(NVEC, WPR)
+    instances in mi_fused.hip: an instance added there without a GPU test fails here, on any machine."""
+    import os
+    import re
+    from tests import test_kernel_widths_gpu as widths
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "llm_fp8_amd", "csrc", "mi_fused.hip")).read()
+    body = src[src.index('extern "C" int mi_rmsnorm_bwd('):]
+    body = body[:body.index("#undef MI_RB")]
+    inst = [(int(a), int(b)) for a, b in re.findall(r"MI_RB\(\s*(\d+)\s*,\s*(\d+)\s*\)", body)]
+    assert len(inst) >= 12 and len({v for v, _ in inst}) == len(inst), inst
+    assert {1, 2, 4} >= {w for _, w in inst}
+    assert sorted(v for v, _ in inst) == sorted(widths.RB_VECS)
+    assert widths.RB_WIDTHS == tuple(512 * v for v in widths.RB_VECS)
