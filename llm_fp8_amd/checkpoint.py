@@ -128,6 +128,12 @@ def save_pretrained(model: torch.nn.Module, out_dir: str, config=None, layout: s
     from safetensors.torch import save_file
     from .llama import to_hf_state_dict
     config = config if config is not None else model.config
+    hollow = [n for n, p in model.named_parameters()
+              if getattr(p, "_mi_sharded", None) is not None and p.untyped_storage().nbytes() < p.numel() * p.element_size()]
+    if hollow:  # a row-sharded weight (distributed.ShardedFP8DP) without its gathered master: its view would be written as zeros
+        raise RuntimeError(f"save_pretrained: {len(hollow)} weight(s) are row-sharded and hold no full master on this rank "
+                           f"({hollow[:4]}{' ...' if len(hollow) > 4 else ''}); call gather_master_weights() on the "
+                           "ShardedFP8DP wrapper first (and reshard() afterwards)")
     os.makedirs(out_dir, exist_ok=True)
     raw = model.state_dict()
     if layout == "hf":

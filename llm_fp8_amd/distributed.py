@@ -514,7 +514,9 @@ class ShardedFP8DP(GradArenaDP):
                 fix.append((sink.wt8[:, row_off:row_off + n], t_wt))
         return ops_, fix
 
-    def _launch_gather(self, sinks, blocking: bool):
+    def _launch_gather(self, sinks, blocking: bool, mark: bool):
+        """All-gather the FP8 rows of `sinks`.  `mark`: the local rows were quantised just now (refresh) and the bytes in flight
+        are current; otherwise they carry the stamp the optimiser gave the sink (after_optimizer_step)."""
         pairs, per_sink = [], []
         for sink in sinks:
             self._check_recipe(sink)
@@ -534,10 +536,11 @@ class ShardedFP8DP(GradArenaDP):
             except (ImportError, RuntimeError, TypeError, AttributeError):
                 works = [dist.all_gather_into_tensor(dst, src, group=self.group, async_op=True) for dst, src in pairs]
         for sink, f in per_sink:
-            # the stamp the bytes in flight deserve: parameter versions and scale-arena generation AS OF THEIR QUANTISATION (now).
-            # Stamping at wait time would declare them current under a scale that has moved on since (per-layer autocasts
-            # without an outer one bump the generation between this launch and the forward that waits)
-            sink.mark()
+            # the stamp the bytes in flight deserve: parameter versions and scale-arena generation AS OF THEIR QUANTISATION (now,
+            # or the optimiser's step).  Stamping at wait time would declare them current under a scale that has moved on since
+            # (per-layer autocasts without an outer one bump the generation between this launch and the forward that waits)
+            if mark:
+                sink.mark()
             stamp, sink.stamp = sink.stamp, None
             self._gathers[id(sink)] = (works, f, stamp)
         if blocking:
@@ -560,9 +563,16 @@ class ShardedFP8DP(GradArenaDP):
         sink.stamp = stamp
 
     def after_optimizer_step(self):
-        """Issue the FP8 all-gathers of the freshly quantised shards: asynchronously, module by module in next-forward order."""
+        """Issue the FP8 all-gathers of the freshly quantised shards: asynchronously, module by module in next-forward order.
+        Only sinks the optimiser has just rewritten (and stamped) are gathered, with the optimiser's stamp: a sink it did not
+        rewrite in full (LLM_FP8_AMD_NO_OPT_WCAST=1, a weight without a gradient this step, a scale moved on) stays stale and
+        is refreshed from the shards by its next forward.  The gathers are collectives, so every rank must pick the same
+        sinks: it does, because what decides freshness -- settings, which weights have a gradient (reduced over the ranks),
+        the number of steps and scale updates -- is the same on every rank."""
         for _m, sinks in self._sinks_in_forward_order():
-            self._launch_gather(sinks, blocking=False)
+            sinks = [s_ for s_ in sinks if s_.fresh()]
+            if sinks:
+                self._launch_gather(sinks, blocking=False, mark=False)
 
     def refresh_operand(self, sink, fmt: int):
         """Delayed scaling, sink not current: cast this rank's rows with the CURRENT scale (amax deposited as the forward cast
@@ -571,7 +581,7 @@ class ShardedFP8DP(GradArenaDP):
         for w, row_off, n in sink.parts:
             h = w._mi_sharded
             ops.cast_amax(h.shard.data, sink.scale, sink.amax, fmt, y=sink.w8[row_off + h.r0:row_off + h.r0 + h.rows], want_t=False)
-        self._launch_gather([sink], blocking=True)
+        self._launch_gather([sink], blocking=True, mark=True)
 
     def refresh_mx_operand(self, sink, fmt: int):
         from .pytorch import ops
@@ -581,7 +591,7 @@ class ShardedFP8DP(GradArenaDP):
             ops.mxfp8_quantize(h.shard.data, fmt, rowwise=True, colwise=True,
                                out=(sink.w8[lo:lo + h.rows], sink.sc[:, lo:lo + h.rows], sink.wt8[:, lo:lo + h.rows],
                                     sink.sct[lo // 32:(lo + h.rows) // 32]))
-        self._launch_gather([sink], blocking=True)
+        self._launch_gather([sink], blocking=True, mark=True)
 
     # ------------------------------------------------------------------------------------------------ full masters on request
     def gather_master_weights(self):

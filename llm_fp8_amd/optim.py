@@ -11,6 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .pytorch.module import stepped_tensor
 
 
 class ClippedAdamW(torch.optim.Optimizer):
@@ -243,7 +244,8 @@ class ClippedAdamW(torch.optim.Optimizer):
                 if s is not None:
                     sinks_seen[id(s[0])] = s[0]
         for sink in sinks_seen.values():  # copies are current only if EVERY part of the operand was rewritten in this step
-            if all(id(w) in touched for w, _, _ in sink.parts):
+            # (a row-sharded part, distributed.ShardedFP8DP, was updated through its shard: this rank's rows of the copies)
+            if all(id(stepped_tensor(w)) in touched for w, _, _ in sink.parts):
                 sink.mark()
             else:
                 sink.stamp = None

@@ -135,10 +135,21 @@ class WeightSink:
         self.stamp = None
 
     def fresh(self) -> bool:
-        return self.stamp is not None and self.stamp == (tuple(w._version for w, _, _ in self.parts), self.arena.generation)
+        return self.stamp is not None and self.stamp == (_part_versions(self.parts), self.arena.generation)
 
     def mark(self) -> None:  # called by the optimiser after it rewrote every part in this step
-        self.stamp = (tuple(w._version for w, _, _ in self.parts), self.arena.generation)
+        self.stamp = (_part_versions(self.parts), self.arena.generation)
+
+
+def stepped_tensor(w):
+    """The tensor the optimiser writes for a weight part: a row-sharded weight (distributed.ShardedFP8DP) is updated through its
+    shard -- the module's Parameter is a storage-less view whose version never moves -- any other weight is itself."""
+    h = getattr(w, "_mi_sharded", None)
+    return w if h is None else h.shard
+
+
+def _part_versions(parts) -> tuple:
+    return tuple(stepped_tensor(w)._version for w, _, _ in parts)
 
 
 # LLM_FP8_AMD_NO_MLP_BIAS_FUSION=1: keep both MLP biases in the GEMM epilogues (the round-2 behaviour; A/B switch)
@@ -197,10 +208,10 @@ class MXWeightSink:
         self.stamp = None
 
     def fresh(self) -> bool:
-        return self.stamp is not None and self.stamp == tuple(w._version for w, _, _ in self.parts)
+        return self.stamp is not None and self.stamp == _part_versions(self.parts)
 
     def mark(self) -> None:  # called by the optimiser after it rewrote every part in this step
-        self.stamp = tuple(w._version for w, _, _ in self.parts)
+        self.stamp = _part_versions(self.parts)
 
 
 def _mx_sink_copies(spec: _GemmSpec, g: int, weights, ns, N: int, K: int, dev):

@@ -182,6 +182,11 @@ def create_optimizer(model, cfg: TrainingConfig):
     params = [p for g in groups for p in g["params"]] if groups is not None else [p for p in model.parameters() if p.requires_grad]
     fused = all(p.is_cuda for p in params)
     wrapped = type(model).__name__ in ("FullyShardedDataParallel", "DistributedDataParallel")
+    if os.environ.get("LLM_FP8_AMD_TORCH_ADAMW") == "1" and type(model).__name__ == "ShardedFP8DP":
+        # torch's AdamW would step the row shards, but train_step clips over model.parameters(), where the shards are not
+        # registered: the decoder weights' gradients would never enter the norm; and no FP8 copy would be kept current
+        raise RuntimeError("LLM_FP8_AMD_TORCH_ADAMW=1 is not supported with --sharding_mode fsdp_fp8 (ShardedFP8DP): its row "
+                           "shards need ClippedAdamW's clip over the ranks -- unset the variable or use another sharding mode")
     if (fused and not wrapped and all(p.dtype == torch.bfloat16 for p in params)
             and os.environ.get("LLM_FP8_AMD_TORCH_ADAMW") != "1"):
         from .optim import ClippedAdamW

@@ -88,6 +88,30 @@ def test_te_layout_roundtrip_keeps_te_names_and_biases(tmp_path):
             assert torch.equal(a.float(), b.float()), k
 
 
+def test_save_refuses_row_sharded_weights_without_their_master(tmp_path):
+    """distributed.ShardedFP8DP leaves a module's GEMM weight as a storage-less expanded view carrying `_mi_sharded`; written as it
+    is, `.contiguous()` would turn it into an all-zero tensor.  save_pretrained must refuse, and save the real values once the
+    master is materialised again (gather_master_weights puts a full tensor back into `.data`)."""
+    from llm_fp8_amd import checkpoint, llama
+    from llm_fp8_amd.distributed import _ShardHandle
+    cfg = _tiny_cfg()
+    torch.manual_seed(2)
+    m = llama.TELlamaForCausalLM(cfg, "default")
+    p = m.model.layers[1].layernorm_mlp.fc2_weight
+    full = p.detach().clone()
+    n = p.shape[0] // 2
+    p._mi_sharded = _ShardHandle(None, torch.nn.Parameter(full[:n].clone()), 0, n)  # rank 0 of 2
+    p.data = torch.zeros(1, dtype=p.dtype).expand(p.shape)
+    with pytest.raises(RuntimeError, match="gather_master_weights"):
+        checkpoint.save_pretrained(m, str(tmp_path / "hollow"))
+    assert not (tmp_path / "hollow" / "model.safetensors").exists()
+    p.data = full.clone()
+    checkpoint.save_pretrained(m, str(tmp_path / "full"))
+    from safetensors.torch import load_file
+    got = load_file(str(tmp_path / "full" / "model.safetensors"))["model.layers.1.mlp.down_proj.weight"]
+    assert torch.equal(got.view(torch.int16), full.view(torch.int16))
+
+
 def test_missing_or_pickled_checkpoints_are_refused(tmp_path):
     from llm_fp8_amd import checkpoint
     (tmp_path / "pytorch_model.bin").write_bytes(b"not read")

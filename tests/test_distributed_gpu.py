@@ -66,7 +66,9 @@ def test_fsdp_full_shard_matches_the_unwrapped_run(dev, world, scenario):
             assert o["worst_rel"] <= 2.0 ** -7, o                  # bf16 sum of two bf16 gradients, then x 1/2
 
 
-@pytest.mark.parametrize("world,scenario", [(2, "default"), (2, "hybrid"), (2, "mxfp8"), (1, "default"), (1, "mxfp8"), (2, "default-bf16")])
+@pytest.mark.parametrize("world,scenario", [(2, "default"), (2, "hybrid"), (2, "mxfp8"), (1, "default"), (1, "mxfp8"), (2, "default-bf16"),
+                                            (1, "default+nowcast"), (2, "default+nowcast"), (1, "mxfp8+nowcast"), (2, "mxfp8+nowcast"),
+                                            (1, "default+skipgrad"), (2, "hybrid+skipgrad"), (1, "default+ckpt")])
 def test_sharded_fp8_dp_matches_the_replicated_run(dev, world, scenario):
     """SURVEY.md 8f rank 3 (second half): distributed.ShardedFP8DP, the FULL_SHARD counterpart (train_multi_gpu.py:392-406, :414-445)
     -- bf16 master rows, gradients and AdamW moments of every GEMM weight at 1/world per rank, reduce-scattered wgrads out of
@@ -75,7 +77,14 @@ def test_sharded_fp8_dp_matches_the_replicated_run(dev, world, scenario):
     gather_master_weights(); and the RESIDENT state of the sharded weights is 1/world: masters, shard gradients and moments are
     measured from the tensors that exist after training.  `default-bf16` = `--mixed_precision bf16 --use_te` (no outer
     autocast: every layer's own autocast bumps the scale arena, so every sink is stale at every forward and is refreshed from
-    the shards -- the stale-master hole of round 2).  2 ranks share the box's GPU (gloo transport); world 1 runs RCCL."""
+    the shards -- the stale-master hole of round 2).  2 ranks share the box's GPU (gloo transport); world 1 runs RCCL.
+
+    Routes where the optimiser does NOT rewrite every FP8 copy (the copies must then be refreshed from the shards, not re-gathered
+    as they were): `+nowcast` (LLM_FP8_AMD_NO_OPT_WCAST=1), `+skipgrad` (one operand without a gradient at step 2: the replicated
+    forward recasts it and deposits its amax, so must the sharded one -- visible in the scale arenas).  Every case compares both
+    runs' scale arenas bitwise and checks every current FP8 copy at every forward against a fresh quantisation of the rank's shard.
+    `+ckpt`: torch's AdamW is refused for the sharded wrapper, save_pretrained refuses a model without gathered masters, and writes
+    the replicated run's tensors after gather_master_weights()."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     if world == 1:
         env.update(LLM_FP8_AMD_FORCE_DIST="1", LLM_FP8_AMD_FORCE_COLLECTIVES="1")
@@ -90,6 +99,13 @@ def test_sharded_fp8_dp_matches_the_replicated_run(dev, world, scenario):
     for o in outs:
         assert o["sharded_weights"] >= 12, o                 # 2 layers x (q, k, v, proj, fc1, fc2)
         assert o["losses_equal"] and o["eval_equal"] and o["weights_equal"], o
+        assert o["arenas_equal"], o                          # scale + amax history: same deposits in both runs
+        assert o["sinks"]["checked"] > 0 and o["sinks"]["mismatch"] == 0, o   # the FP8 copies used are this step's bytes
+        if not any(f in o["flags"] for f in ("nowcast", "skipgrad")) and not scenario.endswith("-bf16"):
+            assert o["sinks"]["train_stale"] == 0, o   # optimiser-written copies: every one gathered after the step, none refreshed
+        if "ckpt" in o["flags"]:
+            c = o["ckpt"]
+            assert c["torch_adamw_refused"] and c["save_before_gather_refused"] and c["files_equal"], o
         assert all(l == l for l in o["losses"]), o
         m = o["mem"]
         assert m["master_bytes"] * world == m["sharded_logical_bytes"], m       # bf16 master rows: exactly 1 / world

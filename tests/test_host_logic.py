@@ -133,3 +133,42 @@ def test_rmsnorm_bwd_width_tests_cover_every_dispatcher_instance():
     assert {1, 2, 4} >= {w for _, w in inst}
     assert sorted(v for v, _ in inst) == sorted(widths.RB_VECS)
     assert widths.RB_WIDTHS == tuple(512 * v for v in widths.RB_VECS)
+
+
+def test_sink_stamp_follows_the_shard_of_a_row_sharded_weight():
+    """module.WeightSink / MXWeightSink declare their FP8 copies current while the parts' versions (and, delayed scaling, the scale
+    arena's generation) are what they were at emission.  A row-sharded weight (distributed.ShardedFP8DP) is written through its
+    shard only -- the module's Parameter is a storage-less view whose version never moves -- so the shard's version must count."""
+    from types import SimpleNamespace
+    from llm_fp8_amd.distributed import _ShardHandle
+    from llm_fp8_amd.pytorch.module import MXWeightSink, WeightSink, stepped_tensor
+
+    def sharded(rows, K):
+        w = torch.nn.Parameter(torch.randn(rows, K).to(torch.bfloat16))
+        shard = torch.nn.Parameter(w.detach()[: rows // 2].clone())
+        w._mi_sharded = _ShardHandle(None, shard, 0, rows // 2)
+        w.data = torch.zeros(1, dtype=w.dtype).expand(w.shape)
+        return w, shard
+
+    arena = SimpleNamespace(generation=0)
+    mf = SimpleNamespace(arena=arena, scale=lambda i: torch.ones(1), amax=lambda i: torch.zeros(1))
+    (w1, s1), (w2, s2) = sharded(64, 64), sharded(32, 64)
+    plain = torch.nn.Parameter(torch.randn(32, 64).to(torch.bfloat16))
+    assert stepped_tensor(w1) is s1 and stepped_tensor(plain) is plain   # what ClippedAdamW counts as rewritten
+    for make in (lambda ws, ns: WeightSink(ws, ns, sum(ns), 64, "cpu", mf, 1), lambda ws, ns: MXWeightSink(ws, ns, sum(ns), 64, "cpu")):
+        for parts, shards in (([w1, w2], [s1, s2]), ([plain], [plain])):
+            sink = make(parts, [p.shape[0] for p in parts])
+            assert not sink.fresh()
+            sink.mark()
+            assert sink.fresh()
+            for t in shards:
+                v = tuple(p._version for p in parts)
+                torch.autograd.graph.increment_version(t)   # what ClippedAdamW does after writing through raw addresses
+                assert not sink.fresh(), "a write to a shard left the sink current"
+                sink.mark()
+                assert sink.fresh()
+                if t is not plain:
+                    assert tuple(p._version for p in parts) == v   # the module Parameter's own counter did not move
+            if isinstance(sink, WeightSink):
+                arena.generation += 1
+                assert not sink.fresh()
