@@ -131,7 +131,10 @@ class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
-        do = do if (do.stride(3) == 1 and do.stride(2) == do.shape[3] and do.stride(0) == do.shape[1] * do.stride(1)) else do.contiguous()
+        # the launcher takes dO only as a bshd view with a token stride of a multiple of 8 at a 16-byte aligned address
+        ok = (do.stride(3) == 1 and do.stride(2) == do.shape[3] and do.stride(0) == do.shape[1] * do.stride(1)
+              and do.stride(1) % 8 == 0 and do.data_ptr() % 16 == 0)
+        do = do if ok else do.clone(memory_format=torch.contiguous_format)  # (a misaligned contiguous view's .contiguous() is itself)
         dq, dk, dv = ops.attn_bwd(do, q, k, v, o, lse, ctx.scale, ctx.causal)
         return dq, dk, dv, None, None
 

@@ -735,15 +735,22 @@ def _bshd_ok(t: torch.Tensor, D: int):
     assert t.stride(0) == t.shape[1] * t.stride(1), "batch and sequence must collapse to one token stride"
 
 
-def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True):
-    """Attention core.  q [B, S, H, D], k/v [B, S, G, D] bf16 (views with a token stride are fine) -> (o [B, S, H, D], lse [B, H, S])."""
+def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True, out=None):
+    """Attention core.  q [B, S, H, D], k/v [B, S, G, D] bf16 (views with a token stride are fine) -> (o [B, S, H, D], lse [B, H, S]).
+    `out` = optional preallocated (o, lse): o may be a view with its own token stride, lse is contiguous fp32."""
     _dev(q, k, v)
     B, S, H, D = q.shape
     G = k.shape[2]
     for t in (q, k, v):
         _bshd_ok(t, D)
-    o = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    if out is None:
+        o = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
+        lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    else:
+        o, lse = out
+        _dev(o, lse)
+        _bshd_ok(o, D)
+        assert o.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1),
             v.stride(1), o.stride(1), float(scale), int(causal), _stream())
     t = KernelTimer.active
@@ -765,14 +772,17 @@ def attn_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     G = k.shape[2]
     for t in (q, k, v, o, do):
         _bshd_ok(t, D)
+    assert o.shape == do.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
     if out is None:
         dq = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
         dk = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
         dv = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
     else:
         dq, dk, dv = out
+        _dev(dq, dk, dv)
         for t in out:
             _bshd_ok(t, D)
+        assert dq.shape == q.shape and dk.shape == dv.shape == k.shape
     delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), delta.data_ptr(),
             dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1), v.stride(1), o.stride(1),

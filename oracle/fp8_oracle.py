@@ -541,8 +541,8 @@ def adamw_step_f64(p_bits, g_bits, m_bits, v_bits, step: int, lr: float, beta1: 
 
 
 def attention_f64(q_bits, k_bits, v_bits, scale: float, causal: bool = True):
-    """Attention core (te_llama.py:45-56: causal, GQA): q [B,S,H,D], k/v [B,S,G,D] bf16 bits -> (o f32 [B,S,H,D], lse_log2 [B,H,S]).
-    float64 math; lse in the log2 domain of the scaled scores (the layout the HIP kernel keeps for its backward)."""
+    """Attention core (te_llama.py:45-56: causal, GQA): q [B,S,H,D], k/v [B,S,G,D] bf16 bits -> (o [B,S,H,D], lse_log2 [B,H,S]).
+    float64 math and results; lse in the log2 domain of the scaled scores (the layout the HIP kernel keeps for its backward)."""
     q = bf16_bits_to_f32(q_bits).astype(np.float64)
     k = bf16_bits_to_f32(k_bits).astype(np.float64)
     v = bf16_bits_to_f32(v_bits).astype(np.float64)
@@ -562,15 +562,18 @@ def attention_f64(q_bits, k_bits, v_bits, scale: float, causal: bool = True):
         l = p.sum(-1, keepdims=True)
         o[:, :, h] = np.einsum("bqk,bkd->bqd", p / l, v[:, :, g])
         lse[:, h] = (m[..., 0] + np.log(l[..., 0])) / np.log(2.0)
-    return o.astype(np.float32), lse.astype(np.float32)
+    return o, lse
 
 
-def attention_bwd_f64(q_bits, k_bits, v_bits, do_bits, scale: float, causal: bool = True):
-    """(dq, dk, dv) float32 of attention_f64's o w.r.t. its inputs, given dO (bf16 bits)."""
+def attention_bwd_f64(q_bits, k_bits, v_bits, do_bits, scale: float, causal: bool = True, o_bits=None):
+    """(dq, dk, dv) float64 of attention_f64's o w.r.t. its inputs, given dO (bf16 bits).
+    delta = rowsum(P * dP) = rowsum(dO * o) exactly; with `o_bits` (the forward's stored bf16 O, [B,S,H,D]) it is
+    rowsum(dO * O) of that O instead, the quantity the HIP backward (like flash attention's) computes."""
     q = bf16_bits_to_f32(q_bits).astype(np.float64)
     k = bf16_bits_to_f32(k_bits).astype(np.float64)
     v = bf16_bits_to_f32(v_bits).astype(np.float64)
     do = bf16_bits_to_f32(do_bits).astype(np.float64)
+    o = None if o_bits is None else bf16_bits_to_f32(o_bits).astype(np.float64)
     B, S, H, D = q.shape
     G = k.shape[2]
     rep = H // G
@@ -585,7 +588,8 @@ def attention_bwd_f64(q_bits, k_bits, v_bits, do_bits, scale: float, causal: boo
         p /= p.sum(-1, keepdims=True)
         dv[:, :, g] += np.einsum("bqk,bqd->bkd", p, do[:, :, h])
         dp = np.einsum("bqd,bkd->bqk", do[:, :, h], v[:, :, g])
-        ds = p * (dp - (p * dp).sum(-1, keepdims=True)) * scale
+        delta = (p * dp).sum(-1, keepdims=True) if o is None else (do[:, :, h] * o[:, :, h]).sum(-1, keepdims=True)
+        ds = p * (dp - delta) * scale
         dq[:, :, h] = np.einsum("bqk,bkd->bqd", ds, k[:, :, g])
         dk[:, :, g] += np.einsum("bqk,bqd->bkd", ds, q[:, :, h])
-    return dq.astype(np.float32), dk.astype(np.float32), dv.astype(np.float32)
+    return dq, dk, dv

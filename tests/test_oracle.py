@@ -178,3 +178,53 @@ def test_fp8_mismatch_classifier():
     got[4] = O.fp8_encode_sat(np.array([104.0], np.float32), O.E4M3)[0]  # neighbour code of 96 (98 -> 96), but 98 is no boundary (100 is)
     assert O.fp8_mismatches_near_boundary(got, v, O.E4M3) == (2, 1)
     assert O.fp8_mismatches_near_boundary(got, v, O.E4M3, abs_slack=np.full(5, 10.0)) == (2, 0)
+
+
+@pytest.mark.parametrize("B,S,H,G,D", [(2, 40, 3, 3, 64), (1, 96, 6, 2, 128), (2, 40, 8, 2, 64), (1, 96, 4, 1, 128)])
+@pytest.mark.parametrize("causal", [True, False])
+def test_attention_oracle_against_torch_float64_autograd(B, S, H, G, D, causal):
+    """attention_f64 / attention_bwd_f64 (hand-derived backward) against torch float64 on the CPU: an explicit softmax with
+    repeat_interleave for GQA, differentiated by autograd, and scaled_dot_product_attention for the forward."""
+    g = torch.Generator().manual_seed(S * H + D + causal)
+    q, k, v = (torch.randn(B, S, n, D, generator=g).to(torch.bfloat16) for n in (H, G, G))
+    do = torch.randn(B, S, H, D, generator=g).to(torch.bfloat16)
+    q = (q.float() * 2.0).to(torch.bfloat16)
+    scale = D ** -0.5
+    o, lse = O.attention_f64(_bf16_bits(q), _bf16_bits(k), _bf16_bits(v), scale, causal)
+    dq, dk, dv = O.attention_bwd_f64(_bf16_bits(q), _bf16_bits(k), _bf16_bits(v), _bf16_bits(do), scale, causal)
+    assert o.dtype == lse.dtype == dq.dtype == dk.dtype == dv.dtype == np.float64
+
+    qr, kr, vr = (t.double().transpose(1, 2).requires_grad_(True) for t in (q, k, v))  # [B, n, S, D]
+    ke, ve = kr.repeat_interleave(H // G, 1), vr.repeat_interleave(H // G, 1)
+    s = (qr @ ke.transpose(-1, -2)) * scale
+    if causal:
+        s = s.masked_fill(torch.triu(torch.ones(S, S, dtype=torch.bool), 1), float("-inf"))
+    o_t = torch.softmax(s, -1) @ ve
+    lse_t = torch.logsumexp(s, -1) / np.log(2.0)
+    o_t.backward(do.double().transpose(1, 2))
+    o_sdpa = torch.nn.functional.scaled_dot_product_attention(qr.detach(), ke.detach(), ve.detach(), is_causal=causal,
+                                                              scale=scale)
+
+    def close(got, ref, what):  # float64 rounding level: both sides sum O(S + D) terms of size <= max|ref| * O(1)
+        err = np.abs(got - ref).max() / np.abs(ref).max()
+        assert err < 1e-12, f"{what}: max error {err:.3g} of max|ref|"
+
+    close(o, o_t.detach().transpose(1, 2).numpy(), "o")
+    close(o, o_sdpa.transpose(1, 2).numpy(), "o vs sdpa")
+    close(lse, lse_t.detach().numpy(), "lse")
+    close(dq, qr.grad.transpose(1, 2).numpy(), "dq")
+    close(dk, kr.grad.transpose(1, 2).numpy(), "dk")
+    close(dv, vr.grad.transpose(1, 2).numpy(), "dv")
+
+    # o_bits: delta = rowsum(dO * O) of a stored bf16 O.  dS = P (dP - delta) is linear in delta, so dq and dk move by
+    # -scale P (delta' - delta) times k and q; dv does not move
+    o_bits = _bf16_bits(torch.from_numpy(o))
+    dq2, dk2, dv2 = O.attention_bwd_f64(_bf16_bits(q), _bf16_bits(k), _bf16_bits(v), _bf16_bits(do), scale, causal, o_bits=o_bits)
+    o_b = torch.from_numpy(O.bf16_bits_to_f32(o_bits).astype(np.float64)).transpose(1, 2)
+    dd = ((do.double().transpose(1, 2) * (o_b - o_t.detach())).sum(-1, keepdims=True))  # delta' - delta [B, H, S, 1]
+    p = torch.softmax(s.detach(), -1)
+    ds_shift = -scale * p * dd
+    close(dq2 - dq, (ds_shift @ ke.detach()).transpose(1, 2).numpy(), "dq shift from the stored O")
+    dk_shift = (ds_shift.transpose(-1, -2) @ qr.detach()).reshape(B, G, H // G, S, D).sum(2)
+    close(dk2 - dk, dk_shift.transpose(1, 2).numpy(), "dk shift from the stored O")
+    assert np.array_equal(dv2, dv)
