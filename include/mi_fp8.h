@@ -126,6 +126,19 @@ int mi_scale_update(float* amax_history, float* scale, float* scale_inv, const f
  * Not part of this library: the timing / ablation / stamp builds (algos 7, 8, 10-30, 46) live in the lab build
  * (tools/bin/libmi_fp8_lab.so, `make -C llm_fp8_amd/csrc lab`, compiled with -DMI_DIAG; see tools/README.md); the product
  * library returns MI_ERR_ARG for them.
+ * Leading dimensions and pointers (every algo; pinned by tests/test_gemm_contract_gpu.py): A, B and D may be views into larger
+ * buffers.  lda, ldb >= K and multiples of 16 (bytes); ldd >= N and a multiple of 4 (elements: a bf16 row may then be only 8-byte
+ * aligned, the kernels' 16-byte stores take that); A, B and D 16-byte aligned.  Anything else is MI_ERR_ARG and nothing is
+ * launched.  Only the K bytes of each operand row are read and only the N elements of each output row are written: padding
+ * columns and neighbouring rows are never touched.  The persistent algos (4, 5, 6, 9, 40-45) use 32-bit buffer offsets over
+ * rows * ld bytes: M * lda, N * ldb and 2 * M * ldd must stay below 2^31 (MI_ERR_SHAPE when asked for explicitly; 0 / 47 fall
+ * back to 3 or 1).
+ * Non-finite values propagate, they are never scrubbed: a NaN byte (0x7F / 0xFF in E4M3, 0x7D-0x7F / 0xFD-0xFF in E5M2; the casts
+ * emit 0x7F for a NaN input on purpose) makes exactly its output row (byte in A) or column (byte in B) NaN, an E5M2 +-Inf byte makes
+ * it non-finite, a NaN / +-Inf bias element gives a NaN / +-Inf column, and every other output keeps the bits it has without the
+ * poison; nothing carries over into a later launch (stream-K workspace included).  *sa_inv or *sb_inv NaN -> all NaN, Inf ->
+ * nothing finite, 0 -> +-0 (exactly the bias, with one).  A product with alpha beyond FLT_MAX is +-Inf in both output types; a
+ * finite fp32 value beyond the bf16 range rounds to +-Inf (round-to-nearest-even), it does not saturate.
  */
 int mi_gemm_fp8(const void* A, const void* B, void* D, const float* sa_inv, const float* sb_inv,
                 const void* bias_bf16, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
@@ -147,6 +160,10 @@ int mi_gemm_fp8_clock(const void* A, const void* B, void* D, const float* sa_inv
  * the idle part of the long one's last round of tiles.  All problems share fmt_a / fmt_b and the tile shape: tile_cfg
  * 0 = 256x256, 1 = 256x192, 2 = 192x256, 3 = 192x192, 4 = 256x256 on the four-wave kernel (every K_p >= 512), -1 = choose among 0-3 (M_p, N_p must be multiples of the tile, K_p of 256;
  * operands below 2 GiB; at most 64 tiles per workgroup).  Results are bitwise those of mi_gemm_fp8(algo 4) per problem.
+ * Each problem has its own leading dimensions and pointers under the rules of mi_gemm_fp8 (lda, ldb >= K, multiples of 16; ldd >= N,
+ * multiple of 4; 16-byte aligned A, B, D; M * lda, N * ldb, 2 * M * ldd < 2^31), checked per problem: MI_ERR_ARG names the
+ * offending one and nothing is launched.  NaN / Inf bytes and scales propagate as in mi_gemm_fp8 and stay inside their own
+ * problem.
  */
 typedef struct mi_gemm_problem {
   const void* A;        /* fp8 [M, K], row stride lda */
@@ -216,7 +233,13 @@ int mi_mxfp8_rope_bwd_quantize(const void* dq_bf16, const void* dk_bf16, const v
  * K8  block-scaled MXFP8 GEMM (v_mfma_scale_f32_16x16x128_f8f6f4 with per-32 E8M0 scales)
  *   D[m,n] = bf16( sum_blk 2^(sa[m,blk]+sb[n,blk]-254) * sum_{k in blk} A[m,k] B[n,k] + bias[n] )
  * A [M,K] fp8 + SA [K/32, M] u8; B [N,K] fp8 + SB [K/32, N] u8 (block-major, as mi_mxfp8_quantize emits); K multiple of 32.
- * algo: 0 = auto (persistent 256x256 kernel when M,N,K % 256 == 0 and bf16 output; else generic), 1 = generic.
+ * algo: 0 = auto (persistent 256x256 kernel when M,N,K % 256 == 0 and bf16 output; else generic), 1 = generic; 4, 5, 40-45 as in
+ * mi_gemm_fp8 (bf16 output, K % 256 == 0).  fmt_a / fmt_b are independent: all four pairs are built (HYBRID backward = E5M2 x E4M3).
+ * No leading dimensions: A, B, D and the scale arrays are tight (lda = ldb = K, ldd = N) and 16-byte aligned.
+ * A NaN data byte makes its output row / column NaN, as in mi_gemm_fp8.  An E8M0 scale byte of 0xFF is NaN (OCP MX): measured on
+ * MI355X, the scaled MFMA turns every output that block feeds into NaN -- the whole row (scale of A) or column (scale of B) -- in
+ * every algo alike (1, 4, 5, 41-43, 44), which is what the oracle computes; mi_mxfp8_quantize never emits 0xFF.  A block whose 32
+ * data bytes are all zero contributes exactly nothing under any scale byte 0 .. 0xFE: the output bits do not depend on it.
  */
 int mi_gemm_mxfp8(const void* A, const void* SA, const void* B, const void* SB, void* D,
                   const void* bias_bf16, int64_t M, int64_t N, int64_t K, int fmt_a, int fmt_b,

@@ -58,6 +58,22 @@ def test_product_library_has_no_lab_surface():
         assert rc == -1
 
 
+def test_persistent_gemms_refuse_operands_of_2_gib_by_leading_dimension():
+    """The persistent kernels address their operands with 32-bit buffer offsets over rows * ld bytes: M * lda (N * ldb, 2 M * ldd)
+    >= 2^31 is MI_ERR_SHAPE for the explicit algos 4 and 9, however small M x K itself is.  Host side only: refused before any
+    launch, the fake pointers are never dereferenced."""
+    from llm_fp8_amd import _lib
+    lib = _lib.load()
+    fake = 0x10000  # non-null, 16-byte aligned
+    M = N = 256
+    K = 512
+    big = (1 << 31) // M  # M * big == 2^31, a multiple of 16
+    for algo in (4, 9):
+        for lda, ldb, ldd in ((big, K, N), (K, big, N), (K, K, big // 2)):
+            rc = lib.mi_gemm_fp8(fake, fake, fake, fake, fake, None, M, N, K, lda, ldb, ldd, 0, 0, 0, algo, None)
+            assert rc == -2 and b"2 GiB" in lib.mi_last_error(), (algo, lda, ldb, ldd)
+
+
 def test_argument_errors_are_reported_not_thrown():
     from llm_fp8_amd import _lib
     lib = _lib.load()

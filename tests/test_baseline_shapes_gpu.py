@@ -107,6 +107,23 @@ def test_3b_full_size_block_scaled_gemm_vs_float64_oracle_sample(ops, name, M, N
     assert torch.equal(d2.float(), d.float() * 2.0)
 
 
+def test_3b_full_size_block_scaled_fc2_dgrad_e5m2_e4m3_vs_float64_oracle_sample(ops):
+    """Sibling of the test above for the HYBRID block-scaled backward: the 3B fc2 dgrad (8192 x 8192 x 3072) with an E5M2 grad_output
+    against E4M3 weights; same sample criterion, same linearity property."""
+    dev = torch.device("cuda:0")
+    name, M, N, K = next(c for c in CASES_3B if c[0] == "3b-fc2-dgrad")
+    fa, fb = O.E5M2, O.E4M3
+    gen = torch.Generator(device=dev).manual_seed(hash((M, N, K, fa)) % (2 ** 31))
+    a8, b8 = _rand_bytes((M, K), fa, gen, dev), _rand_bytes((N, K), fb, gen, dev)
+    sa = torch.randint(120, 131, (K // 32, M), generator=gen, device=dev, dtype=torch.uint8)
+    sb = torch.randint(120, 131, (K // 32, N), generator=gen, device=dev, dtype=torch.uint8)
+    d = ops.gemm_mxfp8(a8, sa, b8, sb, fa, fb)
+    assert d.shape == (M, N) and d.dtype == torch.bfloat16
+    _assert_sample_matches_float64(d, a8, b8, fa, fb, 1.0, f"mx e5m2 x e4m3 {name} {M}x{N}x{K}", sa, sb)
+    d2 = ops.gemm_mxfp8(a8, sa + 1, b8, sb, fa, fb)
+    assert torch.equal(d2.float(), d.float() * 2.0)
+
+
 GROUPED_3B = [(s, 8192, N, K) for s, (N, K) in MODELS["3b"][1].items()]
 
 

@@ -94,6 +94,43 @@ def test_linear_mxfp8_vs_oracle(te, dev):
     np.testing.assert_allclose(_f(lin.bias.grad), O.bf16_bits_to_f32(db_r), rtol=2 ** -7, atol=1e-3)
 
 
+def test_linear_mxfp8_hybrid_vs_oracle(te, dev):
+    """MXFP8BlockScaling(fp8_format=HYBRID): forward E4M3 x E4M3; grad_output quantised as E5M2 (row-wise blocks for dgrad, column-wise
+    for wgrad) and the (E5M2, E4M3) block-scaled dgrad and wgrad GEMMs.  Built like test_linear_mxfp8_vs_oracle."""
+    _, Format, MXFP8BlockScaling = _recipes()
+    recipe = MXFP8BlockScaling(fp8_format=Format.HYBRID)
+    M, K, N = 64, 128, 96
+    g = torch.Generator().manual_seed(18)
+    lin = te.Linear(K, N, bias=True, params_dtype=torch.bfloat16, device=dev)
+    with torch.no_grad():
+        lin.weight.copy_((torch.randn(N, K, generator=g) * 0.05).to(torch.bfloat16))
+        lin.bias.copy_(torch.randn(N, generator=g).to(torch.bfloat16))
+    x = (torch.randn(M, K, generator=g) * torch.exp(torch.randn(M, 1, generator=g))).to(torch.bfloat16)
+    dy = (torch.randn(M, N, generator=g) * torch.exp(torch.randn(M, 1, generator=g) * 2) / 32).to(torch.bfloat16)
+    xd = x.to(dev).requires_grad_(True)
+    with te.fp8_autocast(enabled=True, fp8_recipe=recipe):
+        y = lin(xd)
+    y.backward(dy.to(dev))
+    xb, wb, gb = bf16_bits(x), bf16_bits(lin.weight), bf16_bits(dy)
+    fwd, bwd = O.E4M3, O.E5M2
+    x8, xe = O.mxfp8_quantize_rowwise(xb, fwd)
+    w8, we = O.mxfp8_quantize_rowwise(wb, fwd)
+    y_r = O.gemm_mxfp8_tn(x8, xe, w8, we, fwd, fwd, bf16_bits(lin.bias))
+    g8, ge = O.mxfp8_quantize_rowwise(gb, bwd)        # [M, N], blocks along N (dgrad contracts N)
+    wt8, wte = O.mxfp8_quantize_colwise(wb, fwd)      # [K, N]
+    dx_r = O.gemm_mxfp8_tn(g8, ge, wt8, wte, bwd, fwd)
+    gt8, gte = O.mxfp8_quantize_colwise(gb, bwd)      # [N, M], blocks along M (wgrad contracts M)
+    xt8, xte = O.mxfp8_quantize_colwise(xb, fwd)      # [K, M]
+    dw_r = O.gemm_mxfp8_tn(gt8, gte, xt8, xte, bwd, fwd)
+    # the E5M2 quantisation is what is new: it must differ from the E4M3 one, or the comparison below could not tell them apart
+    assert not np.array_equal(g8, O.mxfp8_quantize_rowwise(gb, fwd)[0])
+    db_r = O.f32_to_bf16_bits(O.bf16_bits_to_f32(gb).astype(np.float64).sum(axis=0).astype(np.float32))
+    assert_gemm_close(_f(y), O.bf16_bits_to_f32(y_r), "mx hybrid y")
+    assert_gemm_close(_f(xd.grad), O.bf16_bits_to_f32(dx_r), "mx hybrid dx")
+    assert_gemm_close(_f(lin.weight.grad), O.bf16_bits_to_f32(dw_r), "mx hybrid dw")
+    np.testing.assert_allclose(_f(lin.bias.grad), O.bf16_bits_to_f32(db_r), rtol=2 ** -7, atol=1e-3)
+
+
 def test_layernorm_linear_split_weights_share_one_slot(te, dev):
     """q|k|v as three Parameters == one Linear on the concatenated weight (same single amax/scale slot)."""
     DelayedScaling, Format, _ = _recipes()
