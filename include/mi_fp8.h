@@ -59,8 +59,9 @@ extern "C" {
  *   4  round 3: diagnostic algo values and mi_attn_fwd_diag moved out (lab build, -DMI_DIAG); mi_gemm_fp8 algos 6, 9, 47 and
  *      mi_gemm_fp8_grouped tile_cfg 4 (four-wave kernel); mi_gemm_fp8_clock; mi_swiglu_cast_bias, mi_dswiglu_cast_bias,
  *      mi_add_bias_rmsnorm_stats (bias fused into the consumer of the GEMM output)
+ *   5  mi_gemm_mxfp8_grouped (a Linear's block-scaled dgrad + wgrad in one persistent launch)
  */
-#define MI_ABI_VERSION 4
+#define MI_ABI_VERSION 5
 int mi_abi_version(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
 const char* mi_last_error(void);
@@ -244,6 +245,33 @@ int mi_mxfp8_rope_bwd_quantize(const void* dq_bf16, const void* dk_bf16, const v
 int mi_gemm_mxfp8(const void* A, const void* SA, const void* B, const void* SB, void* D,
                   const void* bias_bf16, int64_t M, int64_t N, int64_t K, int fmt_a, int fmt_b,
                   int out_dtype, int algo, void* stream);
+
+/*
+ * Grouped form of mi_gemm_mxfp8 (ABI 5): 1 to 4 independent block-scaled problems, bf16 outputs, no bias, in ONE persistent
+ * launch whose workgroups walk a shared tile list, longest tiles first -- what mi_gemm_fp8_grouped is to mi_gemm_fp8: a Linear's
+ * MXFP8 dgrad + wgrad pay one ramp and one exposed epilogue, and the short problem's tiles fill the long one's last round.
+ * All problems share fmt_a / fmt_b (all four pairs are built: HYBRID backward = E5M2 x E4M3) and the tile shape: tile_cfg
+ * 0 = 256x256, 1 = 256x192, 2 = 192x256, 3 = 192x192 (the shapes of mi_gemm_mxfp8 algos 40-43; all four are built), -1 = choose
+ * among those that divide every problem.  tile_cfg 4 is MI_ERR_ARG: the four-wave kernel has no block-scaled main loop.
+ * Operands as in mi_gemm_mxfp8: tight (lda = ldb = K, ldd = N), scales block-major; A, SA, B, SB, D 16-byte aligned.  Every M_p,
+ * N_p a multiple of the tile, every K_p of 256, M K, N K and 2 M N below 2^31, at most 64 tiles per workgroup.
+ * Each problem's output is bit for bit what mi_gemm_mxfp8(algo 4) writes for that problem alone, whatever the tile shape (one
+ * fp32 summation order per output element).  A NaN data byte or a 0xFF scale byte poisons exactly its row (A side) or column
+ * (B side) of its own problem, as documented for mi_gemm_mxfp8; nothing crosses a problem boundary.
+ * Everything refused is refused on the host before anything is launched or dereferenced, and mi_last_error() names the
+ * offending problem: MI_ERR_ARG for n outside 1..4, a null or misaligned pointer, a bad fmt or tile_cfg; MI_ERR_SHAPE for
+ * K % 256 != 0, a shape the tile (or, with -1, any tile) does not divide, an operand of 2 GiB or more, more than 64 tiles per
+ * workgroup.
+ */
+typedef struct mi_gemm_mx_problem {
+  const void* A;   /* fp8 [M, K] tight */
+  const void* SA;  /* E8M0 [K/32, M] block-major */
+  const void* B;   /* fp8 [N, K] tight */
+  const void* SB;  /* E8M0 [K/32, N] block-major */
+  void* D;         /* bf16 [M, N] tight */
+  int64_t M, N, K;
+} mi_gemm_mx_problem;
+int mi_gemm_mxfp8_grouped(const mi_gemm_mx_problem* problems, int n, int fmt_a, int fmt_b, int tile_cfg, void* stream);
 
 /*
  * RoPE fused with the q/k/v split of the QKV projection output  [TE applies a fused RoPE kernel between

@@ -12,7 +12,7 @@ LAB_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "bin", "libmi_fp8_l
 
 MI_FMT_E4M3 = 0
 MI_FMT_E5M2 = 1
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -25,6 +25,11 @@ class GemmProblem(ctypes.Structure):
                 ("lda", ctypes.c_int64), ("ldb", ctypes.c_int64), ("ldd", ctypes.c_int64)]
 
 
+class GemmMxProblem(ctypes.Structure):
+    """include/mi_fp8.h `mi_gemm_mx_problem`."""
+    _fields_ = [("A", ctypes.c_void_p), ("SA", ctypes.c_void_p), ("B", ctypes.c_void_p), ("SB", ctypes.c_void_p),
+                ("D", ctypes.c_void_p), ("M", ctypes.c_int64), ("N", ctypes.c_int64), ("K", ctypes.c_int64)]
+
 # name -> argtypes (all return int unless noted); mirrors include/mi_fp8.h exactly
 SIGNATURES = {
     "mi_abi_version": [],
@@ -34,6 +39,7 @@ SIGNATURES = {
     "mi_transpose_u8": [_p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "mi_scale_update": [_p, _p, _p, _p, _c_int, _c_int, _c_i64, _c_int, _c_int, _p],
     "mi_gemm_fp8_grouped": [_p, _c_int, _c_int, _c_int, _c_int, _p],
+    "mi_gemm_mxfp8_grouped": [_p, _c_int, _c_int, _c_int, _c_int, _p],
     "mi_gemm_fp8": [_p, _p, _p, _p, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
                     _c_int, _c_int, _c_int, _c_int, _p],
     "mi_mxfp8_quantize": [_p, _p, _p, _p, _p, _c_i64, _c_i64, _c_int, _p],

@@ -115,8 +115,8 @@ struct GroupProblem {
   const uint8_t* A;
   const uint8_t* B;
   uint16_t* D;
-  const float* sa_inv;
-  const float* sb_inv;
+  union { const float* sa_inv; const uint8_t* SA; };  // per-tensor: device scalars; MX: E8M0 block scales [K/32, M] / [K/32, N]
+  union { const float* sb_inv; const uint8_t* SB; };
   int lda, ldb, ldd, nk;
   int tiles_m, tiles_n, tile_base, ntiles;
   int a_bytes, b_bytes, d_bytes, pad;

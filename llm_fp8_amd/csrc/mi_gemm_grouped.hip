@@ -10,8 +10,14 @@
 //
 // Kernel = the persistent 8-phase kernel of mi_gemm.hip (same LDS image, same two-wave-group phase schedule, same distributed
 // whole-line epilogue) with every per-problem quantity -- buffer descriptors, leading dimensions, K-tile count, alpha, output
-// -- carried per prefetch cursor and switched at tile boundaries.  Per-tensor scaling only (no MX, no bias): what dgrad / wgrad
-// need.  All problems share the operand formats (FA, FB) and the tile shape.
+// -- carried per prefetch cursor and switched at tile boundaries.  No bias: what dgrad / wgrad need.  All problems share the
+// operand formats (FA, FB) and the tile shape.
+//
+// MX = true (mi_gemm_mxfp8_grouped) is the same kernel with the block-scale path of gemm_256_p8<MX> (mi_gemm.hip): one 256-byte
+// LDS-DMA run of E8M0 scales per wave and K-tile (wave w: operand w >> 2, k-block w & 3) for the NEXT step at the head of phase
+// 0, two 4-KiB scale slots at a 272-byte k-block stride, row-interleaved A fragments (PERM) so that a lane's fragment scales
+// are one LDS read.  The scale descriptor, the scale row count and the scale row of the tile belong to the cursor's problem and
+// switch at tile boundaries like rsA / rsB; all of it is wave-uniform.  alpha is 1: nothing of a problem is read up front.
 #include "mi_gemm_dev.h"
 #include <algorithm>
 #include <cstring>
@@ -26,6 +32,8 @@ namespace mi {
 struct Cursor {
   int ti, kt, nk, oa, ob, lda, ldb;
   rsrc_t rsA, rsB;
+  rsrc_t rsS;  // MX: this wave's scale operand (SA: waves 0-3, SB: waves 4-7) of the cursor's problem
+  int ss, so;  // MX: scale rows of that operand (M or N), and tile's first row + this wave's k-block * rows
   int va0, va1, vb0, vb1;  // per-lane byte offsets (row * ld + chunk) of the wave's first piece of each half-tile: recomputed
                            // only when the cursor enters a tile (the leading dimensions belong to the tile's problem)
 };
@@ -36,13 +44,19 @@ struct Epi {
   float alpha;
 };
 
-template <int FA, int FB, int MA1, int NB1>
+template <int FA, int FB, int MA1, int NB1, bool MX = false>
 __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
   constexpr int RA0 = 64, RA1 = 16 * MA1, RB0 = 32, RB1 = 16 * NB1;
   constexpr int TBM = 2 * (RA0 + RA1), TBN = 4 * (RB0 + RB1);
   constexpr int nA1 = MA1 / 2, nB1 = NB1;
   constexpr int W = nA1 + nB1 + 4;
-  __shared__ __attribute__((aligned(16))) uint8_t lds[kLdsBytes];
+  constexpr int EX = MX ? 1 : 0;  // extra LDS-DMA op per K-tile at the head of phase 0 (the scales of the next step)
+  constexpr bool PERM = MX;       // A fragments row-interleaved: fragment i, row slot s <-> row F * s + i of the half (mi_gemm.hip)
+  // MX: behind the operand buffers, [2 slots of 4 KiB][operand A, B][4 k-blocks][272 B] of E8M0 scales.  (Same array on purpose: with
+  // an array of their own hipcc put `s_waitcnt vmcnt(0)` in front of every fragment read.)
+  constexpr int kSK = 272, kSOp = 4 * kSK, kSSlot = 4096;
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kLdsBytes + (MX ? 2 * kSSlot : 0)];
+  uint8_t* const slds = lds + kLdsBytes;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
@@ -63,7 +77,7 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
 #pragma unroll
   for (int q = 0; q < kMaxGroup; ++q) {
     float a = 1.0f;
-    if (q < ga.n) a = (*ga.p[q].sa_inv) * (*ga.p[q].sb_inv);
+    if (!MX && q < ga.n) a = (*ga.p[q].sa_inv) * (*ga.p[q].sb_inv);
     alpha_of[q] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a)));
   }
 
@@ -124,9 +138,10 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
     chunk = ((ln & 7) ^ swz_f(lr)) * 16;
     const int l0 = wave * 16 + lr;
     const int la = wave * nA1 * 8 + lr, lb = wave * nB1 * 8 + lr;
-    a0 = (l0 / RA0) * (RA0 + RA1) + l0 % RA0;
+    const int p0 = l0 % RA0, p1 = la % RA1;
+    a0 = (l0 / RA0) * (RA0 + RA1) + (PERM ? 4 * (p0 & 15) + (p0 >> 4) : p0);
     b0 = (l0 / RB0) * (RB0 + RB1) + l0 % RB0;
-    a1 = (la / RA1) * (RA0 + RA1) + RA0 + la % RA1;
+    a1 = (la / RA1) * (RA0 + RA1) + RA0 + (PERM ? MA1 * (p1 & 15) + (p1 >> 4) : p1);
     b1 = (lb / RB1) * (RB0 + RB1) + RB0 + lb % RB1;
   };
 
@@ -144,6 +159,12 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
     c.ob = rb * P.ldb;
     c.rsA = __builtin_amdgcn_make_buffer_rsrc((void*)P.A, 0, P.a_bytes, 0x00020000);
     c.rsB = __builtin_amdgcn_make_buffer_rsrc((void*)P.B, 0, P.b_bytes, 0x00020000);
+    if (MX) {  // block-major scales [K/32, rows]: rows = the problem's M (A side) or N (B side)
+      const bool s_is_b = wave >= 4;
+      c.ss = s_is_b ? P.tiles_n * TBN : P.tiles_m * TBM;
+      c.so = (s_is_b ? rb : ra) + (wave & 3) * c.ss;
+      c.rsS = __builtin_amdgcn_make_buffer_rsrc((void*)(s_is_b ? P.SB : P.SA), 0, P.nk * 4 * c.ss, 0x00020000);
+    }
     int a0, a1, b0, b1, ch;
     stage_rows(a0, a1, b0, b1, ch);
     c.va0 = a0 * P.lda + ch;
@@ -164,7 +185,15 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       if (i < n)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(c.rsA, LDS_PTR(lds_half + (wave * n + i) * 1024), 16, voff, soff + i * 8 * c.lda, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(c.rsA, LDS_PTR(lds_half + (wave * n + i) * 1024), 16, voff, soff + i * (PERM ? 32 : 8) * c.lda, 0, 0);
+  };
+  // MX: the 256 scale bytes of (this wave's operand and k-block, the cursor's K-tile, the tile's rows) into scale slot `slot`: ONE
+  // LDS-DMA op per wave and K-tile, 16 lanes x 16 B.  (As 64 lanes x 4 B the 256 x 256 variant spilled a VGPR.)  A 192-row tile
+  // reads 256 bytes all the same: what lies behind its rows is never used, and past the array the descriptor returns 0.
+  auto stage_scales = [&](const Cursor& c, int slot) {
+    if (MX && lane < 16)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(c.rsS, LDS_PTR(slds + slot * kSSlot + (wave >> 2) * kSOp + (wave & 3) * kSK), 16, lane * 16,
+                                               c.kt * 4 * c.ss + c.so, 0, 0);
   };
   auto stage_b = [&](const Cursor& c, int kind, int n, uint8_t* lds_half) {
     const int soff = c.ob + c.kt * BK, voff = kind == kB0 ? c.vb0 : c.vb1;
@@ -194,6 +223,7 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
   uint8_t* const buf0 = lds;
   uint8_t* const buf1 = lds + kBufBytes;
   // prologue: step 0 complete, (step 1: A0, B0) in flight
+  stage_scales(c0, 0);
   stage_a(c0, kA0, 2, buf0 + kOffA0);
   stage_b(c0, kB0, 2, buf0 + kOffB0);
   stage_b(c0, kB1, nB1, buf0 + kOffB1);
@@ -246,7 +276,8 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
       return (v4i){(int)sx[0], (int)sy[0], (int)sx[1], (int)sy[1]};
     };
     auto store_row = [&](int i, const v4i& o0, const v4i& o1) __attribute__((always_inline)) {
-      const int rowoff = e.d_off + ((a * RA0 + i * 16) * e.ldd) * 2;
+      constexpr int kRs = PERM ? F : 1;  // PERM: lane row slot s of fragment i holds row F * s + i of the half
+      const int rowoff = e.d_off + ((a * RA0 + (PERM ? i : i * 16)) * e.ldd) * 2;
       if (NB1 == 2) {
         const bool lo = fr < 8;
         v4i x, y;
@@ -257,13 +288,13 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
           x[k] = lo ? o0[k] : r;
           y[k] = lo ? r : o1[k];
         }
-        const int dvo = ((wr * (RA0 + RA1) + (fr & 7)) * e.ldd + wc * (RB0 + RB1) + (fr >> 3) * RB0 + ecol) * 2;
+        const int dvo = ((wr * (RA0 + RA1) + kRs * (fr & 7)) * e.ldd + wc * (RB0 + RB1) + (fr >> 3) * RB0 + ecol) * 2;
         __builtin_amdgcn_raw_buffer_store_b128((mi::v4u)x, e.rsD, dvo, rowoff, 16);
         asm volatile("s_nop 1" ::"v"(x) : "memory");
-        __builtin_amdgcn_raw_buffer_store_b128((mi::v4u)y, e.rsD, dvo, rowoff + 8 * e.ldd * 2, 16);
+        __builtin_amdgcn_raw_buffer_store_b128((mi::v4u)y, e.rsD, dvo, rowoff + 8 * kRs * e.ldd * 2, 16);
         asm volatile("s_nop 1" ::"v"(y) : "memory");
       } else {
-        const int dvo = ((wr * (RA0 + RA1) + fr) * e.ldd + wc * (RB0 + RB1)) * 2;
+        const int dvo = ((wr * (RA0 + RA1) + kRs * fr) * e.ldd + wc * (RB0 + RB1)) * 2;
         __builtin_amdgcn_raw_buffer_store_b128((mi::v4u)o0, e.rsD, dvo + ecol * 2, rowoff, 16);
         asm volatile("s_nop 1" ::"v"(o0) : "memory");
         typedef unsigned int v2u __attribute__((ext_vector_type(2)));
@@ -298,7 +329,7 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
   // ---- one K-tile = 4 phases (mi_gemm.hip: ktile).  Waits: see the table there; stores per phase 4 | 4 | MA1 | MA1.
 #define MI_WAIT_SYNC(MODE_, flag, PH)                                                                              \
   {                                                                                                                \
-    constexpr int kAllow = (PH) == 0 ? W - nA1 : (PH) == 1 ? W : (PH) == 2 ? W - 2 : W - nB1;                      \
+    constexpr int kAllow = (PH) == 0 ? W + EX - nA1 : (PH) == 1 ? W + EX : (PH) == 2 ? W + EX - 2 : W - nB1;       \
     constexpr int kX = (MODE_) == 0 ? 0                                                                            \
                      : (MODE_) == 1 ? ((PH) == 0 ? 4 : (PH) == 1 ? 8 : (PH) == 2 ? 8 + MA1 : 8 + 2 * MA1)          \
                                     : ((PH) <= 1 ? 4 + 2 * MA1 : (PH) == 2 ? MA1 : 0);                             \
@@ -314,34 +345,79 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
   _Pragma("unroll") for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(EXPR));
 
   v8i af[4], b0f[2], b1f[2];
-  auto ktile = [&](auto mode_c, uint8_t* cur, uint8_t* oth, bool flag, const Epi& pe) {
+  // MX: block scales of the current K-tile -- A side: the lane's 4 (half 0) / MA1 (half 1) fragment scales packed in one register
+  // (byte i = fragment i, selected by the MFMA's op_sel); B side: one byte per fragment
+  int as0 = kUnitScale, as1 = kUnitScale, b0s[2] = {kUnitScale, kUnitScale}, b1s[2] = {kUnitScale, kUnitScale};
+  // Per-lane LDS byte addresses of this lane's scales in slot 0 (k-block = lane >> 4, row slot = lane & 15); slot 1, the second
+  // half and the B fragments are immediate offsets away.  Half 1 of a 192-row tile holds 2 bytes per row slot, not 4.  Recomputed
+  // at the top of every K-tile from the lane id (a handful of VALU), not kept: the 256 x 256 variant has no VGPR to spare for them.
+  auto scale_addrs = [&](int& sc_a, int& sc_a1, int& sc_b) __attribute__((always_inline)) {
+    int ln;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+    const int sfr = ln & 15;
+    const int s0 = (int)(size_t)LDS_PTR(slds) + (ln >> 4) * kSK;
+    sc_a = s0 + wr * (RA0 + RA1) + 4 * sfr;
+    sc_a1 = s0 + wr * (RA0 + RA1) + (MA1 == 4 ? 4 : 2) * sfr;
+    sc_b = s0 + kSOp + wc * (RB0 + RB1) + sfr;
+  };
+  auto mma = [&](auto i_c, const v8i& a_, const v8i& b_, v4f& c_, int sa_, int sb_) __attribute__((always_inline)) {
+    constexpr int I = decltype(i_c)::value;
+    if (MX) c_ = mfma_ba_sel<FA, FB, I>(a_, b_, c_, sa_, sb_);
+    else c_ = mfma_ba<FA, FB>(a_, b_, c_, kUnitScale, kUnitScale);
+  };
+  auto mma_i = [&](int i, const v8i& a_, const v8i& b_, v4f& c_, int sa_, int sb_) __attribute__((always_inline)) {
+    switch (i) {
+      case 0: mma(c0_t{}, a_, b_, c_, sa_, sb_); break;
+      case 1: mma(c1_t{}, a_, b_, c_, sa_, sb_); break;
+      case 2: mma(c2_t{}, a_, b_, c_, sa_, sb_); break;
+      default: mma(std::integral_constant<int, 3>{}, a_, b_, c_, sa_, sb_); break;
+    }
+  };
+  auto ktile = [&](auto mode_c, auto slot_c, uint8_t* cur, uint8_t* oth, bool flag, const Epi& pe) {
     constexpr int MODE = decltype(mode_c)::value;
-    constexpr bool ZC = MODE == 1;
+    constexpr int SLOT = decltype(slot_c)::value;  // scale slot of this step = its LDS buffer
+    // MX has no unit-scale zero-C form: its quadrants are zeroed by v_mov as the epilogue converts them (epi_part, zero = MX)
+    constexpr bool ZC = MODE == 1 && !MX;
     // ---- phase 0: C[0][*][0][*]
     if (MODE == 1) {
+      stage_scales(c1, SLOT ^ 1);
       stage_b(c1, kB1, nB1, oth + kOffB1);
-      if (flag) epi_part(c0_t{}, c0_t{}, pe, false);
+      if (flag) epi_part(c0_t{}, c0_t{}, pe, MX);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) b0f[j] = read_frag(cur + kOffB0, wc * 2 + j, lane);
 #pragma unroll
     for (int i = 0; i < 4; ++i) af[i] = read_frag(cur + kOffA0, wr * 4 + i, lane);
-    if (MODE != 1) stage_b(c1, kB1, nB1, oth + kOffB1);
+    if (MX) {  // every scale of this K-tile up front (inline asm: consumed behind MI_WAIT_SYNC's lgkmcnt(0), like the fragments)
+      int sc_a, sc_a1, sc_b;
+      scale_addrs(sc_a, sc_a1, sc_b);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) asm volatile("ds_read_u8 %0, %1 offset:%2" : "=v"(b0s[j]) : "v"(sc_b), "n"(SLOT * kSSlot + j * 16));
+#pragma unroll
+      for (int j = 0; j < NB1; ++j) asm volatile("ds_read_u8 %0, %1 offset:%2" : "=v"(b1s[j]) : "v"(sc_b), "n"(SLOT * kSSlot + RB0 + j * 16));
+      asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(as0) : "v"(sc_a), "n"(SLOT * kSSlot));
+      if (MA1 == 4) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(as1) : "v"(sc_a1), "n"(SLOT * kSSlot + RA0));
+      else asm volatile("ds_read_u16 %0, %1 offset:%2" : "=v"(as1) : "v"(sc_a1), "n"(SLOT * kSSlot + RA0));
+    }
+    if (MODE != 1) {
+      stage_scales(c1, SLOT ^ 1);
+      stage_b(c1, kB1, nB1, oth + kOffB1);
+    }
     MI_WAIT_SYNC(MODE, flag, 0)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         if (ZC) mfma_ba_zero<FA, FB>(af[i], b0f[j], acc[0][i][0][j], kUnitScale);
-        else acc[0][i][0][j] = mfma_ba<FA, FB>(af[i], b0f[j], acc[0][i][0][j], kUnitScale, kUnitScale);
+        else mma_i(i, af[i], b0f[j], acc[0][i][0][j], as0, b0s[j]);
       }
     MI_PIN(4, 2, acc[0][i][0][j])
     MI_PHASE_END();
     // ---- phase 1: C[0][*][1][*]
     if (MODE == 1) {
       stage_a(c1, kA1, nA1, oth + kOffA1);
-      if (flag) epi_part(c0_t{}, c1_t{}, pe, false);
+      if (flag) epi_part(c0_t{}, c1_t{}, pe, MX);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -353,14 +429,14 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
 #pragma unroll
       for (int j = 0; j < NB1; ++j) {
         if (ZC) mfma_ba_zero<FA, FB>(af[i], b1f[j], acc[0][i][1][j], kUnitScale);
-        else acc[0][i][1][j] = mfma_ba<FA, FB>(af[i], b1f[j], acc[0][i][1][j], kUnitScale, kUnitScale);
+        else mma_i(i, af[i], b1f[j], acc[0][i][1][j], as0, b1s[j]);
       }
     MI_PIN(4, NB1, acc[0][i][1][j])
     MI_PHASE_END();
     // ---- phase 2: C[1][*][1][*]
     if (MODE == 1) {
       stage_a(c2, kA0, 2, cur + kOffA0);
-      if (flag) epi_part(c1_t{}, c0_t{}, pe, false);
+      if (flag) epi_part(c1_t{}, c0_t{}, pe, MX);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -372,14 +448,14 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
 #pragma unroll
       for (int j = 0; j < NB1; ++j) {
         if (ZC) mfma_ba_zero<FA, FB>(af[i], b1f[j], acc[1][i][1][j], kUnitScale);
-        else acc[1][i][1][j] = mfma_ba<FA, FB>(af[i], b1f[j], acc[1][i][1][j], kUnitScale, kUnitScale);
+        else mma_i(i, af[i], b1f[j], acc[1][i][1][j], as1, b1s[j]);
       }
     MI_PIN(MA1, NB1, acc[1][i][1][j])
     MI_PHASE_END();
     // ---- phase 3: C[1][*][0][*]
     stage_b(c2, kB0, 2, cur + kOffB0);
     if (MODE == 1) {
-      if (flag) epi_part(c1_t{}, c1_t{}, pe, false);
+      if (flag) epi_part(c1_t{}, c1_t{}, pe, MX);
       __builtin_amdgcn_sched_barrier(0);
     }
     MI_WAIT_SYNC(MODE, flag, 3)
@@ -388,7 +464,7 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         if (ZC) mfma_ba_zero<FA, FB>(af[i], b0f[j], acc[1][i][0][j], kUnitScale);
-        else acc[1][i][0][j] = mfma_ba<FA, FB>(af[i], b0f[j], acc[1][i][0][j], kUnitScale, kUnitScale);
+        else mma_i(i, af[i], b0f[j], acc[1][i][0][j], as1, b0s[j]);
       }
     MI_PIN(MA1, 2, acc[1][i][0][j])
     MI_PHASE_END();
@@ -400,11 +476,11 @@ __global__ __launch_bounds__(512, 2) void gemm_256_grp(GroupArgs ga) {
   for (int ti = 0; ti < my_tiles; ++ti) {
     const bool have_prev = ti > 0;
     const int nk = ga.p[(__builtin_amdgcn_readlane(tab, ti) >> 28) & 3].nk;
-    ktile(c1_t{}, buf0, buf1, have_prev, prev);
-    ktile(c2_t{}, buf1, buf0, have_prev, prev);
+    ktile(c1_t{}, c0_t{}, buf0, buf1, have_prev, prev);
+    ktile(c2_t{}, c1_t{}, buf1, buf0, have_prev, prev);
     for (int pair = 1; pair < nk / 2; ++pair) {
-      ktile(c0_t{}, buf0, buf1, false, prev);
-      ktile(c0_t{}, buf1, buf0, false, prev);
+      ktile(c0_t{}, c0_t{}, buf0, buf1, false, prev);
+      ktile(c0_t{}, c1_t{}, buf1, buf0, false, prev);
     }
     prev = epi_of(ti);
   }
@@ -494,7 +570,138 @@ static int launch_grouped(const GroupArgs& ga, int cfg, int grid, hipStream_t st
   return MI_OK;
 }
 
+template <int FA, int FB>
+static int launch_grouped_mx(const GroupArgs& ga, int cfg, int grid, hipStream_t st) {
+  switch (cfg) {
+    case 0: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 4, 2, true>), dim3(grid), dim3(512), 0, st, ga); break;
+    case 1: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 4, 1, true>), dim3(grid), dim3(512), 0, st, ga); break;
+    case 2: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 2, 2, true>), dim3(grid), dim3(512), 0, st, ga); break;
+    default: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 2, 1, true>), dim3(grid), dim3(512), 0, st, ga); break;
+  }
+  MI_CHECK_LAUNCH("mi_gemm_mxfp8_grouped launch");
+  return MI_OK;
+}
+
+static const int kGrpBm[4] = {256, 256, 192, 192}, kGrpBn[4] = {256, 192, 256, 192};
+
+// tile shape that minimises K-tile steps x tile area / efficiency over the WHOLE group, among those that divide every problem
+// (-1: none).  A persistent walk over a shared tile list has no per-problem round quantisation, only the tail of the whole list.
+static int pick_group_cfg(const int64_t (*mnk)[3], int n, int ncu) {
+  static const double eff[4] = {1.0, 0.90, 0.90, 0.80};
+  int cfg = -1;
+  double best = 0;
+  for (int c = 0; c < 4; ++c) {
+    bool ok = true;
+    double steps = 0;
+    for (int i = 0; i < n; ++i) {
+      if (mnk[i][0] <= 0 || mnk[i][1] <= 0 || mnk[i][0] % kGrpBm[c] || mnk[i][1] % kGrpBn[c]) ok = false;
+      else steps += (double)(mnk[i][0] / kGrpBm[c]) * (mnk[i][1] / kGrpBn[c]) * (mnk[i][2] / 128);
+    }
+    if (!ok) continue;
+    const double cost = steps / ncu * kGrpBm[c] * kGrpBn[c] / eff[c];
+    if (cfg < 0 || cost < best * 0.97) {
+      cfg = c;
+      best = cost;
+    }
+  }
+  return cfg;
+}
+
 }  // namespace mi
+
+extern "C" int mi_gemm_mxfp8_grouped(const mi_gemm_mx_problem* problems, int n, int fmt_a, int fmt_b, int tile_cfg, void* stream) {
+  using namespace mi;
+  MI_CHECK_ARG(problems && n >= 1 && n <= kMaxGroup, "mi_gemm_mxfp8_grouped: 1 to %d problems", kMaxGroup);
+  MI_CHECK_ARG((fmt_a == 0 || fmt_a == 1) && (fmt_b == 0 || fmt_b == 1), "mi_gemm_mxfp8_grouped: bad fmt");
+  MI_CHECK_ARG(tile_cfg != 4, "mi_gemm_mxfp8_grouped: tile_cfg 4 (four-wave kernel) has no block-scaled form");
+  MI_CHECK_ARG(tile_cfg >= -1 && tile_cfg < 4, "mi_gemm_mxfp8_grouped: tile_cfg must be -1 or 0-3");
+  int64_t mnk[kMaxGroup][3];
+  for (int i = 0; i < n; ++i) {
+    const mi_gemm_mx_problem& q = problems[i];
+    MI_CHECK_ARG(q.A && q.SA && q.B && q.SB && q.D, "mi_gemm_mxfp8_grouped: null pointer in problem %d", i);
+    MI_CHECK_ARG(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.B % 16) == 0 && ((uintptr_t)q.D % 16) == 0 &&
+                     ((uintptr_t)q.SA % 16) == 0 && ((uintptr_t)q.SB % 16) == 0,
+                 "mi_gemm_mxfp8_grouped: operands and scales of problem %d must be 16-byte aligned", i);
+    if (!(q.M > 0 && q.N > 0 && q.K > 0 && q.K % 256 == 0)) {
+      set_error("mi_gemm_mxfp8_grouped: problem %d (%lld x %lld x %lld) needs M, N > 0 and K %% 256 == 0", i, (long long)q.M,
+                (long long)q.N, (long long)q.K);
+      return MI_ERR_SHAPE;
+    }
+    mnk[i][0] = q.M;
+    mnk[i][1] = q.N;
+    mnk[i][2] = q.K;
+  }
+  const int ncu = num_cus();
+  const int cfg = tile_cfg < 0 ? pick_group_cfg(mnk, n, ncu) : tile_cfg;
+  if (cfg < 0) {
+    for (int i = 0; i < n; ++i)
+      if (pick_group_cfg(mnk + i, 1, ncu) < 0) {
+        set_error("mi_gemm_mxfp8_grouped: no tile shape divides problem %d (%lld x %lld)", i, (long long)mnk[i][0], (long long)mnk[i][1]);
+        return MI_ERR_SHAPE;
+      }
+    set_error("mi_gemm_mxfp8_grouped: no tile shape divides every one of the %d problems", n);
+    return MI_ERR_SHAPE;
+  }
+  // longest tiles first (see mi_gemm_fp8_grouped)
+  int order[kMaxGroup];
+  for (int i = 0; i < n; ++i) order[i] = i;
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j)
+      if (problems[order[j]].K > problems[order[i]].K) std::swap(order[i], order[j]);
+  GroupArgs ga;
+  std::memset(&ga, 0, sizeof(ga));
+  int total = 0, ntiles[kMaxGroup], nks[kMaxGroup];
+  for (int k = 0; k < n; ++k) {
+    const mi_gemm_mx_problem& q = problems[order[k]];
+    if (q.M % kGrpBm[cfg] || q.N % kGrpBn[cfg]) {
+      set_error("mi_gemm_mxfp8_grouped: problem %d (%lld x %lld x %lld) does not fit tile shape %d x %d", order[k], (long long)q.M,
+                (long long)q.N, (long long)q.K, kGrpBm[cfg], kGrpBn[cfg]);
+      return MI_ERR_SHAPE;
+    }
+    if (!(q.M * q.K < (1LL << 31) && q.N * q.K < (1LL << 31) && q.M * q.N * 2 < (1LL << 31))) {
+      set_error("mi_gemm_mxfp8_grouped: operands of problem %d exceed 2 GiB (32-bit buffer offsets)", order[k]);
+      return MI_ERR_SHAPE;
+    }
+    GroupProblem& P = ga.p[k];
+    P.A = (const uint8_t*)q.A;
+    P.B = (const uint8_t*)q.B;
+    P.D = (uint16_t*)q.D;
+    P.SA = (const uint8_t*)q.SA;
+    P.SB = (const uint8_t*)q.SB;
+    P.lda = P.ldb = (int)q.K;  // MX operands are tight
+    P.ldd = (int)q.N;
+    P.nk = (int)(q.K / 128);
+    P.tiles_m = (int)(q.M / kGrpBm[cfg]);
+    P.tiles_n = (int)(q.N / kGrpBn[cfg]);
+    if (!(P.tiles_m < 16384 && P.tiles_n < 16384)) {
+      set_error("mi_gemm_mxfp8_grouped: problem %d has too many tiles per dimension", order[k]);
+      return MI_ERR_SHAPE;
+    }
+    P.ntiles = P.tiles_m * P.tiles_n;
+    P.tile_base = total;
+    P.a_bytes = (int)(q.M * q.K);
+    P.b_bytes = (int)(q.N * q.K);
+    P.d_bytes = (int)(q.M * q.N * 2);
+    ntiles[k] = P.ntiles;
+    nks[k] = P.nk;
+    total += P.ntiles;
+  }
+  ga.n = n;
+  ga.total_tiles = total;
+  const int grid = total < ncu ? total : (ncu > kMaxWg ? kMaxWg : ncu);
+  const Sched& sc = cached_sched(grid, n, ntiles, nks);
+  if (!(sc.ok && sc.max_per_wg <= kMaxPerWg)) {
+    set_error("mi_gemm_mxfp8_grouped: more than %d tiles per workgroup (%d tiles in all)", kMaxPerWg, total);
+    return MI_ERR_SHAPE;
+  }
+  std::memcpy(ga.cnt, sc.cnt, sizeof(ga.cnt));
+  std::memcpy(ga.R, sc.R, sizeof(ga.R));
+  hipStream_t st = (hipStream_t)stream;
+  if (fmt_a == 0 && fmt_b == 0) return launch_grouped_mx<0, 0>(ga, cfg, grid, st);
+  if (fmt_a == 1 && fmt_b == 0) return launch_grouped_mx<1, 0>(ga, cfg, grid, st);
+  if (fmt_a == 0 && fmt_b == 1) return launch_grouped_mx<0, 1>(ga, cfg, grid, st);
+  return launch_grouped_mx<1, 1>(ga, cfg, grid, st);
+}
 
 extern "C" int mi_gemm_fp8_grouped(const mi_gemm_problem* problems, int n, int fmt_a, int fmt_b, int tile_cfg, void* stream) {
   using namespace mi;

@@ -395,6 +395,32 @@ def _dgrad_wgrad(g8, wt8, g8t, xt8, sig, si_w, si_x, fmt_b: int, fmt_f: int, dw_
     return dx, dw
 
 
+def _dgrad_wgrad_mx(g8, gs, wt8, wts, gt8, gts, xt8, xts, fmt_b: int, fmt_f: int, dw_out, need_dgrad: bool, need_wgrad: bool):
+    """_dgrad_wgrad under MXFP8 block scaling: dX [M, K] = G8 [M, N] . W8T [K, N]^T and dW [N, K] = G8T [N, M] . X8T [K, M]^T, each
+    operand with its block-major E8M0 scales.  ONE grouped persistent launch (ops.gemm_mxfp8_grouped) where
+    ops.grouped_gemm_mx_choice finds it faster, under the gate of the per-tensor path (both gradients needed, a persistent default
+    algo -- so never under torch.distributed --, the switches not off, shapes eligible), else two launches.  Bitwise the same
+    results either way; `dw_out` (the gradient-arena slot) stays the wgrad's output."""
+    dx = dw = None
+    if need_dgrad and need_wgrad and ops.default_gemm_algo() in (0, 4, 47) and os.environ.get("LLM_FP8_AMD_NO_GROUPED_GEMM") != "1":
+        M, N = g8.shape
+        K = wt8.shape[0]
+        if ops.grouped_gemm_ok(((M, K, N), (N, K, M))) and all(t.is_contiguous() for t in (g8, gs, wt8, wts, gt8, gts, xt8, xts)):
+            dx = torch.empty((M, K), dtype=torch.bfloat16, device=g8.device)
+            dw = dw_out if dw_out is not None else torch.empty((N, K), dtype=torch.bfloat16, device=g8.device)
+            probs = [(g8, gs, wt8, wts, dx), (gt8, gts, xt8, xts, dw)]
+            cfg = ops.grouped_gemm_mx_choice(probs, fmt_b, fmt_f)  # cached per shape set: -1 = two launches are faster here
+            if cfg >= 0:
+                ops.gemm_mxfp8_grouped(probs, fmt_b, fmt_f, tile_cfg=cfg)
+                return dx, dw
+            dx = dw = None
+    if need_dgrad:
+        dx = ops.gemm_mxfp8(g8, gs, wt8, wts, fmt_b, fmt_f)
+    if need_wgrad:
+        dw = ops.gemm_mxfp8(gt8, gts, xt8, xts, fmt_b, fmt_f, out=dw_out)
+    return dx, dw
+
+
 def _skip_2d(dskip: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
     """Residual-branch gradient as a contiguous bf16 [tokens, features] matrix for mi_rmsnorm_bwd's `dres`."""
     if dskip is None:
@@ -491,10 +517,8 @@ class _FP8LinearFn(torch.autograd.Function):
                 db_fused = ops.colsum_finish(cs, ctx.bias_dtype)
             else:
                 g8, gs, gt8, gts = ops.mxfp8_quantize(g2, spec.fmt_bwd, rowwise=ctx.need_dgrad, colwise=ctx.need_wgrad)
-            if ctx.need_dgrad:
-                dx = ops.gemm_mxfp8(g8, gs, wt8, wts, spec.fmt_bwd, spec.fmt_fwd)
-            if ctx.need_wgrad:
-                dw = ops.gemm_mxfp8(gt8, gts, xt8, xts, spec.fmt_bwd, spec.fmt_fwd, out=_wgrad_out(ctx.w_refs, xt8.shape[0]))
+            dx, dw = _dgrad_wgrad_mx(g8, gs, wt8, wts, gt8, gts, xt8, xts, spec.fmt_bwd, spec.fmt_fwd,
+                                     _wgrad_out(ctx.w_refs, xt8.shape[0]) if ctx.need_wgrad else None, ctx.need_dgrad, ctx.need_wgrad)
         else:
             mb, g = spec.meta_bwd, spec.g
             if spec.dy_handoff is not None and spec.dy_handoff.fp8 is not None:
@@ -634,14 +658,14 @@ class _FP8SwiGLUMLPFn(torch.autograd.Function):
         else:
             g8, gs, gt8, gts = ops.mxfp8_quantize(g2, fmt_b, rowwise=True, colwise=ctx.need_w)
             db2 = None
-        dact = ops.gemm_mxfp8(g8, gs, w2t8, w2ts, fmt_b, fmt_f)
-        dw2 = ops.gemm_mxfp8(gt8, gts, at8, ats, fmt_b, fmt_f, out=_wgrad_out(ctx.w_refs[1:], at8.shape[0])) if ctx.need_w else None
+        dact, dw2 = _dgrad_wgrad_mx(g8, gs, w2t8, w2ts, gt8, gts, at8, ats, fmt_b, fmt_f,
+                                    _wgrad_out(ctx.w_refs[1:], at8.shape[0]) if ctx.need_w else None, True, ctx.need_w)
         want_b1 = ctx.dtypes[1] is not None
         dh8, dhs, dht8, dhts, colsum = ops.mxfp8_dswiglu_quantize(h, dact, fmt_b, rowwise=ctx.need_dgrad, colwise=ctx.need_w,
                                                                   want_colsum=want_b1)
         db1 = (colsum, ctx.dtypes[1]) if want_b1 else None
-        dx = ops.gemm_mxfp8(dh8, dhs, w1t8, w1ts, fmt_b, fmt_f) if ctx.need_dgrad else None
-        dw1 = ops.gemm_mxfp8(dht8, dhts, xt8, xts, fmt_b, fmt_f, out=_wgrad_out(ctx.w_refs[:1], xt8.shape[0])) if ctx.need_w else None
+        dx, dw1 = _dgrad_wgrad_mx(dh8, dhs, w1t8, w1ts, dht8, dhts, xt8, xts, fmt_b, fmt_f,
+                                  _wgrad_out(ctx.w_refs[:1], xt8.shape[0]) if ctx.need_w else None, ctx.need_dgrad, ctx.need_w)
         return dx, dw1, db1, dw2, db2
 
     @staticmethod

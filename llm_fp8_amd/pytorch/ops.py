@@ -347,6 +347,33 @@ def gemm_fp8_grouped(problems, fmt_a: int, fmt_b: int, tile_cfg: int = -1) -> No
     _lib.check(rc, "mi_gemm_fp8_grouped")
 
 
+def gemm_mxfp8_grouped(problems, fmt_a: int, fmt_b: int, tile_cfg: int = -1) -> None:
+    """ONE persistent launch for up to 4 block-scaled GEMMs (mi_gemm_mxfp8_grouped): `problems` is a list of
+    (a8 [M,K], sa [K/32,M], b8 [N,K], sb [K/32,N], out bf16 [M,N]), operands as for gemm_mxfp8; all share the operand formats.
+    Outputs are written in place, bit for bit what gemm_mxfp8(algo=4) gives per problem."""
+    n = len(problems)
+    arr = (_lib.GemmMxProblem * n)()
+    for i, (a8, sa, b8, sb, out) in enumerate(problems):
+        _dev(a8, sa, b8, sb, out)
+        M, K = a8.shape
+        N, K2 = b8.shape
+        assert a8.dtype == torch.uint8 and b8.dtype == torch.uint8 and out.dtype == torch.bfloat16
+        assert K == K2 and a8.is_contiguous() and b8.is_contiguous() and sa.is_contiguous() and sb.is_contiguous()
+        assert sa.shape == (K // 32, M) and sb.shape == (K // 32, N), "scales must be block-major [K/32, rows]"
+        assert out.is_contiguous() and out.shape == (M, N)
+        arr[i] = _lib.GemmMxProblem(a8.data_ptr(), sa.data_ptr(), b8.data_ptr(), sb.data_ptr(), out.data_ptr(), M, N, K)
+    t = KernelTimer.active
+    if t is None:
+        rc = _lib.load().mi_gemm_mxfp8_grouped(ctypes.byref(arr), n, fmt_a, fmt_b, tile_cfg, _stream())
+    else:
+        work = sum(2.0 * a.shape[0] * b.shape[0] * a.shape[1] for a, _, b, _, _ in problems)
+        nbytes = sum(a.numel() + b.numel() + 2 * o.numel() for a, _, b, _, o in problems)
+        tag = "+".join(f"{a.shape[0]}x{b.shape[0]}x{a.shape[1]}" for a, _, b, _, _ in problems)
+        with t.span("gemm_mxfp8", tag, work, nbytes):
+            rc = _lib.load().mi_gemm_mxfp8_grouped(ctypes.byref(arr), n, fmt_a, fmt_b, tile_cfg, _stream())
+    _lib.check(rc, "mi_gemm_mxfp8_grouped")
+
+
 def grouped_gemm_ok(shapes, strides_ok: bool = True) -> bool:
     """Can mi_gemm_fp8_grouped take these (M, N, K) problems together?  (one tile shape dividing all, K % 256, < 2 GiB operands)"""
     if not strides_ok or not shapes or len(shapes) > 4:
@@ -495,6 +522,86 @@ def grouped_gemm_autotune(problems, fmt_a: int, fmt_b: int, iters: int = 5) -> i
         # (profiles/r03_grouped_w4_ab.txt); inside a first backward the five rounds above still carry ~1 % of noise: it takes ties
         if 4 in total and best not in (-1, 4) and total[4] <= 1.01 * best_t:
             best, best_t = 4, total[4]
+    finally:
+        KernelTimer.active = saved
+    _GROUP_TUNED[key] = best
+    return best
+
+
+def _mx_shapes(problems):
+    return tuple((a.shape[0], b.shape[0], a.shape[1]) for a, _, b, _, _ in problems)
+
+
+def grouped_gemm_mx_choice(problems, fmt_a: int, fmt_b: int) -> int:
+    """grouped_gemm_choice for a block-scaled group (`problems` as for gemm_mxfp8_grouped): -1 = separate gemm_mxfp8 launches,
+    0-3 = one gemm_mxfp8_grouped launch with that tile shape (never 4: the four-wave kernel has no block-scaled form).  Same policy
+    and the same environment switch (LLM_FP8_AMD_GROUPED_GEMM = auto | plan | autotune | off)."""
+    mode = os.environ.get("LLM_FP8_AMD_GROUPED_GEMM", "auto")
+    if mode == "off":
+        return -1
+    if mode == "auto":
+        import torch.distributed as dist
+        mode = "plan" if (dist.is_available() and dist.is_initialized()) else "autotune"
+    if mode == "plan":
+        return grouped_gemm_plan(_mx_shapes(problems))
+    if mode != "autotune":
+        raise ValueError(f"LLM_FP8_AMD_GROUPED_GEMM={mode!r}: expected auto, plan, autotune or off")
+    return grouped_gemm_mx_autotune(problems, fmt_a, fmt_b)
+
+
+def _mx_tuned_key(shapes, fmt_a: int, fmt_b: int):
+    """Cache key of a block-scaled group in _GROUP_TUNED: never that of a per-tensor group of equal shapes."""
+    return ("mx", tuple(shapes), fmt_a, fmt_b)
+
+
+def grouped_gemm_mx_autotune(problems, fmt_a: int, fmt_b: int, iters: int = 5) -> int:
+    """grouped_gemm_autotune for a block-scaled group: the same interleaved rounds into SCRATCH outputs, candidates -1 (separate
+    gemm_mxfp8 launches at the default algo) and every tile shape that divides the group; cached per (shapes, formats) under a key
+    of its own."""
+    shapes = _mx_shapes(problems)
+    key = _mx_tuned_key(shapes, fmt_a, fmt_b)
+    hit = _GROUP_TUNED.get(key)
+    if hit is not None:
+        return hit
+    problems = [(a8, sa, b8, sb, torch.empty_like(out)) for a8, sa, b8, sb, out in problems]
+    cands = [-1]
+    if grouped_gemm_ok(shapes):
+        cands += [cfg for cfg, (bm, bn) in enumerate(_TILE_CFGS) if all(M % bm == 0 and N % bn == 0 for M, N, K in shapes)]
+
+    def run(c):
+        if c == -1:
+            for a8, sa, b8, sb, out in problems:
+                gemm_mxfp8(a8, sa, b8, sb, fmt_a, fmt_b, out=out)  # the default algo: what two separate launches would really run
+        else:
+            gemm_mxfp8_grouped(problems, fmt_a, fmt_b, tile_cfg=c)
+
+    saved, KernelTimer.active = KernelTimer.active, None  # (the candidates are not part of any timed span)
+    try:
+        live = []
+        for c in cands:
+            try:
+                run(c)  # warm-up; a candidate the library refuses drops out
+                live.append(c)
+            except RuntimeError:
+                continue
+        total = {c: 0.0 for c in live}
+        for r in range(iters):  # interleaved rounds, rotating order (see grouped_gemm_autotune)
+            order = live[r % len(live):] + live[:r % len(live)]
+            for c in order:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                run(c)
+                run(c)
+                e1.record()
+                e1.synchronize()
+                total[c] += e0.elapsed_time(e1)
+        best, best_t = -1, total.get(-1)
+        for c in live:
+            if c == -1:
+                continue
+            t = total[c]
+            if best_t is None or t < best_t * (0.98 if best == -1 else 1.0):  # a grouped launch must win by 2 % over separate ones
+                best, best_t = c, t
     finally:
         KernelTimer.active = saved
     _GROUP_TUNED[key] = best

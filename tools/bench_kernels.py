@@ -312,6 +312,24 @@ def main():
                 if not ops.grouped_gemm_ok([(M, K, N), (N, K, M)]):
                     print(f"grouped {mname} {name}: not eligible", flush=True)
                     continue
+                if os.environ.get("GROUPED_MODE", "pt") == "mx":  # GROUPED_MODE=mx: the block-scaled pair (mi_gemm_mxfp8_grouped)
+                    sc = lambda r, c: torch.randint(124, 131, (r, c), generator=g, device=dev, dtype=torch.uint8)
+                    mx = [(g8, sc(N // 32, M), w8t, sc(N // 32, K), dx), (g8t, sc(M // 32, N), x8t, sc(M // 32, K), dw)]
+                    def sep_mx():
+                        for a8, sa, b8, sb, o in mx:
+                            ops.gemm_mxfp8(a8, sa, b8, sb, 0, 0, out=o, algo=4)
+                    cands = {"separate": sep_mx}
+                    for cfg, (bm, bn) in enumerate(((256, 256), (256, 192), (192, 256), (192, 192))):
+                        if all(a8.shape[0] % bm == 0 and b8.shape[0] % bn == 0 for a8, _, b8, _, _ in mx):
+                            cands[f"grouped{cfg}"] = (lambda c: lambda: ops.gemm_mxfp8_grouped(mx, 0, 0, tile_cfg=c))(cfg)
+                    res = time_interleaved(cands, rounds=10, inner=4)
+                    best = min((k for k in res if k != "separate"), key=res.get)
+                    plan = ops.grouped_gemm_plan(((M, K, N), (N, K, M)))
+                    tsep += res["separate"]; tgrp += res[best]
+                    print(f"grouped-mx {mname} {name:7s} bwd M={M} N={N} K={K}: separate {res['separate']*1e6:7.1f} us   "
+                          + "   ".join(f"{k} {v*1e6:7.1f} us" for k, v in res.items() if k != "separate")
+                          + f"   best {best} {res['separate']/res[best]:.3f}x   count model: {plan}", flush=True)
+                    continue
                 def sep():
                     ops.gemm_fp8(g8, w8t, one, one, 0, 0, out=dx, algo=4)
                     ops.gemm_fp8(g8t, x8t, one, one, 0, 0, out=dw, algo=4)
