@@ -1235,7 +1235,6 @@ __global__ __launch_bounds__(512, 2) void gemm_256_p8(const uint8_t* __restrict_
 // Tile shape for the persistent kernel: minimise rounds x tile area / efficiency over the shapes that divide M, N.
 // cfg: 0 = 256x256, 1 = 256x192, 2 = 192x256, 3 = 192x192.
 static int pick_tile_cfg(int64_t M, int64_t N, int64_t K) {
-  static const int bm[4] = {256, 256, 192, 192}, bn[4] = {256, 192, 256, 192};
   // measured relative efficiency of the shorter phases.  192-COLUMN tiles (NB1 == 1) store half lines (a wave's 48 columns = 64
   // + 32 B per row), 192-ROW tiles keep whole 128-byte lines: 6144x6144x4096 runs 126.5 us as 256x192 and 118.8 us as 192x256
   // tiles.  And half-line stores pay extra when the output lines are COLD, which in a training step they always are (the
@@ -1250,10 +1249,10 @@ static int pick_tile_cfg(int64_t M, int64_t N, int64_t K) {
   // Measured on MI355X with interleaved A/B timing (tools/bench_kernels.py --which tiles; back-to-back timing is biased by
   // clock drift): 8192x3072xK as 512 tiles of 256x192 beats 384 tiles of 256x256 by 5 % (K 3072) to 9 % (K 16384).
   for (int c = 0; c < 4; ++c) {
-    if (M % bm[c] || N % bn[c]) continue;
-    const int64_t tiles = (M / bm[c]) * (N / bn[c]);
+    if (M % kTileBm[c] || N % kTileBn[c]) continue;
+    const int64_t tiles = (M / kTileBm[c]) * (N / kTileBn[c]);
     const int64_t rounds = (tiles + ncu - 1) / ncu;
-    const double cost = (double)rounds * bm[c] * bn[c] / eff[c];
+    const double cost = (double)rounds * kTileBm[c] * kTileBn[c] / eff[c];
     if (best < 0 || cost < best_cost * 0.98) {  // prefer the larger tile unless the gain is > 2 % (in the step fc2 fprop, K = 8192: 170 us as 256x192, 178 us as 256x256 tiles)
       best = c;
       best_cost = cost;
@@ -1355,8 +1354,7 @@ static int launch_p8(const uint8_t* a, const uint8_t* b, uint16_t* D, const floa
     }
   }
   int cfg = (algo >= 40 && algo <= 43) ? algo - 40 : pick_tile_cfg(M, N, K);
-  static const int bm[4] = {256, 256, 192, 192}, bn[4] = {256, 192, 256, 192};
-  if (cfg < 0 || M % bm[cfg] || N % bn[cfg]) {
+  if (cfg < 0 || M % kTileBm[cfg] || N % kTileBn[cfg]) {
     set_error("mi_gemm: no persistent tile shape divides %lld x %lld", (long long)M, (long long)N);
     return MI_ERR_SHAPE;
   }

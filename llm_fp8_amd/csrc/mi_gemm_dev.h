@@ -107,6 +107,10 @@ __device__ __forceinline__ void wait_vmcnt() {
   __builtin_amdgcn_s_barrier();   \
   __builtin_amdgcn_sched_barrier(0);
 
+// Tile shapes of the persistent eight-wave kernels (gemm_256_p8, gemm_256_grp) by tile_cfg 0-3: <MA1, NB1> = <4, 2>, <4, 1>, <2, 2>,
+// <2, 1>, i.e. 256 / 192 rows x 256 / 192 columns.  Host side only: the kernels take MA1 / NB1 as template parameters.
+constexpr int kTileBm[4] = {256, 256, 192, 192}, kTileBn[4] = {256, 192, 256, 192};
+
 // ------------------------------------------------------------------------------------------------
 // Grouped launches (mi_gemm_grouped.hip: eight-wave kernel; mi_gemm_w4.hip: four-wave kernel, 256 x 256 tiles)
 constexpr int kMaxGroup = 4;

@@ -558,35 +558,39 @@ static const Sched& cached_sched(int G, int n, const int* ntiles, const int* nk)
   return it->second;
 }
 
-template <int FA, int FB>
+template <int FA, int FB, bool MX>
 static int launch_grouped(const GroupArgs& ga, int cfg, int grid, hipStream_t st) {
   switch (cfg) {
-    case 0: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 4, 2>), dim3(grid), dim3(512), 0, st, ga); break;
-    case 1: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 4, 1>), dim3(grid), dim3(512), 0, st, ga); break;
-    case 2: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 2, 2>), dim3(grid), dim3(512), 0, st, ga); break;
-    default: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 2, 1>), dim3(grid), dim3(512), 0, st, ga); break;
+    case 0: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 4, 2, MX>), dim3(grid), dim3(512), 0, st, ga); break;
+    case 1: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 4, 1, MX>), dim3(grid), dim3(512), 0, st, ga); break;
+    case 2: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 2, 2, MX>), dim3(grid), dim3(512), 0, st, ga); break;
+    default: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 2, 1, MX>), dim3(grid), dim3(512), 0, st, ga); break;
   }
-  MI_CHECK_LAUNCH("mi_gemm_fp8_grouped launch");
+  MI_CHECK_LAUNCH(MX ? "mi_gemm_mxfp8_grouped launch" : "mi_gemm_fp8_grouped launch");
   return MI_OK;
 }
 
-template <int FA, int FB>
-static int launch_grouped_mx(const GroupArgs& ga, int cfg, int grid, hipStream_t st) {
-  switch (cfg) {
-    case 0: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 4, 2, true>), dim3(grid), dim3(512), 0, st, ga); break;
-    case 1: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 4, 1, true>), dim3(grid), dim3(512), 0, st, ga); break;
-    case 2: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 2, 2, true>), dim3(grid), dim3(512), 0, st, ga); break;
-    default: hipLaunchKernelGGL((gemm_256_grp<FA, FB, 2, 1, true>), dim3(grid), dim3(512), 0, st, ga); break;
-  }
-  MI_CHECK_LAUNCH("mi_gemm_mxfp8_grouped launch");
-  return MI_OK;
+template <bool MX>
+static int launch_grouped_fmt(const GroupArgs& ga, int fmt_a, int fmt_b, int cfg, int grid, hipStream_t st) {
+  if (fmt_a == 0 && fmt_b == 0) return launch_grouped<0, 0, MX>(ga, cfg, grid, st);
+  if (fmt_a == 1 && fmt_b == 0) return launch_grouped<1, 0, MX>(ga, cfg, grid, st);
+  if (fmt_a == 0 && fmt_b == 1) return launch_grouped<0, 1, MX>(ga, cfg, grid, st);
+  return launch_grouped<1, 1, MX>(ga, cfg, grid, st);
 }
 
-static const int kGrpBm[4] = {256, 256, 192, 192}, kGrpBn[4] = {256, 192, 256, 192};
+// One problem of a group as the host path below takes it.  Each entry point fills it from its own ABI struct and runs its own
+// argument checks on it (the two contracts differ in order, wording and return codes); everything after the checks is shared.
+struct GroupIn {
+  const void *A, *B, *sa, *sb;  // sa / sb: the device scalars sa_inv / sb_inv (per-tensor) or the E8M0 block scales SA / SB (MX)
+  void* D;
+  int64_t M, N, K, lda, ldb, ldd;
+  int index;  // position in the caller's array (messages name it)
+};
 
 // tile shape that minimises K-tile steps x tile area / efficiency over the WHOLE group, among those that divide every problem
 // (-1: none).  A persistent walk over a shared tile list has no per-problem round quantisation, only the tail of the whole list.
-static int pick_group_cfg(const int64_t (*mnk)[3], int n, int ncu) {
+// Divisibility is all it asks: M, N <= 0 "divide", and the per-problem checks of the entry points refuse such a problem afterwards.
+static int pick_group_cfg(const GroupIn* in, int n, int ncu) {
   static const double eff[4] = {1.0, 0.90, 0.90, 0.80};
   int cfg = -1;
   double best = 0;
@@ -594,11 +598,11 @@ static int pick_group_cfg(const int64_t (*mnk)[3], int n, int ncu) {
     bool ok = true;
     double steps = 0;
     for (int i = 0; i < n; ++i) {
-      if (mnk[i][0] <= 0 || mnk[i][1] <= 0 || mnk[i][0] % kGrpBm[c] || mnk[i][1] % kGrpBn[c]) ok = false;
-      else steps += (double)(mnk[i][0] / kGrpBm[c]) * (mnk[i][1] / kGrpBn[c]) * (mnk[i][2] / 128);
+      if (in[i].M % kTileBm[c] || in[i].N % kTileBn[c]) ok = false;
+      else steps += (double)(in[i].M / kTileBm[c]) * (in[i].N / kTileBn[c]) * (in[i].K / 128);
     }
     if (!ok) continue;
-    const double cost = steps / ncu * kGrpBm[c] * kGrpBn[c] / eff[c];
+    const double cost = steps / ncu * kTileBm[c] * kTileBn[c] / eff[c];
     if (cfg < 0 || cost < best * 0.97) {
       cfg = c;
       best = cost;
@@ -607,171 +611,51 @@ static int pick_group_cfg(const int64_t (*mnk)[3], int n, int ncu) {
   return cfg;
 }
 
-}  // namespace mi
-
-extern "C" int mi_gemm_mxfp8_grouped(const mi_gemm_mx_problem* problems, int n, int fmt_a, int fmt_b, int tile_cfg, void* stream) {
-  using namespace mi;
-  MI_CHECK_ARG(problems && n >= 1 && n <= kMaxGroup, "mi_gemm_mxfp8_grouped: 1 to %d problems", kMaxGroup);
-  MI_CHECK_ARG((fmt_a == 0 || fmt_a == 1) && (fmt_b == 0 || fmt_b == 1), "mi_gemm_mxfp8_grouped: bad fmt");
-  MI_CHECK_ARG(tile_cfg != 4, "mi_gemm_mxfp8_grouped: tile_cfg 4 (four-wave kernel) has no block-scaled form");
-  MI_CHECK_ARG(tile_cfg >= -1 && tile_cfg < 4, "mi_gemm_mxfp8_grouped: tile_cfg must be -1 or 0-3");
-  int64_t mnk[kMaxGroup][3];
-  for (int i = 0; i < n; ++i) {
-    const mi_gemm_mx_problem& q = problems[i];
-    MI_CHECK_ARG(q.A && q.SA && q.B && q.SB && q.D, "mi_gemm_mxfp8_grouped: null pointer in problem %d", i);
-    MI_CHECK_ARG(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.B % 16) == 0 && ((uintptr_t)q.D % 16) == 0 &&
-                     ((uintptr_t)q.SA % 16) == 0 && ((uintptr_t)q.SB % 16) == 0,
-                 "mi_gemm_mxfp8_grouped: operands and scales of problem %d must be 16-byte aligned", i);
-    if (!(q.M > 0 && q.N > 0 && q.K > 0 && q.K % 256 == 0)) {
-      set_error("mi_gemm_mxfp8_grouped: problem %d (%lld x %lld x %lld) needs M, N > 0 and K %% 256 == 0", i, (long long)q.M,
-                (long long)q.N, (long long)q.K);
-      return MI_ERR_SHAPE;
-    }
-    mnk[i][0] = q.M;
-    mnk[i][1] = q.N;
-    mnk[i][2] = q.K;
-  }
-  const int ncu = num_cus();
-  const int cfg = tile_cfg < 0 ? pick_group_cfg(mnk, n, ncu) : tile_cfg;
-  if (cfg < 0) {
-    for (int i = 0; i < n; ++i)
-      if (pick_group_cfg(mnk + i, 1, ncu) < 0) {
-        set_error("mi_gemm_mxfp8_grouped: no tile shape divides problem %d (%lld x %lld)", i, (long long)mnk[i][0], (long long)mnk[i][1]);
-        return MI_ERR_SHAPE;
-      }
-    set_error("mi_gemm_mxfp8_grouped: no tile shape divides every one of the %d problems", n);
-    return MI_ERR_SHAPE;
-  }
-  // longest tiles first (see mi_gemm_fp8_grouped)
-  int order[kMaxGroup];
-  for (int i = 0; i < n; ++i) order[i] = i;
+// longest tiles first: a round-robin deal of that order over the persistent workgroups is a longest-processing-time schedule
+static void sort_by_decreasing_k(GroupIn* in, int n) {
   for (int i = 0; i < n; ++i)
     for (int j = i + 1; j < n; ++j)
-      if (problems[order[j]].K > problems[order[i]].K) std::swap(order[i], order[j]);
-  GroupArgs ga;
-  std::memset(&ga, 0, sizeof(ga));
-  int total = 0, ntiles[kMaxGroup], nks[kMaxGroup];
-  for (int k = 0; k < n; ++k) {
-    const mi_gemm_mx_problem& q = problems[order[k]];
-    if (q.M % kGrpBm[cfg] || q.N % kGrpBn[cfg]) {
-      set_error("mi_gemm_mxfp8_grouped: problem %d (%lld x %lld x %lld) does not fit tile shape %d x %d", order[k], (long long)q.M,
-                (long long)q.N, (long long)q.K, kGrpBm[cfg], kGrpBn[cfg]);
-      return MI_ERR_SHAPE;
-    }
-    if (!(q.M * q.K < (1LL << 31) && q.N * q.K < (1LL << 31) && q.M * q.N * 2 < (1LL << 31))) {
-      set_error("mi_gemm_mxfp8_grouped: operands of problem %d exceed 2 GiB (32-bit buffer offsets)", order[k]);
-      return MI_ERR_SHAPE;
-    }
-    GroupProblem& P = ga.p[k];
-    P.A = (const uint8_t*)q.A;
-    P.B = (const uint8_t*)q.B;
-    P.D = (uint16_t*)q.D;
-    P.SA = (const uint8_t*)q.SA;
-    P.SB = (const uint8_t*)q.SB;
-    P.lda = P.ldb = (int)q.K;  // MX operands are tight
-    P.ldd = (int)q.N;
-    P.nk = (int)(q.K / 128);
-    P.tiles_m = (int)(q.M / kGrpBm[cfg]);
-    P.tiles_n = (int)(q.N / kGrpBn[cfg]);
-    if (!(P.tiles_m < 16384 && P.tiles_n < 16384)) {
-      set_error("mi_gemm_mxfp8_grouped: problem %d has too many tiles per dimension", order[k]);
-      return MI_ERR_SHAPE;
-    }
-    P.ntiles = P.tiles_m * P.tiles_n;
-    P.tile_base = total;
-    P.a_bytes = (int)(q.M * q.K);
-    P.b_bytes = (int)(q.N * q.K);
-    P.d_bytes = (int)(q.M * q.N * 2);
-    ntiles[k] = P.ntiles;
-    nks[k] = P.nk;
-    total += P.ntiles;
-  }
-  ga.n = n;
-  ga.total_tiles = total;
-  const int grid = total < ncu ? total : (ncu > kMaxWg ? kMaxWg : ncu);
-  const Sched& sc = cached_sched(grid, n, ntiles, nks);
-  if (!(sc.ok && sc.max_per_wg <= kMaxPerWg)) {
-    set_error("mi_gemm_mxfp8_grouped: more than %d tiles per workgroup (%d tiles in all)", kMaxPerWg, total);
-    return MI_ERR_SHAPE;
-  }
-  std::memcpy(ga.cnt, sc.cnt, sizeof(ga.cnt));
-  std::memcpy(ga.R, sc.R, sizeof(ga.R));
-  hipStream_t st = (hipStream_t)stream;
-  if (fmt_a == 0 && fmt_b == 0) return launch_grouped_mx<0, 0>(ga, cfg, grid, st);
-  if (fmt_a == 1 && fmt_b == 0) return launch_grouped_mx<1, 0>(ga, cfg, grid, st);
-  if (fmt_a == 0 && fmt_b == 1) return launch_grouped_mx<0, 1>(ga, cfg, grid, st);
-  return launch_grouped_mx<1, 1>(ga, cfg, grid, st);
+      if (in[j].K > in[i].K) std::swap(in[i], in[j]);
 }
 
-extern "C" int mi_gemm_fp8_grouped(const mi_gemm_problem* problems, int n, int fmt_a, int fmt_b, int tile_cfg, void* stream) {
-  using namespace mi;
-  MI_CHECK_ARG(problems && n >= 1 && n <= kMaxGroup, "mi_gemm_fp8_grouped: 1 to %d problems", kMaxGroup);
-  MI_CHECK_ARG((fmt_a == 0 || fmt_a == 1) && (fmt_b == 0 || fmt_b == 1), "mi_gemm_fp8_grouped: bad fmt");
-  static const int bm[4] = {256, 256, 192, 192}, bn[4] = {256, 192, 256, 192};
-  const int ncu = num_cus();
-  // tile shape: the caller's, or the one that minimises rounds x tile area / efficiency over the WHOLE group (mi_gemm.hip pick_tile_cfg)
-  // tile_cfg 4 = 256 x 256 tiles on the four-wave kernel (mi_gemm_w4.hip; every problem K >= 512): same schedule, other kernel
-  const bool four_wave = tile_cfg == 4;
-  int cfg = four_wave ? 0 : tile_cfg;
-  if (cfg < 0) {
-    static const double eff[4] = {1.0, 0.90, 0.90, 0.80};
-    double best = 0;
-    for (int c = 0; c < 4; ++c) {
-      bool ok = true;
-      double steps = 0;
-      for (int i = 0; i < n; ++i) {
-        if (problems[i].M % bm[c] || problems[i].N % bn[c]) ok = false;
-        else steps += (double)(problems[i].M / bm[c]) * (problems[i].N / bn[c]) * (problems[i].K / 128);
-      }
-      if (!ok) continue;
-      // persistent walk over a shared tile list: no per-problem round quantisation, only the tail of the whole list
-      const double per_wg = steps / ncu;
-      const double cost = per_wg * bm[c] * bn[c] / eff[c];
-      if (cfg < 0 || cost < best * 0.97) {
-        cfg = c;
-        best = cost;
-      }
-    }
+// the size limits that end a problem's checks at both entry points (32-bit buffer offsets, 14-bit tile coordinates)
+static bool group_sizes_ok(const char* who, const GroupIn& q, int cfg) {
+  if (!(q.M * q.lda < (1LL << 31) && q.N * q.ldb < (1LL << 31) && q.M * q.ldd * 2 < (1LL << 31))) {
+    set_error("%s: operands of problem %d exceed 2 GiB (32-bit buffer offsets)", who, q.index);
+    return false;
   }
-  MI_CHECK_ARG(cfg >= 0 && cfg < 4, "mi_gemm_fp8_grouped: no tile shape divides every problem");
-  // longest tiles first: a round-robin deal of that order over the persistent workgroups is a longest-processing-time schedule
-  int order[kMaxGroup];
-  for (int i = 0; i < n; ++i) order[i] = i;
-  for (int i = 0; i < n; ++i)
-    for (int j = i + 1; j < n; ++j)
-      if (problems[order[j]].K > problems[order[i]].K) {
-        const int t = order[i];
-        order[i] = order[j];
-        order[j] = t;
-      }
+  if (!(q.M / kTileBm[cfg] < 16384 && q.N / kTileBn[cfg] < 16384)) {
+    set_error("%s: problem %d has too many tiles per dimension", who, q.index);
+    return false;
+  }
+  return true;
+}
+
+// What both entry points do once `in` (sorted by decreasing K) has passed their checks: tile lists, schedule, launch.
+// four_wave: 256 x 256 tiles (cfg 0) on the four-wave kernel (mi_gemm_w4.hip): same schedule, other kernel; per-tensor only.
+static int launch_group(const char* who, const GroupIn* in, int n, int cfg, int fmt_a, int fmt_b, bool mx, bool four_wave, void* stream) {
   GroupArgs ga;
   std::memset(&ga, 0, sizeof(ga));
   int total = 0, ntiles[kMaxGroup], nks[kMaxGroup];
   for (int k = 0; k < n; ++k) {
-    const mi_gemm_problem& q = problems[order[k]];
-    MI_CHECK_ARG(q.A && q.B && q.D && q.sa_inv && q.sb_inv, "mi_gemm_fp8_grouped: null pointer in problem %d", order[k]);
-    MI_CHECK_ARG(q.M > 0 && q.N > 0 && q.K > 0 && q.M % bm[cfg] == 0 && q.N % bn[cfg] == 0 && q.K % 256 == 0,
-                 "mi_gemm_fp8_grouped: problem %d (%lld x %lld x %lld) does not fit tile shape %d x %d / K %% 256", order[k],
-                 (long long)q.M, (long long)q.N, (long long)q.K, bm[cfg], bn[cfg]);
-    MI_CHECK_ARG(q.lda >= q.K && q.ldb >= q.K && q.ldd >= q.N && q.lda % 16 == 0 && q.ldb % 16 == 0 && q.ldd % 4 == 0,
-                 "mi_gemm_fp8_grouped: bad leading dimensions in problem %d", order[k]);
-    MI_CHECK_ARG(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.B % 16) == 0 && ((uintptr_t)q.D % 16) == 0,
-                 "mi_gemm_fp8_grouped: operands must be 16-byte aligned");
-    MI_CHECK_ARG(q.M * q.lda < (1LL << 31) && q.N * q.ldb < (1LL << 31) && q.M * q.ldd * 2 < (1LL << 31),
-                 "mi_gemm_fp8_grouped: operands of problem %d exceed 2 GiB (32-bit buffer offsets)", order[k]);
+    const GroupIn& q = in[k];
     GroupProblem& P = ga.p[k];
     P.A = (const uint8_t*)q.A;
     P.B = (const uint8_t*)q.B;
     P.D = (uint16_t*)q.D;
-    P.sa_inv = q.sa_inv;
-    P.sb_inv = q.sb_inv;
+    if (mx) {
+      P.SA = (const uint8_t*)q.sa;
+      P.SB = (const uint8_t*)q.sb;
+    } else {
+      P.sa_inv = (const float*)q.sa;
+      P.sb_inv = (const float*)q.sb;
+    }
     P.lda = (int)q.lda;
     P.ldb = (int)q.ldb;
     P.ldd = (int)q.ldd;
     P.nk = (int)(q.K / 128);
-    P.tiles_m = (int)(q.M / bm[cfg]);
-    P.tiles_n = (int)(q.N / bn[cfg]);
-    MI_CHECK_ARG(P.tiles_m < 16384 && P.tiles_n < 16384, "mi_gemm_fp8_grouped: problem %d has too many tiles per dimension", order[k]);
+    P.tiles_m = (int)(q.M / kTileBm[cfg]);
+    P.tiles_n = (int)(q.N / kTileBn[cfg]);
     P.ntiles = P.tiles_m * P.tiles_n;
     P.tile_base = total;
     P.a_bytes = (int)(q.M * q.lda);
@@ -783,15 +667,92 @@ extern "C" int mi_gemm_fp8_grouped(const mi_gemm_problem* problems, int n, int f
   }
   ga.n = n;
   ga.total_tiles = total;
+  const int ncu = num_cus();
   const int grid = total < ncu ? total : (ncu > kMaxWg ? kMaxWg : ncu);
   const Sched& sc = cached_sched(grid, n, ntiles, nks);
-  MI_CHECK_ARG(sc.ok && sc.max_per_wg <= kMaxPerWg, "mi_gemm_fp8_grouped: more than %d tiles per workgroup (%d tiles in all)", kMaxPerWg, total);
+  if (!(sc.ok && sc.max_per_wg <= kMaxPerWg)) {
+    set_error("%s: more than %d tiles per workgroup (%d tiles in all)", who, kMaxPerWg, total);
+    return mx ? MI_ERR_SHAPE : MI_ERR_ARG;  // each entry point answers a shape it cannot take with the code it always has
+  }
   std::memcpy(ga.cnt, sc.cnt, sizeof(ga.cnt));
   std::memcpy(ga.R, sc.R, sizeof(ga.R));
   hipStream_t st = (hipStream_t)stream;
   if (four_wave) return launch_w4_grouped(ga, fmt_a, fmt_b, grid, st);
-  if (fmt_a == 0 && fmt_b == 0) return launch_grouped<0, 0>(ga, cfg, grid, st);
-  if (fmt_a == 1 && fmt_b == 0) return launch_grouped<1, 0>(ga, cfg, grid, st);
-  if (fmt_a == 0 && fmt_b == 1) return launch_grouped<0, 1>(ga, cfg, grid, st);
-  return launch_grouped<1, 1>(ga, cfg, grid, st);
+  return mx ? launch_grouped_fmt<true>(ga, fmt_a, fmt_b, cfg, grid, st) : launch_grouped_fmt<false>(ga, fmt_a, fmt_b, cfg, grid, st);
+}
+
+}  // namespace mi
+
+extern "C" int mi_gemm_mxfp8_grouped(const mi_gemm_mx_problem* problems, int n, int fmt_a, int fmt_b, int tile_cfg, void* stream) {
+  using namespace mi;
+  MI_CHECK_ARG(problems && n >= 1 && n <= kMaxGroup, "mi_gemm_mxfp8_grouped: 1 to %d problems", kMaxGroup);
+  MI_CHECK_ARG((fmt_a == 0 || fmt_a == 1) && (fmt_b == 0 || fmt_b == 1), "mi_gemm_mxfp8_grouped: bad fmt");
+  MI_CHECK_ARG(tile_cfg != 4, "mi_gemm_mxfp8_grouped: tile_cfg 4 (four-wave kernel) has no block-scaled form");
+  MI_CHECK_ARG(tile_cfg >= -1 && tile_cfg < 4, "mi_gemm_mxfp8_grouped: tile_cfg must be -1 or 0-3");
+  GroupIn in[kMaxGroup];
+  for (int i = 0; i < n; ++i) {
+    const mi_gemm_mx_problem& q = problems[i];
+    MI_CHECK_ARG(q.A && q.SA && q.B && q.SB && q.D, "mi_gemm_mxfp8_grouped: null pointer in problem %d", i);
+    MI_CHECK_ARG(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.B % 16) == 0 && ((uintptr_t)q.D % 16) == 0 &&
+                     ((uintptr_t)q.SA % 16) == 0 && ((uintptr_t)q.SB % 16) == 0,
+                 "mi_gemm_mxfp8_grouped: operands and scales of problem %d must be 16-byte aligned", i);
+    if (!(q.M > 0 && q.N > 0 && q.K > 0 && q.K % 256 == 0)) {
+      set_error("mi_gemm_mxfp8_grouped: problem %d (%lld x %lld x %lld) needs M, N > 0 and K %% 256 == 0", i, (long long)q.M,
+                (long long)q.N, (long long)q.K);
+      return MI_ERR_SHAPE;
+    }
+    in[i] = {q.A, q.B, q.SA, q.SB, q.D, q.M, q.N, q.K, q.K, q.K, q.N, i};  // MX operands are tight
+  }
+  const int ncu = num_cus();
+  const int cfg = tile_cfg < 0 ? pick_group_cfg(in, n, ncu) : tile_cfg;
+  if (cfg < 0) {
+    for (int i = 0; i < n; ++i)
+      if (pick_group_cfg(in + i, 1, ncu) < 0) {
+        set_error("mi_gemm_mxfp8_grouped: no tile shape divides problem %d (%lld x %lld)", i, (long long)in[i].M, (long long)in[i].N);
+        return MI_ERR_SHAPE;
+      }
+    set_error("mi_gemm_mxfp8_grouped: no tile shape divides every one of the %d problems", n);
+    return MI_ERR_SHAPE;
+  }
+  sort_by_decreasing_k(in, n);
+  for (int k = 0; k < n; ++k) {
+    const GroupIn& q = in[k];
+    if (q.M % kTileBm[cfg] || q.N % kTileBn[cfg]) {
+      set_error("mi_gemm_mxfp8_grouped: problem %d (%lld x %lld x %lld) does not fit tile shape %d x %d", q.index, (long long)q.M,
+                (long long)q.N, (long long)q.K, kTileBm[cfg], kTileBn[cfg]);
+      return MI_ERR_SHAPE;
+    }
+    if (!group_sizes_ok("mi_gemm_mxfp8_grouped", q, cfg)) return MI_ERR_SHAPE;
+  }
+  return launch_group("mi_gemm_mxfp8_grouped", in, n, cfg, fmt_a, fmt_b, true, false, stream);
+}
+
+extern "C" int mi_gemm_fp8_grouped(const mi_gemm_problem* problems, int n, int fmt_a, int fmt_b, int tile_cfg, void* stream) {
+  using namespace mi;
+  MI_CHECK_ARG(problems && n >= 1 && n <= kMaxGroup, "mi_gemm_fp8_grouped: 1 to %d problems", kMaxGroup);
+  MI_CHECK_ARG((fmt_a == 0 || fmt_a == 1) && (fmt_b == 0 || fmt_b == 1), "mi_gemm_fp8_grouped: bad fmt");
+  GroupIn in[kMaxGroup];
+  for (int i = 0; i < n; ++i) {
+    const mi_gemm_problem& q = problems[i];
+    in[i] = {q.A, q.B, q.sa_inv, q.sb_inv, q.D, q.M, q.N, q.K, q.lda, q.ldb, q.ldd, i};
+  }
+  // tile shape: the caller's, or (any negative tile_cfg) the one pick_group_cfg finds for the whole group
+  // tile_cfg 4 = 256 x 256 tiles on the four-wave kernel (mi_gemm_w4.hip; every problem K >= 512): same schedule, other kernel
+  const bool four_wave = tile_cfg == 4;
+  const int cfg = four_wave ? 0 : tile_cfg < 0 ? pick_group_cfg(in, n, num_cus()) : tile_cfg;
+  MI_CHECK_ARG(cfg >= 0 && cfg < 4, "mi_gemm_fp8_grouped: no tile shape divides every problem");
+  sort_by_decreasing_k(in, n);
+  for (int k = 0; k < n; ++k) {
+    const GroupIn& q = in[k];
+    MI_CHECK_ARG(q.A && q.B && q.D && q.sa && q.sb, "mi_gemm_fp8_grouped: null pointer in problem %d", q.index);
+    MI_CHECK_ARG(q.M > 0 && q.N > 0 && q.K > 0 && q.M % kTileBm[cfg] == 0 && q.N % kTileBn[cfg] == 0 && q.K % 256 == 0,
+                 "mi_gemm_fp8_grouped: problem %d (%lld x %lld x %lld) does not fit tile shape %d x %d / K %% 256", q.index,
+                 (long long)q.M, (long long)q.N, (long long)q.K, kTileBm[cfg], kTileBn[cfg]);
+    MI_CHECK_ARG(q.lda >= q.K && q.ldb >= q.K && q.ldd >= q.N && q.lda % 16 == 0 && q.ldb % 16 == 0 && q.ldd % 4 == 0,
+                 "mi_gemm_fp8_grouped: bad leading dimensions in problem %d", q.index);
+    MI_CHECK_ARG(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.B % 16) == 0 && ((uintptr_t)q.D % 16) == 0,
+                 "mi_gemm_fp8_grouped: operands must be 16-byte aligned");
+    if (!group_sizes_ok("mi_gemm_fp8_grouped", q, cfg)) return MI_ERR_ARG;
+  }
+  return launch_group("mi_gemm_fp8_grouped", in, n, cfg, fmt_a, fmt_b, false, four_wave, stream);
 }

@@ -366,59 +366,44 @@ def _wgrad_out(weights, K: int) -> Optional[torch.Tensor]:
     return arena[off:end].view(-1, K)
 
 
-def _dgrad_wgrad(g8, wt8, g8t, xt8, sig, si_w, si_x, fmt_b: int, fmt_f: int, dw_out, need_dgrad: bool, need_wgrad: bool):
-    """A Linear's two backward GEMMs on one grad_output: dX [M, K] = G8 [M, N] . W8T [K, N]^T and dW [N, K] = G8T [N, M] . X8T [K, M]^T.
-    ONE grouped persistent launch (ops.gemm_fp8_grouped) where that is faster (ops.grouped_gemm_choice: measured once per shape in
-    a single-process run, the count model under torch.distributed; env LLM_FP8_AMD_GROUPED_GEMM = auto | plan | autotune | off) --
-    one ramp, one exposed epilogue, and the short problem's tiles fill the idle part of the long one's last round -- else two
-    launches.  Bitwise the
-    same results either way.  (Under torch.distributed the GEMMs run one workgroup per tile so that RCCL's kernels get CUs:
-    no persistent grouping there.)"""
-    dx = dw = None
+def _grouped_or_two(dgrad, wgrad, mx: bool, fmt_b: int, fmt_f: int, dw_out, need_dgrad: bool, need_wgrad: bool):
+    """A Linear's two backward GEMMs on one grad_output: dX [M, K] = G8 [M, N] . W8T [K, N]^T and dW [N, K] = G8T [N, M] . X8T [K, M]^T;
+    `dgrad` / `wgrad` are their operands as ops.gemm_fp8 (with `mx`: ops.gemm_mxfp8) takes them.
+    ONE grouped persistent launch (ops.gemm_fp8_grouped / ops.gemm_mxfp8_grouped) where that is faster (ops.grouped_gemm_choice:
+    measured once per shape in a single-process run, the count model under torch.distributed; env LLM_FP8_AMD_GROUPED_GEMM =
+    auto | plan | autotune | off) -- one ramp, one exposed epilogue, and the short problem's tiles fill the idle part of the long
+    one's last round -- else two launches.  Bitwise the same results either way; `dw_out` (the gradient-arena slot) stays the
+    wgrad's output.  (Under torch.distributed the GEMMs run one workgroup per tile so that RCCL's kernels get CUs: no persistent
+    grouping there.)"""
     if need_dgrad and need_wgrad and ops.default_gemm_algo() in (0, 4, 47) and os.environ.get("LLM_FP8_AMD_NO_GROUPED_GEMM") != "1":
+        g8, wt8 = dgrad[0], dgrad[2 if mx else 1]
         M, N = g8.shape
         K = wt8.shape[0]
-        if (ops.grouped_gemm_ok(((M, K, N), (N, K, M))) and g8.stride(1) == 1 and wt8.stride(1) == 1 and g8t.stride(1) == 1
-                and xt8.stride(1) == 1):
+        # per-tensor operands may be row-strided views; block-scaled operands and their scales are tight
+        layout_ok = (all(t.is_contiguous() for t in dgrad + wgrad) if mx else
+                     all(t.stride(1) == 1 for t in dgrad[:2] + wgrad[:2]))
+        if ops.grouped_gemm_ok(((M, K, N), (N, K, M))) and layout_ok:
             dx = torch.empty((M, K), dtype=torch.bfloat16, device=g8.device)
             dw = dw_out if dw_out is not None else torch.empty((N, K), dtype=torch.bfloat16, device=g8.device)
-            probs = [(g8, wt8, sig, si_w, dx), (g8t, xt8, sig, si_x, dw)]
-            cfg = ops.grouped_gemm_choice(probs, fmt_b, fmt_f)  # cached per shape set: -1 = two launches are faster here
+            probs = [dgrad + (dx,), wgrad + (dw,)]
+            cfg = ops.grouped_gemm_choice(probs, fmt_b, fmt_f, mx=mx)  # cached per shape set: -1 = two launches are faster here
             if cfg >= 0:
-                ops.gemm_fp8_grouped(probs, fmt_b, fmt_f, tile_cfg=cfg)
+                (ops.gemm_mxfp8_grouped if mx else ops.gemm_fp8_grouped)(probs, fmt_b, fmt_f, tile_cfg=cfg)
                 return dx, dw
-            dx = dw = None
-    if need_dgrad:
-        dx = ops.gemm_fp8(g8, wt8, sig, si_w, fmt_b, fmt_f)
-    if need_wgrad:
-        dw = ops.gemm_fp8(g8t, xt8, sig, si_x, fmt_b, fmt_f, out=dw_out)
+    gemm = ops.gemm_mxfp8 if mx else ops.gemm_fp8
+    dx = gemm(*dgrad, fmt_b, fmt_f) if need_dgrad else None
+    dw = gemm(*wgrad, fmt_b, fmt_f, out=dw_out) if need_wgrad else None
     return dx, dw
+
+
+def _dgrad_wgrad(g8, wt8, g8t, xt8, sig, si_w, si_x, fmt_b: int, fmt_f: int, dw_out, need_dgrad: bool, need_wgrad: bool):
+    """_grouped_or_two for the delayed-scaling recipes: one device scalar scale-inverse per operand."""
+    return _grouped_or_two((g8, wt8, sig, si_w), (g8t, xt8, sig, si_x), False, fmt_b, fmt_f, dw_out, need_dgrad, need_wgrad)
 
 
 def _dgrad_wgrad_mx(g8, gs, wt8, wts, gt8, gts, xt8, xts, fmt_b: int, fmt_f: int, dw_out, need_dgrad: bool, need_wgrad: bool):
-    """_dgrad_wgrad under MXFP8 block scaling: dX [M, K] = G8 [M, N] . W8T [K, N]^T and dW [N, K] = G8T [N, M] . X8T [K, M]^T, each
-    operand with its block-major E8M0 scales.  ONE grouped persistent launch (ops.gemm_mxfp8_grouped) where
-    ops.grouped_gemm_mx_choice finds it faster, under the gate of the per-tensor path (both gradients needed, a persistent default
-    algo -- so never under torch.distributed --, the switches not off, shapes eligible), else two launches.  Bitwise the same
-    results either way; `dw_out` (the gradient-arena slot) stays the wgrad's output."""
-    dx = dw = None
-    if need_dgrad and need_wgrad and ops.default_gemm_algo() in (0, 4, 47) and os.environ.get("LLM_FP8_AMD_NO_GROUPED_GEMM") != "1":
-        M, N = g8.shape
-        K = wt8.shape[0]
-        if ops.grouped_gemm_ok(((M, K, N), (N, K, M))) and all(t.is_contiguous() for t in (g8, gs, wt8, wts, gt8, gts, xt8, xts)):
-            dx = torch.empty((M, K), dtype=torch.bfloat16, device=g8.device)
-            dw = dw_out if dw_out is not None else torch.empty((N, K), dtype=torch.bfloat16, device=g8.device)
-            probs = [(g8, gs, wt8, wts, dx), (gt8, gts, xt8, xts, dw)]
-            cfg = ops.grouped_gemm_mx_choice(probs, fmt_b, fmt_f)  # cached per shape set: -1 = two launches are faster here
-            if cfg >= 0:
-                ops.gemm_mxfp8_grouped(probs, fmt_b, fmt_f, tile_cfg=cfg)
-                return dx, dw
-            dx = dw = None
-    if need_dgrad:
-        dx = ops.gemm_mxfp8(g8, gs, wt8, wts, fmt_b, fmt_f)
-    if need_wgrad:
-        dw = ops.gemm_mxfp8(gt8, gts, xt8, xts, fmt_b, fmt_f, out=dw_out)
-    return dx, dw
+    """_grouped_or_two under MXFP8 block scaling: each operand with its block-major E8M0 scales."""
+    return _grouped_or_two((g8, gs, wt8, wts), (gt8, gts, xt8, xts), True, fmt_b, fmt_f, dw_out, need_dgrad, need_wgrad)
 
 
 def _skip_2d(dskip: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:

@@ -323,11 +323,32 @@ def mxfp8_rope_bwd_quantize(dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor
     return y_row, s_row, y_colT, s_colT
 
 
+def _group_shapes(problems, mx: bool):
+    """(M, N, K) of every problem of a group: (a8, b8, sa_inv, sb_inv, out) tuples per-tensor, (a8, sa, b8, sb, out) block-scaled."""
+    ib = 2 if mx else 1
+    return tuple((p[0].shape[0], p[ib].shape[0], p[0].shape[1]) for p in problems)
+
+
+def _grouped_launch(entry: str, span: str, arr, shapes, fmt_a: int, fmt_b: int, tile_cfg: int) -> None:
+    """The tail gemm_fp8_grouped and gemm_mxfp8_grouped share: the launch of `entry` over the marshalled problems `arr` of the
+    given (M, N, K), inside a KernelTimer span `span` where a timer is active."""
+    fn = getattr(_lib.load(), entry)
+    args = (ctypes.byref(arr), len(shapes), fmt_a, fmt_b, tile_cfg, _stream())
+    t = KernelTimer.active
+    if t is None:
+        rc = fn(*args)
+    else:
+        work = sum(2.0 * M * N * K for M, N, K in shapes)
+        nbytes = sum(M * K + N * K + 2 * M * N for M, N, K in shapes)
+        with t.span(span, "+".join(f"{M}x{N}x{K}" for M, N, K in shapes), work, nbytes):
+            rc = fn(*args)
+    _lib.check(rc, entry)
+
+
 def gemm_fp8_grouped(problems, fmt_a: int, fmt_b: int, tile_cfg: int = -1) -> None:
     """ONE persistent launch for up to 4 GEMMs D = (A . B^T) * (sa_inv * sb_inv) (mi_gemm_fp8_grouped): `problems` is a list of
     (a8 [M,K], b8 [N,K], sa_inv, sb_inv, out bf16 [M,N]); all share the operand formats.  Outputs are written in place."""
-    n = len(problems)
-    arr = (_lib.GemmProblem * n)()
+    arr = (_lib.GemmProblem * len(problems))()
     for i, (a8, b8, sa, sb, out) in enumerate(problems):
         _dev(a8, b8, sa, sb, out)
         assert a8.dtype == torch.uint8 and b8.dtype == torch.uint8 and out.dtype == torch.bfloat16
@@ -335,24 +356,14 @@ def gemm_fp8_grouped(problems, fmt_a: int, fmt_b: int, tile_cfg: int = -1) -> No
         assert out.shape == (a8.shape[0], b8.shape[0])
         arr[i] = _lib.GemmProblem(a8.data_ptr(), b8.data_ptr(), out.data_ptr(), sa.data_ptr(), sb.data_ptr(), a8.shape[0], b8.shape[0],
                                   a8.shape[1], a8.stride(0), b8.stride(0), out.stride(0))
-    t = KernelTimer.active
-    if t is None:
-        rc = _lib.load().mi_gemm_fp8_grouped(ctypes.byref(arr), n, fmt_a, fmt_b, tile_cfg, _stream())
-    else:
-        work = sum(2.0 * a.shape[0] * b.shape[0] * a.shape[1] for a, b, _, _, _ in problems)
-        nbytes = sum(a.numel() + b.numel() + 2 * o.numel() for a, b, _, _, o in problems)
-        tag = "+".join(f"{a.shape[0]}x{b.shape[0]}x{a.shape[1]}" for a, b, _, _, _ in problems)
-        with t.span("gemm_fp8", tag, work, nbytes):
-            rc = _lib.load().mi_gemm_fp8_grouped(ctypes.byref(arr), n, fmt_a, fmt_b, tile_cfg, _stream())
-    _lib.check(rc, "mi_gemm_fp8_grouped")
+    _grouped_launch("mi_gemm_fp8_grouped", "gemm_fp8", arr, _group_shapes(problems, False), fmt_a, fmt_b, tile_cfg)
 
 
 def gemm_mxfp8_grouped(problems, fmt_a: int, fmt_b: int, tile_cfg: int = -1) -> None:
     """ONE persistent launch for up to 4 block-scaled GEMMs (mi_gemm_mxfp8_grouped): `problems` is a list of
     (a8 [M,K], sa [K/32,M], b8 [N,K], sb [K/32,N], out bf16 [M,N]), operands as for gemm_mxfp8; all share the operand formats.
     Outputs are written in place, bit for bit what gemm_mxfp8(algo=4) gives per problem."""
-    n = len(problems)
-    arr = (_lib.GemmMxProblem * n)()
+    arr = (_lib.GemmMxProblem * len(problems))()
     for i, (a8, sa, b8, sb, out) in enumerate(problems):
         _dev(a8, sa, b8, sb, out)
         M, K = a8.shape
@@ -362,16 +373,7 @@ def gemm_mxfp8_grouped(problems, fmt_a: int, fmt_b: int, tile_cfg: int = -1) -> 
         assert sa.shape == (K // 32, M) and sb.shape == (K // 32, N), "scales must be block-major [K/32, rows]"
         assert out.is_contiguous() and out.shape == (M, N)
         arr[i] = _lib.GemmMxProblem(a8.data_ptr(), sa.data_ptr(), b8.data_ptr(), sb.data_ptr(), out.data_ptr(), M, N, K)
-    t = KernelTimer.active
-    if t is None:
-        rc = _lib.load().mi_gemm_mxfp8_grouped(ctypes.byref(arr), n, fmt_a, fmt_b, tile_cfg, _stream())
-    else:
-        work = sum(2.0 * a.shape[0] * b.shape[0] * a.shape[1] for a, _, b, _, _ in problems)
-        nbytes = sum(a.numel() + b.numel() + 2 * o.numel() for a, _, b, _, o in problems)
-        tag = "+".join(f"{a.shape[0]}x{b.shape[0]}x{a.shape[1]}" for a, _, b, _, _ in problems)
-        with t.span("gemm_mxfp8", tag, work, nbytes):
-            rc = _lib.load().mi_gemm_mxfp8_grouped(ctypes.byref(arr), n, fmt_a, fmt_b, tile_cfg, _stream())
-    _lib.check(rc, "mi_gemm_mxfp8_grouped")
+    _grouped_launch("mi_gemm_mxfp8_grouped", "gemm_mxfp8", arr, _group_shapes(problems, True), fmt_a, fmt_b, tile_cfg)
 
 
 def grouped_gemm_ok(shapes, strides_ok: bool = True) -> bool:
@@ -439,9 +441,10 @@ def grouped_gemm_plan(shapes, n_cu: int = 256) -> int:
 _GROUP_TUNED: dict = {}
 
 
-def grouped_gemm_choice(problems, fmt_a: int, fmt_b: int) -> int:
-    """-1 = launch a Linear's dgrad and wgrad separately, 0-3 = one grouped launch with that tile shape.  Policy
-    (env LLM_FP8_AMD_GROUPED_GEMM):
+def grouped_gemm_choice(problems, fmt_a: int, fmt_b: int, mx: bool = False) -> int:
+    """-1 = launch a Linear's dgrad and wgrad separately, 0-3 = one grouped launch with that tile shape, 4 = one grouped launch of
+    256 x 256 tiles on the four-wave kernel (never under `mx`: that kernel has no block-scaled form).  `problems` as for
+    gemm_fp8_grouped, or, with `mx`, as for gemm_mxfp8_grouped.  Policy (env LLM_FP8_AMD_GROUPED_GEMM):
       auto (default)  single process: `autotune` -- MEASURED once per (shapes, formats) the first time the shape set shows up, i.e.
                       inside the first backward of a run: ~7 timed relaunches per candidate on SCRATCH outputs and one host
                       synchronisation per candidate; every later step only reads the cache (no host sync).  Under torch.distributed:
@@ -457,37 +460,44 @@ def grouped_gemm_choice(problems, fmt_a: int, fmt_b: int) -> int:
         import torch.distributed as dist
         mode = "plan" if (dist.is_available() and dist.is_initialized()) else "autotune"
     if mode == "plan":
-        return grouped_gemm_plan(tuple((a.shape[0], b.shape[0], a.shape[1]) for a, b, _, _, _ in problems))
+        return grouped_gemm_plan(_group_shapes(problems, mx))
     if mode != "autotune":
         raise ValueError(f"LLM_FP8_AMD_GROUPED_GEMM={mode!r}: expected auto, plan, autotune or off")
-    return grouped_gemm_autotune(problems, fmt_a, fmt_b)
+    return grouped_gemm_autotune(problems, fmt_a, fmt_b, mx=mx)
 
 
-def grouped_gemm_autotune(problems, fmt_a: int, fmt_b: int, iters: int = 5) -> int:
-    """Measured choice for a recurring group of GEMMs (a Linear's dgrad + wgrad): -1 = separate launches, 0-3 = one grouped launch
-    with that tile shape, 4 = one grouped launch of 256 x 256 tiles on the four-wave kernel.  Timed once per (shapes, formats) on the operands at hand but into SCRATCH outputs (the live dX buffer and
-    gradient-arena slot are not touched), and cached.  The model (grouped_gemm_plan) ranks the same candidates from counts alone;
-    the measurement also sees what the model leaves out (per-tile epilogue cost, L2 behaviour, clock)."""
-    shapes = tuple((a.shape[0], b.shape[0], a.shape[1]) for a, b, _, _, _ in problems)
-    key = (shapes, fmt_a, fmt_b)
+def _tuned_key(shapes, fmt_a: int, fmt_b: int, mx: bool):
+    """Cache key of a group in _GROUP_TUNED: that of a block-scaled group is never that of a per-tensor group of equal shapes."""
+    return ("mx", tuple(shapes), fmt_a, fmt_b) if mx else (tuple(shapes), fmt_a, fmt_b)
+
+
+def grouped_gemm_autotune(problems, fmt_a: int, fmt_b: int, iters: int = 5, mx: bool = False) -> int:
+    """Measured choice for a recurring group of GEMMs (a Linear's dgrad + wgrad): -1 = separate launches (gemm_fp8, with `mx`
+    gemm_mxfp8, at the default algo), 0-3 = one grouped launch with that tile shape, 4 = one grouped launch of 256 x 256 tiles on
+    the four-wave kernel (per-tensor only).  Timed once per (shapes, formats) on the operands at hand but into SCRATCH outputs (the
+    live dX buffer and gradient-arena slot are not touched), and cached, a block-scaled group under a key of its own.  The model
+    (grouped_gemm_plan) ranks the same candidates from counts alone; the measurement also sees what the model leaves out (per-tile
+    epilogue cost, L2 behaviour, clock)."""
+    shapes = _group_shapes(problems, mx)
+    key = _tuned_key(shapes, fmt_a, fmt_b, mx)
     hit = _GROUP_TUNED.get(key)
     if hit is not None:
         return hit
-    problems = [(a8, b8, sa, sb, torch.empty_like(out)) for a8, b8, sa, sb, out in problems]
-    cands = {-1: None}
+    single, grouped = (gemm_mxfp8, gemm_mxfp8_grouped) if mx else (gemm_fp8, gemm_fp8_grouped)
+    problems = [(*p[:4], torch.empty_like(p[4])) for p in problems]
+    cands = [-1]
     if grouped_gemm_ok(shapes):
-        for cfg, (bm, bn) in enumerate(_TILE_CFGS):
-            if all(M % bm == 0 and N % bn == 0 for M, N, K in shapes):
-                cands[cfg] = cfg
-        if all(M % 256 == 0 and N % 256 == 0 and K >= 512 for M, N, K in shapes) and os.environ.get("LLM_FP8_AMD_GEMM_W4G", "1") != "0":
-            cands[4] = 4  # 256 x 256 tiles on the four-wave kernel (mi_gemm_w4.hip)
+        cands += [cfg for cfg, (bm, bn) in enumerate(_TILE_CFGS) if all(M % bm == 0 and N % bn == 0 for M, N, K in shapes)]
+        if (not mx and all(M % 256 == 0 and N % 256 == 0 and K >= 512 for M, N, K in shapes)
+                and os.environ.get("LLM_FP8_AMD_GEMM_W4G", "1") != "0"):
+            cands.append(4)  # 256 x 256 tiles on the four-wave kernel (mi_gemm_w4.hip)
 
     def run(c):
         if c == -1:
-            for a8, b8, sa, sb, out in problems:
-                gemm_fp8(a8, b8, sa, sb, fmt_a, fmt_b, out=out)  # the default algo: what two separate launches would really run
+            for p in problems:
+                single(*p[:4], fmt_a, fmt_b, out=p[4])  # the default algo: what two separate launches would really run
         else:
-            gemm_fp8_grouped(problems, fmt_a, fmt_b, tile_cfg=c)
+            grouped(problems, fmt_a, fmt_b, tile_cfg=c)
 
     saved, KernelTimer.active = KernelTimer.active, None  # (the candidates are not part of any timed span)
     try:
@@ -522,86 +532,6 @@ def grouped_gemm_autotune(problems, fmt_a: int, fmt_b: int, iters: int = 5) -> i
         # (profiles/r03_grouped_w4_ab.txt); inside a first backward the five rounds above still carry ~1 % of noise: it takes ties
         if 4 in total and best not in (-1, 4) and total[4] <= 1.01 * best_t:
             best, best_t = 4, total[4]
-    finally:
-        KernelTimer.active = saved
-    _GROUP_TUNED[key] = best
-    return best
-
-
-def _mx_shapes(problems):
-    return tuple((a.shape[0], b.shape[0], a.shape[1]) for a, _, b, _, _ in problems)
-
-
-def grouped_gemm_mx_choice(problems, fmt_a: int, fmt_b: int) -> int:
-    """grouped_gemm_choice for a block-scaled group (`problems` as for gemm_mxfp8_grouped): -1 = separate gemm_mxfp8 launches,
-    0-3 = one gemm_mxfp8_grouped launch with that tile shape (never 4: the four-wave kernel has no block-scaled form).  Same policy
-    and the same environment switch (LLM_FP8_AMD_GROUPED_GEMM = auto | plan | autotune | off)."""
-    mode = os.environ.get("LLM_FP8_AMD_GROUPED_GEMM", "auto")
-    if mode == "off":
-        return -1
-    if mode == "auto":
-        import torch.distributed as dist
-        mode = "plan" if (dist.is_available() and dist.is_initialized()) else "autotune"
-    if mode == "plan":
-        return grouped_gemm_plan(_mx_shapes(problems))
-    if mode != "autotune":
-        raise ValueError(f"LLM_FP8_AMD_GROUPED_GEMM={mode!r}: expected auto, plan, autotune or off")
-    return grouped_gemm_mx_autotune(problems, fmt_a, fmt_b)
-
-
-def _mx_tuned_key(shapes, fmt_a: int, fmt_b: int):
-    """Cache key of a block-scaled group in _GROUP_TUNED: never that of a per-tensor group of equal shapes."""
-    return ("mx", tuple(shapes), fmt_a, fmt_b)
-
-
-def grouped_gemm_mx_autotune(problems, fmt_a: int, fmt_b: int, iters: int = 5) -> int:
-    """grouped_gemm_autotune for a block-scaled group: the same interleaved rounds into SCRATCH outputs, candidates -1 (separate
-    gemm_mxfp8 launches at the default algo) and every tile shape that divides the group; cached per (shapes, formats) under a key
-    of its own."""
-    shapes = _mx_shapes(problems)
-    key = _mx_tuned_key(shapes, fmt_a, fmt_b)
-    hit = _GROUP_TUNED.get(key)
-    if hit is not None:
-        return hit
-    problems = [(a8, sa, b8, sb, torch.empty_like(out)) for a8, sa, b8, sb, out in problems]
-    cands = [-1]
-    if grouped_gemm_ok(shapes):
-        cands += [cfg for cfg, (bm, bn) in enumerate(_TILE_CFGS) if all(M % bm == 0 and N % bn == 0 for M, N, K in shapes)]
-
-    def run(c):
-        if c == -1:
-            for a8, sa, b8, sb, out in problems:
-                gemm_mxfp8(a8, sa, b8, sb, fmt_a, fmt_b, out=out)  # the default algo: what two separate launches would really run
-        else:
-            gemm_mxfp8_grouped(problems, fmt_a, fmt_b, tile_cfg=c)
-
-    saved, KernelTimer.active = KernelTimer.active, None  # (the candidates are not part of any timed span)
-    try:
-        live = []
-        for c in cands:
-            try:
-                run(c)  # warm-up; a candidate the library refuses drops out
-                live.append(c)
-            except RuntimeError:
-                continue
-        total = {c: 0.0 for c in live}
-        for r in range(iters):  # interleaved rounds, rotating order (see grouped_gemm_autotune)
-            order = live[r % len(live):] + live[:r % len(live)]
-            for c in order:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                run(c)
-                run(c)
-                e1.record()
-                e1.synchronize()
-                total[c] += e0.elapsed_time(e1)
-        best, best_t = -1, total.get(-1)
-        for c in live:
-            if c == -1:
-                continue
-            t = total[c]
-            if best_t is None or t < best_t * (0.98 if best == -1 else 1.0):  # a grouped launch must win by 2 % over separate ones
-                best, best_t = c, t
     finally:
         KernelTimer.active = saved
     _GROUP_TUNED[key] = best

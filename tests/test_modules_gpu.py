@@ -749,8 +749,12 @@ def test_grouped_backward_gemms_change_nothing(te, dev, monkeypatch):
         calls = {"n": 0}
         if grouped:
             monkeypatch.delenv("LLM_FP8_AMD_NO_GROUPED_GEMM", raising=False)
-            monkeypatch.setattr(_ops, "grouped_gemm_autotune", lambda problems, fa, fb, iters=3: 0 if all(
-                a.shape[0] % 256 == 0 and b.shape[0] % 256 == 0 for a, b, _, _, _ in problems) else 3)
+
+            def autotune(problems, fa, fb, iters=3, mx=False):
+                assert mx is False  # the per-tensor sites must not ask for the block-scaled candidates and cache entry
+                return 0 if all(a.shape[0] % 256 == 0 and b.shape[0] % 256 == 0 for a, b, _, _, _ in problems) else 3
+
+            monkeypatch.setattr(_ops, "grouped_gemm_autotune", autotune)
             orig = _ops.gemm_fp8_grouped
             monkeypatch.setattr(_ops, "gemm_fp8_grouped", lambda *a, **k: (calls.__setitem__("n", calls["n"] + 1), orig(*a, **k))[1])
         else:

@@ -110,7 +110,8 @@ def test_mx_and_per_tensor_groups_do_not_share_a_cache_entry():
     try:
         ops._GROUP_TUNED.clear()
         ops._GROUP_TUNED[(shapes, 1, 0)] = 4   # what grouped_gemm_autotune stores for the per-tensor group (4: the four-wave form)
-        key = ops._mx_tuned_key(shapes, 1, 0)
+        key = ops._tuned_key(shapes, 1, 0, True)
+        assert ops._tuned_key(shapes, 1, 0, False) == (shapes, 1, 0)
         assert key != (shapes, 1, 0) and key not in ops._GROUP_TUNED
         ops._GROUP_TUNED[key] = 0
         # cached answers come back without touching the operands: meta tensors have no storage
@@ -118,7 +119,7 @@ def test_mx_and_per_tensor_groups_do_not_share_a_cache_entry():
         o = lambda r, c: torch.empty((r, c), dtype=torch.bfloat16, device="meta")
         mx = [(t(M, K), t(K // 32, M), t(N, K), t(K // 32, N), o(M, N)) for M, N, K in shapes]
         pt = [(t(M, K), t(N, K), None, None, o(M, N)) for M, N, K in shapes]
-        assert ops.grouped_gemm_mx_autotune(mx, 1, 0) == 0
+        assert ops.grouped_gemm_autotune(mx, 1, 0, mx=True) == 0
         assert ops.grouped_gemm_autotune(pt, 1, 0) == 4
     finally:
         ops._GROUP_TUNED.clear()
@@ -128,10 +129,10 @@ def test_mx_and_per_tensor_groups_do_not_share_a_cache_entry():
 def test_switch_off_returns_minus_one_without_touching_a_tensor(monkeypatch):
     from llm_fp8_amd.pytorch import ops
     monkeypatch.setenv("LLM_FP8_AMD_GROUPED_GEMM", "off")
-    assert ops.grouped_gemm_mx_choice([(None, None, None, None, None)] * 2, 1, 0) == -1
+    assert ops.grouped_gemm_choice([(None, None, None, None, None)] * 2, 1, 0, mx=True) == -1
     monkeypatch.setenv("LLM_FP8_AMD_GROUPED_GEMM", "plan")  # the count model: shapes only
     t = lambda r, c: torch.empty((r, c), dtype=torch.uint8, device="meta")
     shapes = ((8192, 3072, 8192), (8192, 3072, 8192))
     probs = [(t(M, K), None, t(N, K), None, None) for M, N, K in shapes]
-    assert ops.grouped_gemm_mx_choice(probs, 1, 0) == ops.grouped_gemm_plan(shapes)
-    assert ops.grouped_gemm_mx_choice(probs, 1, 0) in (-1, 0, 1, 2, 3)
+    assert ops.grouped_gemm_choice(probs, 1, 0, mx=True) == ops.grouped_gemm_plan(shapes)
+    assert ops.grouped_gemm_choice(probs, 1, 0, mx=True) in (-1, 0, 1, 2, 3)

@@ -190,8 +190,19 @@ def _force_grouped(monkeypatch, ops_, calls):
     """Every eligible site takes the grouped launch (through the autotune, as the per-tensor twin of this test does)."""
     monkeypatch.delenv("LLM_FP8_AMD_NO_GROUPED_GEMM", raising=False)
     monkeypatch.delenv("LLM_FP8_AMD_GROUPED_GEMM", raising=False)
-    monkeypatch.setattr(ops_, "grouped_gemm_mx_autotune", lambda problems, fa, fb, iters=3: 0 if all(
-        a.shape[0] % 256 == 0 and b.shape[0] % 256 == 0 for a, _, b, _, _ in problems) else 3)
+
+    real = ops_.grouped_gemm_autotune
+
+    def autotune(problems, fa, fb, iters=3, mx=False):
+        # a block-scaled group (second operand slot: the [K/32, M] scales of the first) must ask for the block-scaled candidates
+        # and cache entry, a per-tensor one (the model's delayed-scaling Linear) must not
+        a, sa = problems[0][:2]
+        assert mx is (sa.shape == (a.shape[1] // 32, a.shape[0]))
+        if not mx:
+            return real(problems, fa, fb, iters, mx=False)  # measured, as it is without this stand-in
+        return 0 if all(a.shape[0] % 256 == 0 and b.shape[0] % 256 == 0 for a, _, b, _, _ in problems) else 3
+
+    monkeypatch.setattr(ops_, "grouped_gemm_autotune", autotune)
     orig = ops_.gemm_mxfp8_grouped
     monkeypatch.setattr(ops_, "gemm_mxfp8_grouped", lambda *a, **k: (calls.__setitem__("n", calls["n"] + 1), orig(*a, **k))[1])
     return orig

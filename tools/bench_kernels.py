@@ -319,7 +319,7 @@ def main():
                         for a8, sa, b8, sb, o in mx:
                             ops.gemm_mxfp8(a8, sa, b8, sb, 0, 0, out=o, algo=4)
                     cands = {"separate": sep_mx}
-                    for cfg, (bm, bn) in enumerate(((256, 256), (256, 192), (192, 256), (192, 192))):
+                    for cfg, (bm, bn) in enumerate(ops._TILE_CFGS):
                         if all(a8.shape[0] % bm == 0 and b8.shape[0] % bn == 0 for a8, _, b8, _, _ in mx):
                             cands[f"grouped{cfg}"] = (lambda c: lambda: ops.gemm_mxfp8_grouped(mx, 0, 0, tile_cfg=c))(cfg)
                     res = time_interleaved(cands, rounds=10, inner=4)
