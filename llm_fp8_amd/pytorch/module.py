@@ -89,13 +89,13 @@ def handoff_readers(t) -> bool:
 class _GemmSpec:
     """Everything non-tensor a GEMM site needs: recipe, meta windows, slot base, update trigger."""
     __slots__ = ("recipe", "meta_fwd", "meta_bwd", "g", "fmt_fwd", "fmt_bwd", "trigger_bwd_update", "training", "eps",
-                 "wcache", "first_mb", "with_skip", "rstd", "dy_handoff", "defer_bias")
+                 "wcache", "first_mb", "with_skip", "rstd", "dy_handoff", "defer_bias", "q")
 
     def __init__(self, recipe, meta_fwd, meta_bwd, g, trigger_bwd_update, training, eps=1e-5, wcache=None, first_mb=None,
                  with_skip=False, rstd=None, dy_handoff=None, defer_bias=False):
         self.dy_handoff = dy_handoff
-        # LayerNormMLP (delayed scaling, fused SwiGLU): the fc1 bias is added inside the SwiGLU kernels (always, when there is
-        # one) and -- defer_bias -- the fc2 bias is left to the caller's residual add (residual_add_stats(..., bias=...)): TE's
+        # LayerNormMLP (fused SwiGLU): under delayed scaling the fc1 bias is added inside the SwiGLU kernels (always, when there
+        # is one) and -- defer_bias, both recipes -- the fc2 bias is left to the caller's residual add (residual_add_stats(..., bias=...)): TE's
         # bias + activation fusion.  The bias add costs 12 % of a K = 3072 GEMM in its epilogue and nothing in an HBM-bound kernel.
         self.defer_bias = defer_bias
         self.eps = eps
@@ -109,11 +109,40 @@ class _GemmSpec:
         self.wcache, self.first_mb = wcache, first_mb
         self.recipe, self.meta_fwd, self.meta_bwd, self.g = recipe, meta_fwd, meta_bwd, g
         self.fmt_fwd, self.fmt_bwd = fmt_codes(recipe.fp8_format)
+        # q: what differs between the recipes at a GEMM site (the only place that chooses)
+        self.q = _MXQ(self.fmt_fwd, self.fmt_bwd) if recipe.mxfp8() else _DelayedQ(meta_fwd, meta_bwd, self.fmt_fwd, self.fmt_bwd)
         self.trigger_bwd_update = trigger_bwd_update
         self.training = training
 
 
-class WeightSink:
+class _Sink:
+    """What WeightSink and MXWeightSink share: `parts` = (weight, first row, rows) of the operand, announced to the optimiser on the
+    weights themselves, and `stamp` = what `_now()` gave when the optimiser last rewrote every part (the copies are current while
+    it still gives that)."""
+    __slots__ = ("parts", "stamp")
+
+    def _register(self, weights, ns, attr: str) -> None:
+        self.parts, r = [], 0
+        for w, n in zip(weights, ns):
+            self.parts.append((w, r, n))
+            setattr(w, attr, (self, r, n))
+            r += n
+        self.stamp = None
+
+    def holds(self, weights, mf) -> bool:
+        return len(self.parts) == len(weights) and all(a is b for (a, _, _), b in zip(self.parts, weights))
+
+    def _now(self):
+        return _part_versions(self.parts)
+
+    def fresh(self) -> bool:
+        return self.stamp is not None and self.stamp == self._now()
+
+    def mark(self) -> None:  # called by the optimiser after it rewrote every part in this step
+        self.stamp = self._now()
+
+
+class WeightSink(_Sink):
     """FP8 copies (w8 [N,K], w8T [K,N]) of one GEMM's weight operand that the OPTIMISER keeps current (optim.ClippedAdamW ->
     mi_adamw_cast_bf16_multi): under delayed scaling the scale of the next forward's weight cast is final once this step's
     forward has ended, and the optimiser streams every weight anyway, so it emits the bytes (and the amax) that forward
@@ -121,24 +150,33 @@ class WeightSink:
     step on Llama-3.2-3B).  `stamp` = (versions of the parts, generation of the scale arena) at emission; the copies are used
     only while both still match (no other write to the weights, no scale update in between: an evaluation pass or a second
     micro-batch re-casts as before)."""
-    __slots__ = ("w8", "w8t", "parts", "arena", "scale", "amax", "stamp")
+    __slots__ = ("w8", "w8t", "arena", "scale", "amax")
 
     def __init__(self, weights, ns, N, K, dev, mf, slot):
         self.w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
         self.w8t = torch.empty((K, N), dtype=torch.uint8, device=dev)
-        self.parts, r = [], 0
-        for w, n in zip(weights, ns):
-            self.parts.append((w, r, n))
-            w._mi_fp8_sink = (self, r, n)
-            r += n
         self.arena, self.scale, self.amax = mf.arena, mf.scale(slot), mf.amax(slot)
-        self.stamp = None
+        self._register(weights, ns, "_mi_fp8_sink")
 
-    def fresh(self) -> bool:
-        return self.stamp is not None and self.stamp == (_part_versions(self.parts), self.arena.generation)
+    def holds(self, weights, mf) -> bool:
+        return self.arena is mf.arena and super().holds(weights, mf)
 
-    def mark(self) -> None:  # called by the optimiser after it rewrote every part in this step
-        self.stamp = (_part_versions(self.parts), self.arena.generation)
+    def _now(self):
+        return _part_versions(self.parts), self.arena.generation
+
+
+class MXWeightSink(_Sink):
+    """MXFP8 copies (row-wise w8 [N,K] + E8M0 [K/32,N]; column-wise, stored transposed, wt8 [K,N] + E8M0 [N/32,K]) of one GEMM's
+    weight operand that the OPTIMISER keeps current (optim.ClippedAdamW -> mi_adamw_mxcast_bf16_multi).  Block scaling has no
+    state, so the only condition for using them is that nobody wrote the weights since: `stamp` = versions of the parts."""
+    __slots__ = ("w8", "sc", "wt8", "sct")
+
+    def __init__(self, weights, ns, N, K, dev):
+        self.w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
+        self.sc = torch.empty((K // 32, N), dtype=torch.uint8, device=dev)
+        self.wt8 = torch.empty((K, N), dtype=torch.uint8, device=dev)
+        self.sct = torch.empty((N // 32, K), dtype=torch.uint8, device=dev)
+        self._register(weights, ns, "_mi_mx_sink")
 
 
 def stepped_tensor(w):
@@ -189,131 +227,223 @@ def _weight_ok_for_sink(w, K: int) -> bool:
             and (w.is_contiguous() or getattr(w, "_mi_sharded", None) is not None))
 
 
-class MXWeightSink:
-    """MXFP8 copies (row-wise w8 [N,K] + E8M0 [K/32,N]; column-wise, stored transposed, wt8 [K,N] + E8M0 [N/32,K]) of one GEMM's
-    weight operand that the OPTIMISER keeps current (optim.ClippedAdamW -> mi_adamw_mxcast_bf16_multi).  Block scaling has no
-    state, so the only condition for using them is that nobody wrote the weights since: `stamp` = versions of the parts."""
-    __slots__ = ("w8", "sc", "wt8", "sct", "parts", "stamp")
+# What differs between the two recipes at a GEMM site, behind the same few methods (`_GemmSpec.q` is one or the other).  A quantised
+# operand has one shape under both: (row, col), the row-wise copy [R, C] and the column-wise one, stored transposed [C, R], each a
+# (data, scale) pair -- None data where the copy was not asked for.  `scale` is the one-element scale-inverse under delayed scaling
+# and the block-major E8M0 tensor under MXFP8.  A GEMM contracts the row-wise copies of its operands: the forward takes `row` of
+# the input and the weight, the backward pair takes `col` of both with the two copies of grad_output.  `g` is the GEMM's index in
+# its module.
 
-    def __init__(self, weights, ns, N, K, dev):
-        self.w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
-        self.sc = torch.empty((K // 32, N), dtype=torch.uint8, device=dev)
-        self.wt8 = torch.empty((K, N), dtype=torch.uint8, device=dev)
-        self.sct = torch.empty((N // 32, K), dtype=torch.uint8, device=dev)
-        self.parts, r = [], 0
+
+class _DelayedQ:
+    """Delayed scaling.  Meta slots of GEMM `g`: forward 3g = input, 3g + 1 = weight; backward 2g = grad_output.  What the forward
+    saves for backward (`col` of an activation, both copies of a weight) carries the scale-inverse from scale_inv_snapshot() as
+    of its quantisation -- the arena is rewritten at autocast exit, before backward; the snapshot is not -- while `row` of an
+    activation and both copies of a grad_output, consumed in the pass that makes them, carry the live one."""
+    __slots__ = ("mf", "mb", "fmt_f", "fmt_b")
+    mx = False
+    cache_key, sink_key = "ds", "sink"
+    no_sink = "row-sharded weights of this shape cannot take an FP8 sink"
+    swiglu_adds_bias = True     # the fc1 bias of the fused MLP is added inside the SwiGLU kernels
+    colsum_dtypes = None        # a Linear's bias gradient rides on the cast of dy whatever the bias dtype
+
+    def __init__(self, mf, mb, fmt_f: int, fmt_b: int):
+        self.mf, self.mb, self.fmt_f, self.fmt_b = mf, mb, fmt_f, fmt_b
+
+    def _act(self, y, yT, s: int):
+        return (y, self.mf.scale_inv(s)), (yT, self.mf.scale_inv_snapshot()[s:s + 1])
+
+    def quantize(self, x2, g: int, want_t: bool, norm=None):
+        """`norm` = (rstd, gamma): x2 is un-normalised and RMSNorm is fused into the cast."""
+        mf, s = self.mf, 3 * g
+        if norm is None:
+            return self._act(*ops.cast_amax(x2, mf.scale(s), mf.amax(s), self.fmt_f, want_t=want_t), s)
+        return self._act(*ops.norm_cast(x2, norm[0], norm[1], mf.scale(s), mf.amax(s), self.fmt_f, want_t=want_t), s)
+
+    def swiglu(self, h, g: int, want_t: bool, bias):
+        mf, s = self.mf, 3 * g
+        return self._act(*ops.swiglu_cast(h, mf.scale(s), mf.amax(s), self.fmt_f, want_t=want_t, bias=bias), s)
+
+    def _grad(self, y, yT, cs, s: int):
+        si = self.mb.scale_inv(s)
+        return (y, si), (yT, si), cs
+
+    def quantize_grad(self, g2, g: int, want_y: bool, want_t: bool, colsum: bool = False):
+        """-> (row, col, partial column sums or None)"""
+        mb, s = self.mb, 2 * g
+        out = ops.cast_amax(g2, mb.scale(s), mb.amax(s), self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum)
+        return self._grad(out[0], out[1], out[2] if colsum else None, s)
+
+    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
+        mb, s = self.mb, 2 * g
+        return self._grad(*ops.dswiglu_cast(h, dact, mb.scale(s), mb.amax(s), self.fmt_b, want_y=want_y, want_t=want_t,
+                                            want_colsum=colsum, bias=bias), s)
+
+    def offer(self, handoff: DyHandoff, g: int, want_y: bool, want_t: bool) -> None:
+        if self.mb is not None:
+            handoff.offer(self.mb.scale(2 * g), self.mb.amax(2 * g), self.fmt_b, want_y, want_t)
+
+    def taken(self, fp8, g: int):
+        """(y, yT) that a DyHandoff producer `put`, as quantize_grad returns them."""
+        return self._grad(fp8[0], fp8[1], None, 2 * g)
+
+    def operands(self, a, b):
+        """One GEMM's operand tuple as ops.gemm_fp8 and _grouped_or_two take it."""
+        return a[0], b[0], a[1], b[1]
+
+    def gemm(self, a, b, bias):
+        return ops.gemm_fp8(a[0], b[0], a[1], b[1], self.fmt_f, self.fmt_f, bias=bias)
+
+    # -- weights: `flat` is what the micro-batch cache holds under (cache_key, g) --
+    def unflat(self, flat):
+        w8, w8t, siw = flat
+        return (w8, siw), (w8t, siw)
+
+    def quantize_weights(self, weights, ns, N: int, K: int, dev, g: int, want_t: bool):
+        mf, s = self.mf, 3 * g + 1
+        w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
+        w8t = torch.empty((K, N), dtype=torch.uint8, device=dev) if want_t else None
+        r = 0
         for w, n in zip(weights, ns):
-            self.parts.append((w, r, n))
-            w._mi_mx_sink = (self, r, n)
+            wb = w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
+            ops.cast_amax(wb.contiguous(), mf.scale(s), mf.amax(s), self.fmt_f,
+                          y=w8[r:r + n], yT=None if w8t is None else w8t[:, r:r + n], want_t=want_t)
             r += n
-        self.stamp = None
+        return w8, w8t, mf.scale_inv_snapshot()[s:s + 1]
 
-    def fresh(self) -> bool:
-        return self.stamp is not None and self.stamp == _part_versions(self.parts)
+    def new_sink(self, weights, ns, N: int, K: int, dev, g: int):  # None: an operand of this shape cannot take a sink
+        return WeightSink(weights, ns, N, K, dev, self.mf, 3 * g + 1) if N % 8 == 0 and K % 8 == 0 else None
 
-    def mark(self) -> None:  # called by the optimiser after it rewrote every part in this step
-        self.stamp = _part_versions(self.parts)
+    def refresh(self, dp, sink) -> None:
+        # the bytes in the sink were quantised with another scale generation (or never): the only bf16 source is the ranks'
+        # shards -- cast the local rows with the CURRENT scale and gather (what a replicated run's forward cast does)
+        dp.refresh_operand(sink, self.fmt_f)
 
-
-def _mx_sink_copies(spec: _GemmSpec, g: int, weights, ns, N: int, K: int, dev):
-    """(w8, sc, wt8, sct) from the optimiser-maintained sink of GEMM `g` if they are current, else None (the caller quantises).
-    A training pass creates the sink the first time round; the optimiser fills it at its next step.  Row-sharded weights
-    (distributed.ShardedFP8DP) always go through the sink: a stale one is refreshed from the ranks' shards."""
-    shard = sharded_handle(weights)
-    if shard is None and (spec.wcache is None or spec.fmt_fwd != 0 or not weight_sinks_enabled()):
-        return None
-    if shard is not None and (spec.wcache is None or spec.fmt_fwd != 0):
-        raise RuntimeError("row-sharded weights need the module's FP8 weight cache and an E4M3 forward format")
-    sink = spec.wcache.get(("mxsink", g))
-    stale = sink is None or len(sink.parts) != len(weights) or any(a is not b for (a, _, _), b in zip(sink.parts, weights))
-    if stale:
-        if not spec.training and shard is None:
-            return None
-        ok = (N % 32 == 0 and K % 32 == 0 and all(n % 32 == 0 for n in ns) and all(_weight_ok_for_sink(w, K) for w in weights))
-        if not ok:
-            if shard is not None:
-                raise RuntimeError("row-sharded weights of this shape cannot take an MXFP8 sink")
-            return None
-        sink = spec.wcache[("mxsink", g)] = MXWeightSink(weights, ns, N, K, dev)
-    if shard is not None:
-        shard.dp.wait_operand(sink)            # an FP8 all-gather issued after the optimiser step may still be in flight
-        if not sink.fresh():
-            shard.dp.refresh_mx_operand(sink, spec.fmt_fwd)
-    return (sink.w8, sink.sc, sink.wt8, sink.sct) if sink.fresh() else None
+    def sink_flat(self, sink, g: int):
+        return sink.w8, sink.w8t, self.mf.scale_inv_snapshot()[3 * g + 1:3 * g + 2]
 
 
-def _cast_weights(spec: _GemmSpec, g: int, weights, ns, N: int, K: int, dev, need_t: bool):
-    """FP8 copies (w8 [N,K], w8T [K,N]) of the concatenated weight parts of GEMM `g` under delayed scaling, plus the
-    scale_inv they were quantised with.  Honours the micro-batch cache of the spec (see _GemmSpec)."""
-    mf = spec.meta_fwd
-    ck = ("ds", g)
-    if spec.first_mb is False and spec.wcache is not None:
-        hit = spec.wcache.get(ck)
-        if hit is not None and (hit[1] is not None or not need_t):
-            return hit
+class _MXQ:
+    """MXFP8 block scaling: no state, every quantisation finds its own E8M0 scales."""
+    __slots__ = ("fmt_f", "fmt_b")
+    mx = True
+    cache_key, sink_key = "mx", "mxsink"
+    no_sink = "row-sharded weights of this shape cannot take an MXFP8 sink"
+    swiglu_adds_bias = False    # the quantising SwiGLU kernels have no bias form: the fc1 bias stays in the GEMM epilogue
+    colsum_dtypes = (torch.bfloat16, torch.float32)  # ... only for these bias dtypes, else g2.sum(0)
+
+    def __init__(self, fmt_f: int, fmt_b: int):
+        self.fmt_f, self.fmt_b = fmt_f, fmt_b
+
+    def quantize(self, x2, g: int, want_t: bool, norm=None):
+        if norm is None:
+            q = ops.mxfp8_quantize(x2, self.fmt_f, rowwise=True, colwise=want_t)
+        else:
+            q = ops.mxfp8_norm_quantize(x2, norm[0], norm[1], self.fmt_f, rowwise=True, colwise=want_t)
+        return q[:2], q[2:]
+
+    def swiglu(self, h, g: int, want_t: bool, bias):
+        assert bias is None
+        q = ops.mxfp8_swiglu_quantize(h, self.fmt_f, rowwise=True, colwise=want_t)
+        return q[:2], q[2:]
+
+    def quantize_grad(self, g2, g: int, want_y: bool, want_t: bool, colsum: bool = False):
+        q = ops.mxfp8_quantize(g2, self.fmt_b, rowwise=want_y, colwise=want_t, want_colsum=colsum)
+        return q[:2], q[2:4], q[4] if colsum else None
+
+    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
+        assert bias is None
+        q = ops.mxfp8_dswiglu_quantize(h, dact, self.fmt_b, rowwise=want_y, colwise=want_t, want_colsum=colsum)
+        return q[:2], q[2:4], q[4]
+
+    def offer(self, handoff: DyHandoff, g: int, want_y: bool, want_t: bool) -> None:
+        handoff.offer(None, None, self.fmt_b, want_y, want_t, mx=True)
+
+    def taken(self, fp8, g: int):
+        return fp8[:2], fp8[2:], None
+
+    def operands(self, a, b):
+        """One GEMM's operand tuple as ops.gemm_mxfp8 and _grouped_or_two take it."""
+        return a + b
+
+    def gemm(self, a, b, bias):
+        return ops.gemm_mxfp8(a[0], a[1], b[0], b[1], self.fmt_f, self.fmt_f, bias=bias)
+
+    def unflat(self, flat):
+        return flat[:2], flat[2:]
+
+    def quantize_weights(self, weights, ns, N: int, K: int, dev, g: int, want_t: bool):
+        """Every part is quantised straight into its row-block of the operand's buffers (mi_mxfp8_quantize_ex), no bf16
+        concatenation -- unless a part is not a multiple of 32 rows."""
+        fmt = self.fmt_f
+        ws_ = [(w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous() for w in weights]
+        if len(ws_) == 1:
+            return ops.mxfp8_quantize(ws_[0], fmt, rowwise=True, colwise=want_t)
+        if any(n % 32 for n in ns):
+            return ops.mxfp8_quantize(torch.cat(ws_, 0), fmt, rowwise=True, colwise=want_t)
+        w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
+        sc = torch.empty((K // 32, N), dtype=torch.uint8, device=dev)
+        wt8 = torch.empty((K, N), dtype=torch.uint8, device=dev) if want_t else None
+        sct = torch.empty((N // 32, K), dtype=torch.uint8, device=dev) if want_t else None
+        r = 0
+        for w, n in zip(ws_, ns):
+            ops.mxfp8_quantize(w, fmt, rowwise=True, colwise=want_t,
+                               out=(w8[r:r + n], sc[:, r:r + n], wt8[:, r:r + n] if want_t else None,
+                                    sct[r // 32:(r + n) // 32] if want_t else None))
+            r += n
+        return w8, sc, wt8, sct
+
+    def new_sink(self, weights, ns, N: int, K: int, dev, g: int):
+        return MXWeightSink(weights, ns, N, K, dev) if N % 32 == 0 and K % 32 == 0 and all(n % 32 == 0 for n in ns) else None
+
+    def refresh(self, dp, sink) -> None:
+        dp.refresh_mx_operand(sink, self.fmt_f)
+
+    def sink_flat(self, sink, g: int):
+        return sink.w8, sink.sc, sink.wt8, sink.sct
+
+
+def _weight_operand(spec: _GemmSpec, g: int, weights, ns, N: int, K: int, dev, need_t: bool):
+    """FP8 copies (row, col) of the concatenated weight parts of GEMM `g` (query | key | value): from the micro-batch cache of
+    the spec (see _GemmSpec), else from the sink the optimiser keeps current, else quantised now."""
+    q, wc = spec.q, spec.wcache
+    ck = (q.cache_key, g)
+    if spec.first_mb is False and wc is not None:
+        hit = wc.get(ck)
+        if hit is not None:
+            op = q.unflat(hit)
+            if op[1][0] is not None or not need_t:
+                return op
     # (no grad-mode test here: inside an autograd Function's forward grad mode is always off; fresh copies are the bytes a
     # cast would produce now in any mode)
+    keep = spec.first_mb is True and wc is not None
     shard = sharded_handle(weights)
-    if shard is not None and (spec.wcache is None or spec.fmt_fwd != 0):
+    if shard is not None and (wc is None or spec.fmt_fwd != 0):
         raise RuntimeError("row-sharded weights need the module's FP8 weight cache and an E4M3 forward format")
-    if spec.wcache is not None and spec.fmt_fwd == 0 and (weight_sinks_enabled() or shard is not None):
-        sink = spec.wcache.get(("sink", g))
-        stale = sink is None or sink.arena is not mf.arena or len(sink.parts) != len(weights) or any(a is not b for (a, _, _), b in zip(sink.parts, weights))
-        if stale and not spec.training and shard is None:
-            sink = None  # sinks are created by training passes only; an evaluation pass may USE a fresh one (same bytes)
-        elif stale:
-            if all(_weight_ok_for_sink(w, K) for w in weights) and N % 8 == 0 and K % 8 == 0:
-                sink = spec.wcache[("sink", g)] = WeightSink(weights, ns, N, K, dev, mf, 3 * g + 1)
-            else:
-                sink = None
+    flat = None
+    if wc is not None and spec.fmt_fwd == 0 and (weight_sinks_enabled() or shard is not None):
+        sink = wc.get((q.sink_key, g))
+        if sink is None or not sink.holds(weights, spec.meta_fwd):
+            # a training pass creates the sink the first time round and the optimiser fills it at its next step; an evaluation
+            # pass may USE a fresh one (same bytes).  Row-sharded weights always go through the sink.
+            sink = None
+            if (spec.training or shard is not None) and all(_weight_ok_for_sink(w, K) for w in weights):
+                sink = q.new_sink(weights, ns, N, K, dev, g)
+                if sink is not None:
+                    wc[(q.sink_key, g)] = sink
         if shard is not None:
             if sink is None:
-                raise RuntimeError("row-sharded weights of this shape cannot take an FP8 sink")
+                raise RuntimeError(q.no_sink)
             shard.dp.wait_operand(sink)        # an FP8 all-gather issued after the optimiser step may still be in flight
             if not sink.fresh():
-                # the bytes in the sink were quantised with another scale generation (or never): the only bf16 source is the
-                # ranks' shards -- cast the local rows with the CURRENT scale and gather (what a replicated run's forward cast does)
-                shard.dp.refresh_operand(sink, spec.fmt_fwd)
+                q.refresh(shard.dp, sink)
         if sink is not None and sink.fresh():
-            siw = mf.scale_inv_snapshot()[3 * g + 1:3 * g + 2]
-            if spec.first_mb is True:
-                spec.wcache[ck] = (sink.w8, sink.w8t, siw)
-            return sink.w8, sink.w8t, siw
-    keep = spec.first_mb is True and spec.wcache is not None
-    want_t = need_t or keep
-    w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
-    w8t = torch.empty((K, N), dtype=torch.uint8, device=dev) if want_t else None
-    r = 0
-    for w, n in zip(weights, ns):
-        wb = w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
-        ops.cast_amax(wb.contiguous(), mf.scale(3 * g + 1), mf.amax(3 * g + 1), spec.fmt_fwd,
-                      y=w8[r:r + n], yT=None if w8t is None else w8t[:, r:r + n], want_t=want_t)
-        r += n
-    siw = mf.scale_inv_snapshot()[3 * g + 1:3 * g + 2]  # the arena is rewritten at autocast exit; the snapshot is not
+            flat = q.sink_flat(sink, g)
+    if flat is None:
+        flat = q.quantize_weights(weights, ns, N, K, dev, g, need_t or keep)
     if keep:
-        spec.wcache[ck] = (w8, w8t, siw)
-    return w8, w8t, siw
-
-
-def _mx_quantize_weights(weights, ns, N: int, K: int, fmt: int, colwise: bool):
-    """MXFP8 copies of the concatenated weight parts of one GEMM operand (query | key | value): every part is quantised
-    straight into its row-block of the operand's buffers (mi_mxfp8_quantize_ex), no bf16 concatenation."""
-    ws_ = [(w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous() for w in weights]
-    if len(ws_) == 1:
-        return ops.mxfp8_quantize(ws_[0], fmt, rowwise=True, colwise=colwise)
-    if any(n % 32 for n in ns):
-        return ops.mxfp8_quantize(torch.cat(ws_, 0), fmt, rowwise=True, colwise=colwise)
-    dev = ws_[0].device
-    w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
-    sc = torch.empty((K // 32, N), dtype=torch.uint8, device=dev)
-    wt8 = torch.empty((K, N), dtype=torch.uint8, device=dev) if colwise else None
-    sct = torch.empty((N // 32, K), dtype=torch.uint8, device=dev) if colwise else None
-    r = 0
-    for w, n in zip(ws_, ns):
-        ops.mxfp8_quantize(w, fmt, rowwise=True, colwise=colwise,
-                           out=(w8[r:r + n], sc[:, r:r + n], wt8[:, r:r + n] if colwise else None,
-                                sct[r // 32:(r + n) // 32] if colwise else None))
-        r += n
-    return w8, sc, wt8, sct
+        wc[ck] = flat
+    return q.unflat(flat)
 
 
 class _AddStatsFn(torch.autograd.Function):
@@ -366,15 +496,16 @@ def _wgrad_out(weights, K: int) -> Optional[torch.Tensor]:
     return arena[off:end].view(-1, K)
 
 
-def _grouped_or_two(dgrad, wgrad, mx: bool, fmt_b: int, fmt_f: int, dw_out, need_dgrad: bool, need_wgrad: bool):
+def _grouped_or_two(q, grad, w_col, x_col, dw_out, need_dgrad: bool, need_wgrad: bool):
     """A Linear's two backward GEMMs on one grad_output: dX [M, K] = G8 [M, N] . W8T [K, N]^T and dW [N, K] = G8T [N, M] . X8T [K, M]^T;
-    `dgrad` / `wgrad` are their operands as ops.gemm_fp8 (with `mx`: ops.gemm_mxfp8) takes them.
+    `grad` = (row, col[, column sums]) of grad_output, `w_col` / `x_col` the column-wise copies the forward saved.
     ONE grouped persistent launch (ops.gemm_fp8_grouped / ops.gemm_mxfp8_grouped) where that is faster (ops.grouped_gemm_choice:
     measured once per shape in a single-process run, the count model under torch.distributed; env LLM_FP8_AMD_GROUPED_GEMM =
     auto | plan | autotune | off) -- one ramp, one exposed epilogue, and the short problem's tiles fill the idle part of the long
     one's last round -- else two launches.  Bitwise the same results either way; `dw_out` (the gradient-arena slot) stays the
     wgrad's output.  (Under torch.distributed the GEMMs run one workgroup per tile so that RCCL's kernels get CUs: no persistent
     grouping there.)"""
+    dgrad, wgrad, mx, fmt_b, fmt_f = q.operands(grad[0], w_col), q.operands(grad[1], x_col), q.mx, q.fmt_b, q.fmt_f
     if need_dgrad and need_wgrad and ops.default_gemm_algo() in (0, 4, 47) and os.environ.get("LLM_FP8_AMD_NO_GROUPED_GEMM") != "1":
         g8, wt8 = dgrad[0], dgrad[2 if mx else 1]
         M, N = g8.shape
@@ -396,16 +527,6 @@ def _grouped_or_two(dgrad, wgrad, mx: bool, fmt_b: int, fmt_f: int, dw_out, need
     return dx, dw
 
 
-def _dgrad_wgrad(g8, wt8, g8t, xt8, sig, si_w, si_x, fmt_b: int, fmt_f: int, dw_out, need_dgrad: bool, need_wgrad: bool):
-    """_grouped_or_two for the delayed-scaling recipes: one device scalar scale-inverse per operand."""
-    return _grouped_or_two((g8, wt8, sig, si_w), (g8t, xt8, sig, si_x), False, fmt_b, fmt_f, dw_out, need_dgrad, need_wgrad)
-
-
-def _dgrad_wgrad_mx(g8, gs, wt8, wts, gt8, gts, xt8, xts, fmt_b: int, fmt_f: int, dw_out, need_dgrad: bool, need_wgrad: bool):
-    """_grouped_or_two under MXFP8 block scaling: each operand with its block-major E8M0 scales."""
-    return _grouped_or_two((g8, gs, wt8, wts), (gt8, gts, xt8, xts), True, fmt_b, fmt_f, dw_out, need_dgrad, need_wgrad)
-
-
 def _skip_2d(dskip: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
     """Residual-branch gradient as a contiguous bf16 [tokens, features] matrix for mi_rmsnorm_bwd's `dres`."""
     if dskip is None:
@@ -414,67 +535,72 @@ def _skip_2d(dskip: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torc
     return d if (d.dtype == torch.bfloat16 and d.is_contiguous()) else d.to(torch.bfloat16).contiguous()
 
 
+def _quantize_input(ctx, spec: _GemmSpec, x2, ln_w, want_t: bool, need_dgrad: bool):
+    """The input of GEMM spec.g as an FP8 operand.  `ln_w` (with spec.eps): K9 -- x2 is the UN-normalised input and RMSNorm is
+    fused into its quantisation; ctx.norm keeps what the RMSNorm backward needs."""
+    ctx.norm = None
+    if ln_w is None:
+        return spec.q.quantize(x2, spec.g, want_t)
+    gam = (ln_w if ln_w.dtype == torch.bfloat16 else ln_w.to(torch.bfloat16)).contiguous()
+    # spec.rstd: the statistics came with the input (residual_add_stats)
+    rstd = spec.rstd if spec.rstd is not None else ops.rmsnorm_stats(x2, spec.eps)
+    if need_dgrad:
+        ctx.norm = (x2, rstd, gam, ln_w.dtype)
+    return spec.q.quantize(x2, spec.g, want_t, (rstd, gam))
+
+
+def _finish_dx(ctx, dx, dskip, colsums=None):
+    """The end of a GEMM Function's backward: RMSNorm backward of a fused norm with the residual-branch gradient added in the
+    kernel, the update trigger, dx in the input's shape and dtype, `dskip` added where no kernel took it.
+    `colsums`: the caller's bias gradients as (partial column sums, dtype) or None each -- ONE launch finishes them together
+    with the RMSNorm weight gradient.  Returns (dx, dln, finished colsums)."""
+    dln = None
+    if ctx.norm is not None and dx is not None:
+        xin, rstd, gam, ln_dtype = ctx.norm
+        ctx.norm = None
+        dx, dln = ops.rmsnorm_bwd(dx, xin, rstd, gam, dres=_skip_2d(dskip, dx), dgamma_dtype=ln_dtype, finish=colsums is None)
+        dskip = None
+        if colsums is not None:
+            dln = (dln, ln_dtype)
+    if colsums is not None:
+        pend = [t for t in (*colsums, dln) if t is not None]
+        if pend:
+            done = iter(ops.colsum_finish_multi(pend))
+            colsums = [None if t is None else next(done) for t in colsums]
+            dln = None if dln is None else next(done)
+    if ctx.spec.trigger_bwd_update:
+        # this GEMM belongs to the first FP8 module of the outermost autocast: its backward is the last
+        FP8GlobalStateManager.reduce_and_update_fp8_tensors(forward=False)
+    if dx is not None:
+        dx = dx.view(ctx.x_shape).to(ctx.x_dtype)
+    if dskip is not None:
+        dx = dskip if dx is None else dx + dskip
+    return dx, dln, colsums
+
+
 class _FP8LinearFn(torch.autograd.Function):
     """y[M, sum N_i] = x[M,K] . cat(W_i)[N,K]^T (+ bias), FP8 operands, bf16 result."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, bias: Optional[torch.Tensor], spec: _GemmSpec, ln_w: Optional[torch.Tensor],
                 *weights: torch.Tensor):
-        """`ln_w` (with spec.eps): K9 -- x is the UN-normalised input and RMSNorm is fused into its FP8 cast."""
+        """`ln_w`: see _quantize_input."""
         x2 = _as_bf16_2d(x)
         M, K = x2.shape
         if M % 8 or K % 16:
             raise RuntimeError(f"FP8 Linear needs tokens % 8 == 0 and in_features % 16 == 0, got {M} x {K}")
         ns = [w.shape[0] for w in weights]
         N = sum(ns)
-        dev = x2.device
+        q, g = spec.q, spec.g
         # (forward runs in no-grad mode; needs_input_grad is all-False when grad was disabled at apply time)
         need_dgrad = bool(ctx.needs_input_grad[0]) or bool(ctx.needs_input_grad[3])
         need_wgrad = any(ctx.needs_input_grad[4:])
-        bias_bf16 = None if bias is None else bias.to(torch.bfloat16).contiguous()
-        ctx.norm = None
-        if spec.recipe.mxfp8():
-            if ln_w is not None:
-                gam = (ln_w if ln_w.dtype == torch.bfloat16 else ln_w.to(torch.bfloat16)).contiguous()
-                rstd = spec.rstd if spec.rstd is not None else ops.rmsnorm_stats(x2, spec.eps)
-                x8, xs, xt8, xts = ops.mxfp8_norm_quantize(x2, rstd, gam, spec.fmt_fwd, rowwise=True, colwise=need_wgrad)
-                if need_dgrad:
-                    ctx.norm = (x2, rstd, gam, ln_w.dtype)
-            else:
-                x8, xs, xt8, xts = ops.mxfp8_quantize(x2, spec.fmt_fwd, rowwise=True, colwise=need_wgrad)
-            ck = ("mx", spec.g)
-            hit = spec.wcache.get(ck) if (spec.first_mb is False and spec.wcache is not None) else None
-            if hit is not None and (hit[2] is not None or not need_dgrad):
-                w8, ws, wt8, wts = hit
-            else:
-                kept = _mx_sink_copies(spec, spec.g, weights, ns, N, K, x2.device)
-                if kept is not None:
-                    w8, ws, wt8, wts = kept
-                else:
-                    w8, ws, wt8, wts = _mx_quantize_weights(weights, ns, N, K, spec.fmt_fwd, need_dgrad or spec.first_mb is True)
-                if spec.first_mb is True and spec.wcache is not None:
-                    spec.wcache[ck] = (w8, ws, wt8, wts)
-            y = ops.gemm_mxfp8(x8, xs, w8, ws, spec.fmt_fwd, spec.fmt_fwd, bias=bias_bf16)
-            ctx.saved_fp8 = (xt8, xts, wt8, wts, None)
-            if spec.dy_handoff is not None and bias is None and (need_wgrad or need_dgrad):
-                spec.dy_handoff.offer(None, None, spec.fmt_bwd, need_dgrad, need_wgrad, mx=True)
-        else:
-            mf, g = spec.meta_fwd, spec.g
-            if ln_w is not None:
-                gam = (ln_w if ln_w.dtype == torch.bfloat16 else ln_w.to(torch.bfloat16)).contiguous()
-                rstd = spec.rstd if spec.rstd is not None else ops.rmsnorm_stats(x2, spec.eps)
-                x8, x8t = ops.norm_cast(x2, rstd, gam, mf.scale(3 * g), mf.amax(3 * g), spec.fmt_fwd, want_t=need_wgrad)
-                if need_dgrad:
-                    ctx.norm = (x2, rstd, gam, ln_w.dtype)
-            else:
-                x8, x8t = ops.cast_amax(x2, mf.scale(3 * g), mf.amax(3 * g), spec.fmt_fwd, want_t=need_wgrad)
-            w8, w8t, siw = _cast_weights(spec, g, weights, ns, N, K, dev, need_dgrad)
-            y = ops.gemm_fp8(x8, w8, mf.scale_inv(3 * g), siw, spec.fmt_fwd, spec.fmt_fwd, bias=bias_bf16)
-            # scale_inv as of quantisation time: the arena is updated at autocast exit, before backward
-            sinv = (mf.scale_inv_snapshot()[3 * g:3 * g + 1], siw) if (need_wgrad or need_dgrad) else None
-            ctx.saved_fp8 = (x8t, None, w8t, None, sinv)
-            if spec.dy_handoff is not None and bias is None and spec.meta_bwd is not None and (need_wgrad or need_dgrad):
-                spec.dy_handoff.offer(spec.meta_bwd.scale(2 * g), spec.meta_bwd.amax(2 * g), spec.fmt_bwd, need_dgrad, need_wgrad)
+        x8 = _quantize_input(ctx, spec, x2, ln_w, need_wgrad, need_dgrad)
+        w8 = _weight_operand(spec, g, weights, ns, N, K, x2.device, need_dgrad)
+        y = q.gemm(x8[0], w8[0], None if bias is None else bias.to(torch.bfloat16).contiguous())
+        ctx.saved_fp8 = (x8[1], w8[1])
+        if spec.dy_handoff is not None and bias is None and (need_wgrad or need_dgrad):
+            q.offer(spec.dy_handoff, g, need_dgrad, need_wgrad)
         ctx.spec, ctx.ns, ctx.x_shape, ctx.x_dtype = spec, ns, x.shape, x.dtype
         ctx.w_dtypes = [w.dtype for w in weights]
         ctx.w_refs = weights if need_wgrad else None  # the Parameters themselves (not saved tensors): for _wgrad_out
@@ -488,52 +614,23 @@ class _FP8LinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy: torch.Tensor, dskip: Optional[torch.Tensor] = None):
         spec = ctx.spec
+        q, g = spec.q, spec.g
         g2 = _as_bf16_2d(dy)
-        M, N = g2.shape
-        xt8, xts, wt8, wts, sinv = ctx.saved_fp8
+        x_col, w_col = ctx.saved_fp8
         ctx.saved_fp8 = None
-        dx = dw = db_fused = None
-        if spec.recipe.mxfp8():
-            if spec.dy_handoff is not None and spec.dy_handoff.fp8 is not None:
-                g8, gs, gt8, gts = spec.dy_handoff.take(dy)  # already quantised by the op that produced it (dy is a placeholder)
-            elif ctx.has_bias and ctx.bias_dtype in (torch.bfloat16, torch.float32):  # the bias gradient rides on the quantisation
-                g8, gs, gt8, gts, cs = ops.mxfp8_quantize(g2, spec.fmt_bwd, rowwise=ctx.need_dgrad, colwise=ctx.need_wgrad,
-                                                          want_colsum=True)
-                db_fused = ops.colsum_finish(cs, ctx.bias_dtype)
-            else:
-                g8, gs, gt8, gts = ops.mxfp8_quantize(g2, spec.fmt_bwd, rowwise=ctx.need_dgrad, colwise=ctx.need_wgrad)
-            dx, dw = _dgrad_wgrad_mx(g8, gs, wt8, wts, gt8, gts, xt8, xts, spec.fmt_bwd, spec.fmt_fwd,
-                                     _wgrad_out(ctx.w_refs, xt8.shape[0]) if ctx.need_wgrad else None, ctx.need_dgrad, ctx.need_wgrad)
-        else:
-            mb, g = spec.meta_bwd, spec.g
-            if spec.dy_handoff is not None and spec.dy_handoff.fp8 is not None:
-                g8, g8t = spec.dy_handoff.take(dy)  # already quantised by the op that produced it (dy is a placeholder)
-            elif ctx.has_bias:  # the bias gradient rides on the cast of dy
-                g8, g8t, cs = ops.cast_amax(g2, mb.scale(2 * g), mb.amax(2 * g), spec.fmt_bwd,
-                                            want_y=ctx.need_dgrad, want_t=ctx.need_wgrad, want_colsum=True)
-                db_fused = ops.colsum_finish(cs, ctx.bias_dtype)
-            else:
-                g8, g8t = ops.cast_amax(g2, mb.scale(2 * g), mb.amax(2 * g), spec.fmt_bwd,
-                                        want_y=ctx.need_dgrad, want_t=ctx.need_wgrad)
-            sig = mb.scale_inv(2 * g)
-            dx, dw = _dgrad_wgrad(g8, wt8, g8t, xt8, sig, sinv[1], sinv[0], spec.fmt_bwd, spec.fmt_fwd,
-                                  _wgrad_out(ctx.w_refs, xt8.shape[0]) if ctx.need_wgrad else None, ctx.need_dgrad, ctx.need_wgrad)
         db = None
-        if ctx.has_bias:
-            db = db_fused if db_fused is not None else g2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
-        dln = None
-        if ctx.norm is not None and dx is not None:
-            xin, rstd, gam, ln_dtype = ctx.norm
-            ctx.norm = None
-            dx, dln = ops.rmsnorm_bwd(dx, xin, rstd, gam, dres=_skip_2d(dskip, dx), dgamma_dtype=ln_dtype)
-            dskip = None
-        if spec.trigger_bwd_update:
-            # this GEMM belongs to the first FP8 module of the outermost autocast: its backward is the last
-            FP8GlobalStateManager.reduce_and_update_fp8_tensors(forward=False)
-        if dx is not None:
-            dx = dx.view(ctx.x_shape).to(ctx.x_dtype)
-        if dskip is not None:
-            dx = dskip if dx is None else dx + dskip
+        if spec.dy_handoff is not None and spec.dy_handoff.fp8 is not None:
+            grad = q.taken(spec.dy_handoff.take(dy), g)  # already quantised by the op that produced it (dy is a placeholder)
+        elif ctx.has_bias and (q.colsum_dtypes is None or ctx.bias_dtype in q.colsum_dtypes):  # the bias gradient rides on it
+            grad = q.quantize_grad(g2, g, ctx.need_dgrad, ctx.need_wgrad, colsum=True)
+            db = ops.colsum_finish(grad[2], ctx.bias_dtype)
+        else:
+            grad = q.quantize_grad(g2, g, ctx.need_dgrad, ctx.need_wgrad)
+        dx, dw = _grouped_or_two(q, grad, w_col, x_col, _wgrad_out(ctx.w_refs, x_col[0].shape[0]) if ctx.need_wgrad else None,
+                                 ctx.need_dgrad, ctx.need_wgrad)
+        if ctx.has_bias and db is None:
+            db = g2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
+        dx, dln, _ = _finish_dx(ctx, dx, dskip)
         dws: List[Optional[torch.Tensor]] = [None] * len(ctx.ns)
         if dw is not None:
             parts = torch.split(dw, ctx.ns, dim=0)
@@ -542,9 +639,9 @@ class _FP8LinearFn(torch.autograd.Function):
 
 
 class _FP8SwiGLUMLPFn(torch.autograd.Function):
-    """fc1 (FP8) -> SwiGLU fused with the FP8 cast of fc2's input -> fc2 (FP8), delayed scaling: TE's LayerNormMLP
-    structure (te_llama.py:58-63).  The bf16 activation is never materialised; backward fuses dSwiGLU with the cast of
-    fc1's grad_output and returns the fc1 bias gradient from the same pass."""
+    """fc1 (FP8) -> SwiGLU fused with the FP8 quantisation of fc2's input -> fc2 (FP8): TE's LayerNormMLP structure
+    (te_llama.py:58-63).  The bf16 activation is never materialised; backward fuses dSwiGLU with the quantisation of fc1's
+    grad_output and returns the fc1 bias gradient from the same pass."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, spec: _GemmSpec, ln_w=None):
@@ -552,162 +649,53 @@ class _FP8SwiGLUMLPFn(torch.autograd.Function):
         M, K = x2.shape
         if M % 8 or K % 16:
             raise RuntimeError(f"FP8 LayerNormMLP needs tokens % 8 == 0 and hidden % 16 == 0, got {M} x {K}")
-        mf, fmt = spec.meta_fwd, spec.fmt_fwd
+        q, dev = spec.q, x2.device
         need_dgrad = bool(ctx.needs_input_grad[0]) or bool(ctx.needs_input_grad[6])
         need_w = bool(ctx.needs_input_grad[1]) or bool(ctx.needs_input_grad[3])
         bwd = need_dgrad or need_w
-        ctx.norm = None
+        x8 = _quantize_input(ctx, spec, x2, ln_w, need_w, need_dgrad)
+        w1_8 = _weight_operand(spec, 0, (w1,), [w1.shape[0]], w1.shape[0], K, dev, bwd)
+        # fc1: where the SwiGLU kernels take a bias the GEMM leaves it out and they add it (fp32) to the gate / up values they
+        # unpack anyway; else it stays in the GEMM's epilogue
+        b1_bf = None if b1 is None else b1.detach().to(torch.bfloat16).contiguous()
+        fuse_b1 = b1_bf is not None and q.swiglu_adds_bias and _FUSE_MLP_BIAS and (b1_bf.data_ptr() % 16 == 0)
+        h = q.gemm(x8[0], w1_8[0], None if fuse_b1 else b1_bf)
+        a8 = q.swiglu(h, 1, need_w, b1_bf if fuse_b1 else None)
+        ctx.b1_fused = b1_bf if fuse_b1 else None
+        w2_8 = _weight_operand(spec, 1, (w2,), [w2.shape[0]], w2.shape[0], w2.shape[1], dev, bwd)
+        # fc2: with defer_bias the caller adds the bias in its residual add (LayerNormMLP.forward hands it over)
+        y = q.gemm(a8[0], w2_8[0], None if (b2 is None or spec.defer_bias) else b2.to(torch.bfloat16).contiguous())
+        ctx.saved_fp8 = (x8[1], w1_8[1], a8[1], w2_8[1], h if bwd else None)
         ctx.spec, ctx.x_shape, ctx.x_dtype = spec, x.shape, x.dtype
         ctx.dtypes = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype)
         ctx.need_dgrad, ctx.need_w = need_dgrad, need_w
         ctx.w_refs = (w1, w2) if need_w else None  # the Parameters themselves: for _wgrad_out
-        if spec.recipe.mxfp8():
-            return _FP8SwiGLUMLPFn._forward_mx(ctx, x, x2, w1, b1, w2, b2, spec, ln_w, need_dgrad, need_w, bwd)
-        if ln_w is not None:  # K9: x is the un-normalised input
-            gam = (ln_w if ln_w.dtype == torch.bfloat16 else ln_w.to(torch.bfloat16)).contiguous()
-            rstd = spec.rstd if spec.rstd is not None else ops.rmsnorm_stats(x2, spec.eps)
-            x8, x8t = ops.norm_cast(x2, rstd, gam, mf.scale(0), mf.amax(0), fmt, want_t=need_w)
-            if need_dgrad:
-                ctx.norm = (x2, rstd, gam, ln_w.dtype)
-        else:
-            x8, x8t = ops.cast_amax(x2, mf.scale(0), mf.amax(0), fmt, want_t=need_w)
-        dev = x2.device
-        w1_8, w1_8t, si1 = _cast_weights(spec, 0, (w1,), [w1.shape[0]], w1.shape[0], K, dev, bwd)
-        # fc1: the GEMM leaves the bias out, the SwiGLU kernels add it (fp32) to the gate / up values they unpack anyway
-        b1_bf = None if b1 is None else b1.detach().to(torch.bfloat16).contiguous()
-        fuse_b1 = b1_bf is not None and _FUSE_MLP_BIAS and (b1_bf.data_ptr() % 16 == 0)
-        h = ops.gemm_fp8(x8, w1_8, mf.scale_inv(0), si1, fmt, fmt, bias=None if (b1_bf is None or fuse_b1) else b1_bf)
-        a8, a8t = ops.swiglu_cast(h, mf.scale(3), mf.amax(3), fmt, want_t=need_w, bias=b1_bf if fuse_b1 else None)
-        ctx.b1_fused = b1_bf if fuse_b1 else None
-        w2_8, w2_8t, si2 = _cast_weights(spec, 1, (w2,), [w2.shape[0]], w2.shape[0], w2.shape[1], dev, bwd)
-        # fc2: with defer_bias the caller adds the bias in its residual add (LayerNormMLP.forward hands it over)
-        y = ops.gemm_fp8(a8, w2_8, mf.scale_inv(3), si2, fmt, fmt,
-                         bias=None if (b2 is None or spec.defer_bias) else b2.to(torch.bfloat16).contiguous())
-        snap = mf.scale_inv_snapshot() if bwd else None
-        sinv = (snap[0:1], si1, snap[3:4], si2) if bwd else None  # scale_inv of x, w1, act, w2 as of quantisation time
-        ctx.saved_fp8 = (x8t, w1_8t, a8t, w2_8t, h if bwd else None, sinv)
-        ctx.spec, ctx.x_shape, ctx.x_dtype = spec, x.shape, x.dtype
-        ctx.dtypes = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype)
-        ctx.need_dgrad, ctx.need_w = need_dgrad, need_w
         if spec.with_skip:
             ctx.set_materialize_grads(False)
             return y.view(*x.shape[:-1], w2.shape[0]), x
         return y.view(*x.shape[:-1], w2.shape[0])
-
-    @staticmethod
-    def _mx_weights(spec, g, w, need_t):
-        ck = ("mx", g)
-        hit = spec.wcache.get(ck) if (spec.first_mb is False and spec.wcache is not None) else None
-        if hit is not None and (hit[2] is not None or not need_t):
-            return hit
-        q = _mx_sink_copies(spec, g, [w], [w.shape[0]], w.shape[0], w.shape[1], w.device)
-        if q is None:
-            wb = (w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous()
-            q = ops.mxfp8_quantize(wb, spec.fmt_fwd, rowwise=True, colwise=need_t or spec.first_mb is True)
-        if spec.first_mb is True and spec.wcache is not None:
-            spec.wcache[ck] = q
-        return q
-
-    @staticmethod
-    def _forward_mx(ctx, x, x2, w1, b1, w2, b2, spec, ln_w, need_dgrad, need_w, bwd):
-        fmt = spec.fmt_fwd
-        if ln_w is not None:
-            gam = (ln_w if ln_w.dtype == torch.bfloat16 else ln_w.to(torch.bfloat16)).contiguous()
-            rstd = spec.rstd if spec.rstd is not None else ops.rmsnorm_stats(x2, spec.eps)
-            x8, xs, xt8, xts = ops.mxfp8_norm_quantize(x2, rstd, gam, fmt, rowwise=True, colwise=need_w)
-            if need_dgrad:
-                ctx.norm = (x2, rstd, gam, ln_w.dtype)
-        else:
-            x8, xs, xt8, xts = ops.mxfp8_quantize(x2, fmt, rowwise=True, colwise=need_w)
-        w1_8, w1s, w1t8, w1ts = _FP8SwiGLUMLPFn._mx_weights(spec, 0, w1, bwd)
-        h = ops.gemm_mxfp8(x8, xs, w1_8, w1s, fmt, fmt, bias=None if b1 is None else b1.to(torch.bfloat16).contiguous())
-        a8, as_, at8, ats = ops.mxfp8_swiglu_quantize(h, fmt, rowwise=True, colwise=need_w)
-        w2_8, w2s, w2t8, w2ts = _FP8SwiGLUMLPFn._mx_weights(spec, 1, w2, bwd)
-        y = ops.gemm_mxfp8(a8, as_, w2_8, w2s, fmt, fmt, bias=None if (b2 is None or spec.defer_bias) else b2.to(torch.bfloat16).contiguous())
-        ctx.saved_fp8 = ((xt8, xts), (w1t8, w1ts), (at8, ats), (w2t8, w2ts), h if bwd else None, None)
-        if spec.with_skip:
-            ctx.set_materialize_grads(False)
-            return y.view(*x.shape[:-1], w2.shape[0]), x
-        return y.view(*x.shape[:-1], w2.shape[0])
-
-    @staticmethod
-    def _backward_mx(ctx, dy):
-        spec = ctx.spec
-        fmt_f, fmt_b = spec.fmt_fwd, spec.fmt_bwd
-        (xt8, xts), (w1t8, w1ts), (at8, ats), (w2t8, w2ts), h, _ = ctx.saved_fp8
-        ctx.saved_fp8 = None
-        g2 = _as_bf16_2d(dy)
-        if ctx.dtypes[3] is not None:  # fc2 bias gradient rides on the quantisation of dy
-            g8, gs, gt8, gts, cs2 = ops.mxfp8_quantize(g2, fmt_b, rowwise=True, colwise=ctx.need_w, want_colsum=True)
-            db2 = (cs2, ctx.dtypes[3])  # partial sums: finished with the layer's other column sums in _finish_backward
-        else:
-            g8, gs, gt8, gts = ops.mxfp8_quantize(g2, fmt_b, rowwise=True, colwise=ctx.need_w)
-            db2 = None
-        dact, dw2 = _dgrad_wgrad_mx(g8, gs, w2t8, w2ts, gt8, gts, at8, ats, fmt_b, fmt_f,
-                                    _wgrad_out(ctx.w_refs[1:], at8.shape[0]) if ctx.need_w else None, True, ctx.need_w)
-        want_b1 = ctx.dtypes[1] is not None
-        dh8, dhs, dht8, dhts, colsum = ops.mxfp8_dswiglu_quantize(h, dact, fmt_b, rowwise=ctx.need_dgrad, colwise=ctx.need_w,
-                                                                  want_colsum=want_b1)
-        db1 = (colsum, ctx.dtypes[1]) if want_b1 else None
-        dx, dw1 = _dgrad_wgrad_mx(dh8, dhs, w1t8, w1ts, dht8, dhts, xt8, xts, fmt_b, fmt_f,
-                                  _wgrad_out(ctx.w_refs[:1], xt8.shape[0]) if ctx.need_w else None, ctx.need_dgrad, ctx.need_w)
-        return dx, dw1, db1, dw2, db2
 
     @staticmethod
     def backward(ctx, dy, dskip=None):
-        spec = ctx.spec
-        if spec.recipe.mxfp8():
-            dx, dw1, db1, dw2, db2 = _FP8SwiGLUMLPFn._backward_mx(ctx, dy)
-            return _FP8SwiGLUMLPFn._finish_backward(ctx, dx, dw1, db1, dw2, db2, dskip)
-        mb, fmt_f, fmt_b = spec.meta_bwd, spec.fmt_fwd, spec.fmt_bwd
-        x8t, w1_8t, a8t, w2_8t, h, sinv = ctx.saved_fp8
+        q = ctx.spec.q
+        x_col, w1_col, a_col, w2_col, h = ctx.saved_fp8
         ctx.saved_fp8 = None
-        g2 = _as_bf16_2d(dy)
-        # fc2 backward (GEMM index 1: bwd slot 2)
-        if ctx.dtypes[3] is not None:  # fc2 bias gradient rides on the cast of dy
-            g8, g8t, cs2 = ops.cast_amax(g2, mb.scale(2), mb.amax(2), fmt_b, want_t=ctx.need_w, want_colsum=True)
-            db2 = (cs2, ctx.dtypes[3])  # partial sums: finished with the layer's other column sums in _finish_backward
-        else:
-            g8, g8t = ops.cast_amax(g2, mb.scale(2), mb.amax(2), fmt_b, want_t=ctx.need_w)
-            db2 = None
-        dact, dw2 = _dgrad_wgrad(g8, w2_8t, g8t, a8t, mb.scale_inv(2), sinv[3], sinv[2], fmt_b, fmt_f,
-                                 _wgrad_out(ctx.w_refs[1:], a8t.shape[0]) if ctx.need_w else None, True, ctx.need_w)
-        # dSwiGLU + cast of fc1's grad_output (GEMM index 0: bwd slot 0) + fc1 bias gradient
-        want_b1 = ctx.dtypes[1] is not None
-        dh8, dh8t, colsum = ops.dswiglu_cast(h, dact, mb.scale(0), mb.amax(0), fmt_b, want_y=ctx.need_dgrad,
-                                             want_t=ctx.need_w, want_colsum=want_b1, bias=getattr(ctx, "b1_fused", None))
-        db1 = (colsum, ctx.dtypes[1]) if want_b1 else None
-        dx, dw1 = _dgrad_wgrad(dh8, w1_8t, dh8t, x8t, mb.scale_inv(0), sinv[1], sinv[0], fmt_b, fmt_f,
-                                _wgrad_out(ctx.w_refs[:1], x8t.shape[0]) if ctx.need_w else None, ctx.need_dgrad, ctx.need_w)
-        return _FP8SwiGLUMLPFn._finish_backward(ctx, dx, dw1, db1, dw2, db2, dskip)
-
-    @staticmethod
-    def _finish_backward(ctx, dx, dw1, db1, dw2, db2, dskip=None):
-        """db1 / db2 arrive as (partial column sums, dtype): one launch finishes them together with the RMSNorm weight gradient."""
-        spec = ctx.spec
-        dln = None
-        if ctx.norm is not None and dx is not None:
-            xin, rstd, gam, ln_dtype = ctx.norm
-            ctx.norm = None
-            dx, dln = ops.rmsnorm_bwd(dx, xin, rstd, gam, dres=_skip_2d(dskip, dx), dgamma_dtype=ln_dtype, finish=False)
-            dln = (dln, ln_dtype)
-            dskip = None
-        pend = [t for t in (db1, db2, dln) if t is not None]
-        if pend:
-            done = iter(ops.colsum_finish_multi(pend))
-            db1 = next(done) if db1 is not None else None
-            db2 = next(done) if db2 is not None else None
-            dln = next(done) if dln is not None else None
-        if spec.trigger_bwd_update:
-            FP8GlobalStateManager.reduce_and_update_fp8_tensors(forward=False)
-        if dx is not None:
-            dx = dx.view(ctx.x_shape).to(ctx.x_dtype)
-        if dskip is not None:
-            dx = dskip if dx is None else dx + dskip
-        if dw1 is not None and dw1.dtype != ctx.dtypes[0]:
-            dw1 = dw1.to(ctx.dtypes[0])
-        if dw2 is not None and dw2.dtype != ctx.dtypes[2]:
-            dw2 = dw2.to(ctx.dtypes[2])
+        dt_w1, dt_b1, dt_w2, dt_b2 = ctx.dtypes
+        # fc2 backward (GEMM 1); its bias gradient rides on the quantisation of dy
+        grad = q.quantize_grad(_as_bf16_2d(dy), 1, True, ctx.need_w, colsum=dt_b2 is not None)
+        db2 = None if dt_b2 is None else (grad[2], dt_b2)  # partial sums: finished with the layer's other column sums in _finish_dx
+        dact, dw2 = _grouped_or_two(q, grad, w2_col, a_col, _wgrad_out(ctx.w_refs[1:], a_col[0].shape[0]) if ctx.need_w else None,
+                                    True, ctx.need_w)
+        # dSwiGLU + quantisation of fc1's grad_output (GEMM 0) + fc1 bias gradient
+        grad = q.dswiglu(h, dact, 0, ctx.need_dgrad, ctx.need_w, dt_b1 is not None, ctx.b1_fused)
+        db1 = None if dt_b1 is None else (grad[2], dt_b1)
+        dx, dw1 = _grouped_or_two(q, grad, w1_col, x_col, _wgrad_out(ctx.w_refs[:1], x_col[0].shape[0]) if ctx.need_w else None,
+                                  ctx.need_dgrad, ctx.need_w)
+        dx, dln, (db1, db2) = _finish_dx(ctx, dx, dskip, (db1, db2))
+        if dw1 is not None and dw1.dtype != dt_w1:
+            dw1 = dw1.to(dt_w1)
+        if dw2 is not None and dw2.dtype != dt_w2:
+            dw2 = dw2.to(dt_w2)
         return dx, dw1, db1, dw2, db2, None, dln
 
 
@@ -727,6 +715,19 @@ class _FP8Module(torch.nn.Module):
         # used when forward() is called without `is_first_microbatch` (the decoder layer does not thread the flag through):
         # the training harness sets it per micro-batch of a gradient-accumulation window (train.train_step)
         self.default_is_first_microbatch = None
+
+    def _spec(self, st, is_first_microbatch, g: int = 0, eps: float = 1e-5, **kw) -> _GemmSpec:
+        """The spec of this module's GEMM `g` from what _prepare returned.  GEMM 0's backward is the module's last FP8 op: it
+        carries the update trigger."""
+        recipe, mf, mb, first = st
+        if is_first_microbatch is None:
+            is_first_microbatch = self.default_is_first_microbatch
+        return _GemmSpec(recipe, mf, mb, g, first and g == 0, self.training, eps, self._wcache, is_first_microbatch, **kw)
+
+    def _norm(self, x):  # (the modules with a norm in front)
+        if self.normalization == "RMSNorm":
+            return _rmsnorm(x, self.layer_norm_weight, self.eps, self.zero_centered_gamma)
+        return _layernorm(x, self.layer_norm_weight, self.layer_norm_bias, self.eps, self.zero_centered_gamma)
 
     def _prepare(self, device) -> Optional[Tuple[Recipe, Optional[ModuleMeta], Optional[ModuleMeta], bool]]:
         """Called at the top of forward.  None -> run the plain bf16 path."""
@@ -827,14 +828,11 @@ class Linear(_FP8Module):
         self.use_bias = bias
 
     def forward(self, inp: torch.Tensor, is_first_microbatch=None) -> torch.Tensor:
-        if is_first_microbatch is None:
-            is_first_microbatch = self.default_is_first_microbatch
         st = self._prepare(inp.device)
         if st is None:
             if getattr(self, "_pending_norm", None) is not None:
                 raise RuntimeError("Linear: a deferred RMSNorm is pending but FP8 is off for this forward")
             return F.linear(inp, _master(self.weight).to(inp.dtype), None if self.bias is None else self.bias.to(inp.dtype))
-        recipe, mf, mb, first = st
         # `offer_dy_handoff` (set on the lm_head by train.prepare_model): the output carries a DyHandoff through which the op
         # that consumes it directly (loss.causal_lm_loss) can deliver this layer's grad_output already quantised
         handoff = DyHandoff() if (getattr(self, "offer_dy_handoff", False) and self.training and torch.is_grad_enabled()
@@ -848,9 +846,8 @@ class Linear(_FP8Module):
             if inp.data_ptr() != ptr or tuple(inp.shape) != shape:
                 raise RuntimeError("Linear: a deferred RMSNorm is pending for another tensor than the one this forward received")
             rstd = _usable_rstd(rs, inp, eps)
-        spec = _GemmSpec(recipe, mf, mb, 0, first, self.training, eps, wcache=self._wcache, first_mb=is_first_microbatch,
-                         rstd=rstd, dy_handoff=handoff)
-        y = _FP8LinearFn.apply(inp, self.bias, spec, ln_w, self.weight)
+        y = _FP8LinearFn.apply(inp, self.bias, self._spec(st, is_first_microbatch, eps=eps, rstd=rstd, dy_handoff=handoff), ln_w,
+                               self.weight)
         if handoff is not None and handoff.offered():
             y._mi_dy_handoff = handoff
         return y
@@ -909,33 +906,22 @@ class LayerNormLinear(_FP8Module):
         bs = [getattr(self, n) for n in self.bias_names]
         return bs[0] if len(bs) == 1 else torch.cat(bs, 0)
 
-    def _norm(self, x):
-        if self.normalization == "RMSNorm":
-            return _rmsnorm(x, self.layer_norm_weight, self.eps, self.zero_centered_gamma)
-        return _layernorm(x, self.layer_norm_weight, self.layer_norm_bias, self.eps, self.zero_centered_gamma)
-
     def forward(self, inp: torch.Tensor, is_first_microbatch=None, _with_skip: bool = False, _rstd=None, _dy_handoff=None):
         """`_with_skip` (extension used by MultiheadAttention / the decoder layer): returns (out, skip) where `skip` carries
         `inp` for the residual add, its gradient fused into the RMSNorm backward when the fused-norm path is active.
         `_rstd`: (rstd, eps) of `inp` from residual_add_stats, used instead of a statistics pass when eps matches."""
-        if is_first_microbatch is None:
-            is_first_microbatch = self.default_is_first_microbatch
         st = self._prepare(inp.device)
         ws, b = self._weights(), self._bias()
         if st is not None and _can_fuse_norm(self, st[0], inp) and not self.return_layernorm_output:
-            recipe, mf, mb, first = st
-            return _FP8LinearFn.apply(inp, b, _GemmSpec(recipe, mf, mb, 0, first, self.training, self.eps, self._wcache,
-                                                        is_first_microbatch, with_skip=_with_skip, rstd=_usable_rstd(_rstd, inp, self.eps),
-                                                        dy_handoff=_dy_handoff),
+            return _FP8LinearFn.apply(inp, b, self._spec(st, is_first_microbatch, eps=self.eps, with_skip=_with_skip,
+                                                         rstd=_usable_rstd(_rstd, inp, self.eps), dy_handoff=_dy_handoff),
                                       self.layer_norm_weight, *ws)
         ln = self._norm(inp)
         if st is None:
             w = _master(ws[0]) if len(ws) == 1 else torch.cat([_master(w_) for w_ in ws], 0)
             out = F.linear(ln, w.to(ln.dtype), None if b is None else b.to(ln.dtype))
         else:
-            recipe, mf, mb, first = st
-            out = _FP8LinearFn.apply(ln, b, _GemmSpec(recipe, mf, mb, 0, first, self.training, wcache=self._wcache,
-                                                      first_mb=is_first_microbatch), None, *ws)
+            out = _FP8LinearFn.apply(ln, b, self._spec(st, is_first_microbatch), None, *ws)
         if _with_skip:  # unfused route: the residual is the input itself (autograd adds its gradient)
             return out, inp
         return (out, ln) if self.return_layernorm_output else out
@@ -997,26 +983,18 @@ class LayerNormMLP(_FP8Module):
         self.fc2_bias = torch.nn.Parameter(torch.zeros(hidden_size, dtype=dt, device=device)) if bias else None
         self.fused_swiglu = True  # K10: SwiGLU fused with the FP8 cast (delayed scaling); False -> two Linears + torch ops
 
-    def _norm(self, x):
-        if self.normalization == "RMSNorm":
-            return _rmsnorm(x, self.layer_norm_weight, self.eps, self.zero_centered_gamma)
-        return _layernorm(x, self.layer_norm_weight, self.layer_norm_bias, self.eps, self.zero_centered_gamma)
-
     def forward(self, inp: torch.Tensor, is_first_microbatch=None, _with_skip: bool = False, _rstd=None, _defer_bias: bool = False):
         """`_defer_bias` (extension, with `_with_skip`): returns (out, skip, bias) where `out` lacks the fc2 bias and `bias` is the
         tensor the caller must add (residual_add_stats(skip, out, eps, bias=bias)), or None when nothing was deferred."""
-        if is_first_microbatch is None:
-            is_first_microbatch = self.default_is_first_microbatch
         st = self._prepare(inp.device)
         if (st is not None and self.activation == "swiglu" and self.fused_swiglu and _can_fuse_norm(self, st[0], inp)):
-            recipe, mf, mb, first = st  # K9 + K10: norm -> cast, fc1, SwiGLU -> cast, fc2 in one autograd node
+            # K9 + K10: norm -> cast, fc1, SwiGLU -> cast, fc2 in one autograd node
             # (the residual add that takes the deferred fc2 bias is recipe-independent: MXFP8 defers too; the fc1 bias stays in the
             # MXFP8 GEMM's epilogue, its quantising SwiGLU kernels have no bias form)
             defer = bool(_defer_bias and _with_skip and _FUSE_MLP_BIAS and self.fc2_bias is not None)
             res = _FP8SwiGLUMLPFn.apply(inp, self.fc1_weight, self.fc1_bias, self.fc2_weight, self.fc2_bias,
-                                        _GemmSpec(recipe, mf, mb, 0, first, self.training, self.eps, self._wcache,
-                                                  is_first_microbatch, with_skip=_with_skip, rstd=_usable_rstd(_rstd, inp, self.eps),
-                                                  defer_bias=defer),
+                                        self._spec(st, is_first_microbatch, eps=self.eps, with_skip=_with_skip,
+                                                   rstd=_usable_rstd(_rstd, inp, self.eps), defer_bias=defer),
                                         self.layer_norm_weight)
             if _defer_bias and _with_skip:
                 return res[0], res[1], (self.fc2_bias if defer else None)
@@ -1032,14 +1010,9 @@ class LayerNormMLP(_FP8Module):
             h = F.linear(ln, _master(self.fc1_weight).to(ln.dtype), None if self.fc1_bias is None else self.fc1_bias.to(ln.dtype))
             return F.linear(self.act_fn(h), _master(self.fc2_weight).to(ln.dtype),
                             None if self.fc2_bias is None else self.fc2_bias.to(ln.dtype))
-        recipe, mf, mb, first = st
+        recipe = st[0]
         if self.activation == "swiglu" and self.fused_swiglu and (recipe.delayed() or inp.numel() // inp.shape[-1] % 32 == 0):
             return _FP8SwiGLUMLPFn.apply(ln, self.fc1_weight, self.fc1_bias, self.fc2_weight, self.fc2_bias,
-                                         _GemmSpec(recipe, mf, mb, 0, first, self.training, wcache=self._wcache,
-                                                   first_mb=is_first_microbatch))
-        # fc1's backward is the last FP8 op of this module's backward -> it carries the update trigger
-        h = _FP8LinearFn.apply(ln, self.fc1_bias, _GemmSpec(recipe, mf, mb, 0, first, self.training, wcache=self._wcache,
-                                                            first_mb=is_first_microbatch), None, self.fc1_weight)
-        a = self.act_fn(h)
-        return _FP8LinearFn.apply(a, self.fc2_bias, _GemmSpec(recipe, mf, mb, 1, False, self.training, wcache=self._wcache,
-                                                              first_mb=is_first_microbatch), None, self.fc2_weight)
+                                         self._spec(st, is_first_microbatch))
+        h = _FP8LinearFn.apply(ln, self.fc1_bias, self._spec(st, is_first_microbatch), None, self.fc1_weight)
+        return _FP8LinearFn.apply(self.act_fn(h), self.fc2_bias, self._spec(st, is_first_microbatch, 1), None, self.fc2_weight)

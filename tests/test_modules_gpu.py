@@ -291,6 +291,31 @@ def test_te_decoder_layer_vs_hf_bf16_layer(te, dev, scenario):
     assert grel < 0.25, f"{scenario}: o_proj grad relative error {grel:.4f}"
 
 
+@pytest.mark.parametrize("scenario,expected", [
+    ("default", {"cast_amax": 12, "gemm_fp8": 12, "swiglu_cast": 1, "dswiglu_cast": 1}),
+    ("mxfp8", {"mxfp8_quantize": 14, "gemm_mxfp8": 12})])
+def test_decoder_layer_step_launch_counts(te, dev, scenario, expected):
+    """Launches per kind of one forward + backward of a decoder layer of the model above: the host
+    code around the GEMM sites serves both recipes, and a change to it must neither add nor drop a launch for either."""
+    from transformers.models.llama.modeling_llama import LlamaForCausalLM
+    from llm_fp8_amd import llama
+    from llm_fp8_amd.pytorch.profiler import KernelTimer
+    cfg = _tiny_cfg()
+    torch.manual_seed(0)
+    tem = llama.TELlamaForCausalLM.from_hf_state_dict(LlamaForCausalLM(cfg).to(dev).to(torch.bfloat16).state_dict(), cfg, scenario).to(dev)
+    ids = torch.randint(0, cfg.vocab_size, (2, 64), device=dev)
+    tem.train()
+    for _ in range(3):
+        tem(input_ids=ids, labels=ids).loss.backward()
+        tem.zero_grad()
+    x = torch.randn(2, 64, cfg.hidden_size, device=dev, dtype=torch.bfloat16, requires_grad=True)
+    with KernelTimer().install() as timer:
+        y = tem.model.layers[0](x)
+        y.backward(torch.randn_like(y) / 16)
+    torch.cuda.synchronize()
+    assert {k: v["launches"] for k, v in timer.summarize().items()} == expected
+
+
 @pytest.mark.parametrize("use_te,scenario", [(True, "default"), (True, "mxfp8"), (False, "default")])
 def test_train_steps_run_and_update_once_per_step(te, dev, use_te, scenario):
     from llm_fp8_amd import llama, train
@@ -738,7 +763,7 @@ def test_optimizer_mxfp8_weight_handoff_is_bitwise_the_forward_quantiser(te, dev
 
 
 def test_grouped_backward_gemms_change_nothing(te, dev, monkeypatch):
-    """module._dgrad_wgrad: a Linear's dgrad + wgrad as ONE grouped launch (forced on for every eligible site through the autotune
+    """module._grouped_or_two: a Linear's dgrad + wgrad as ONE grouped launch (forced on for every eligible site through the autotune
     cache) against two launches: identical losses, weights and amax histories after 3 optimiser steps, bit for bit."""
     from llm_fp8_amd import train
     from llm_fp8_amd.pytorch.fp8 import FP8GlobalStateManager as G

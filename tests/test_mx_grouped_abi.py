@@ -94,7 +94,7 @@ def test_operands_of_2_gib_are_refused():
 
 
 def test_eligibility_of_the_3b_backward_pairs():
-    """(dgrad, wgrad) of q|k|v, o-proj, fc1 and fc2 of Llama-3.2-3B at 8192 tokens, as module._dgrad_wgrad_mx forms them."""
+    """(dgrad, wgrad) of q|k|v, o-proj, fc1 and fc2 of Llama-3.2-3B at 8192 tokens, as module._MXQ.operands forms them for module._grouped_or_two."""
     from llm_fp8_amd.pytorch import ops
     M = 8192
     for k_in, n_out in ((3072, 5120), (3072, 3072), (3072, 16384), (8192, 3072)):

@@ -209,7 +209,7 @@ def _force_grouped(monkeypatch, ops_, calls):
 
 
 def test_grouped_mx_backward_gemms_change_nothing(dev, monkeypatch):
-    """module._dgrad_wgrad_mx: the MXFP8 recipe with every eligible backward pair as ONE grouped launch against
+    """module._grouped_or_two: the MXFP8 recipe with every eligible backward pair as ONE grouped launch against
     LLM_FP8_AMD_NO_GROUPED_GEMM=1: identical losses and parameter bits after 3 optimiser steps."""
     from llm_fp8_amd import train
     from llm_fp8_amd.pytorch.fp8 import FP8GlobalStateManager as G
