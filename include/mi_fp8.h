@@ -426,7 +426,9 @@ int mi_adamw_bf16(void* p_bf16, const void* g_bf16, void* exp_avg_bf16, void* ex
  * num_gqa_groups, qkv_format="bshd", attention_dropout 0; TE dispatches to flash-attn, README.md:27-28).  bf16 in/out,
  * fp32 softmax statistics, scores never written to memory.
  *   q, o [B, S, H, D]; k, v [B, S, G, D] (H % G == 0), D contiguous, `*_ts` = token stride in elements (multiple of 8), so
- *   the operands may be column slices of one fused [tokens, (H + 2G) * D] buffer.  D in {64, 128}, S % 128 == 0.  Every
+ *   the operands may be column slices of one fused [tokens, (H + 2G) * D] buffer.  D in {64, 128}, S >= 128 and S % 16 == 0
+ *   (the reference's collator pads to a multiple of 16; S % 128 != 0 launches the TAIL instantiations, whose last 128-row
+ *   block is partial: rows at or past S are neither read nor written).  Every
  *   bf16 pointer (here and in mi_attn_bwd) must be 16-byte aligned; other shapes, strides or alignments are refused.
  *   lse [B, H, S] fp32 = log2-domain log-sum-exp (max * c + log2(sum), c = scale * log2(e)); kept for the backward.
  */
@@ -443,6 +445,7 @@ int mi_attn_fwd_diag(const void* q, const void* k, const void* v, void* o, float
  * Backward of mi_attn_fwd: P is recomputed from q, k and `lse`; two launches (dQ pass, which also writes
  * delta[B, H, S] = rowsum(dO * O), then the dK/dV pass), no sums across workgroups: results are bitwise reproducible.
  * dq [B, S, H, D], dk / dv [B, S, G, D] bf16 with their own token strides (they may be slices of one fused buffer).
+ * Shapes as mi_attn_fwd (S >= 128, S % 16 == 0); `delta`, like `lse`, is written for rows below S only.
  */
 int mi_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                 float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,

@@ -13,6 +13,10 @@
 //
 // Layouts: q/o [B, S, H, D], k/v [B, S, G, D] bf16 with D contiguous and a caller-given token stride; lse [B, H, S] f32 in
 // the log2 domain (m * c + log2 l, c = scale * log2 e).
+//
+// Sequence lengths: S >= 128, S % 16 == 0 (the reference's collator pads a batch to a multiple of 16).  S % 128 == 0 launches
+// the kernels with TAIL = false, which is the code without any of the guards.  Otherwise the grids are ceil(S / 128) blocks
+// and the TAIL = true instantiations guard the one partial block / tile / slice at the end (see attn_fwd_kernel).
 #include "mi_common.h"
 
 namespace mi {
@@ -100,9 +104,26 @@ __device__ __forceinline__ void stage_dma(rsrc_t rs, const int* voff, int soff, 
   for (int i = 0; i < D / 32; ++i)
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, MI_LDS_PTR(tile + (4 * i + w) * 1024), 16, voff[i], soff, 0, 0);
 }
+// TAIL form: the tile advance goes into the per-lane offset, the part of the address that the buffer's range check sees, so a
+// row at or past S (past num_records) is not fetched and its 16 bytes of the image are zeros
+template <int D>
+__device__ __forceinline__ void stage_dma_checked(rsrc_t rs, const int* voff, int adv, char* tile, int w) {
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, MI_LDS_PTR(tile + (4 * i + w) * 1024), 16, (int)((u32)voff[i] + (u32)adv), 0, 0, 0);
+}
+template <int D, bool TAIL>
+__device__ __forceinline__ void stage_tile(rsrc_t rs, const int* voff, int adv, char* tile, int w) {
+  if (TAIL) stage_dma_checked<D>(rs, voff, adv, tile, w);
+  else stage_dma<D>(rs, voff, adv, tile, w);
+}
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-template <int D, bool CAUSAL, bool DIAG = false>
+// TAIL (all three kernels): S is a multiple of 16 but not of 128, so the last 128-row block (and the last 64-key tile, the
+// last 32-row slice) is partial.  Rows at or past S belong to the next batch / head or lie outside the tensor: their loads
+// are clamped to row S - 1 or replaced by zeros, their stores are predicated, and a wave whose 32 rows are all past S keeps
+// staging its share of every tile and meeting every barrier but skips the arithmetic.  TAIL = false is the code as it was.
+template <int D, bool CAUSAL, bool DIAG = false, bool TAIL = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                           const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                           float* __restrict__ lse, int S, int H, int G, int64_t q_ts,
@@ -115,13 +136,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
   const int qb = gridDim.x - 1 - blockIdx.x, head = blockIdx.y, b = blockIdx.z, g = head / (H / G);
   const int q_first = qb * ATT_QB + w * 32;  // first query row of this wave
   const int qrow = q_first + r;
-  const int ntiles = CAUSAL ? (qb * ATT_QB + ATT_QB) / ATT_KB : S / ATT_KB;
+  int ntiles = CAUSAL ? (qb * ATT_QB + ATT_QB) / ATT_KB : S / ATT_KB;
+  if (TAIL) {  // the last tile is partial; a causal row below S never sees a key at or past S, so the diagonal logic stays
+    const int stiles = (S + ATT_KB - 1) / ATT_KB;
+    ntiles = CAUSAL ? min(ntiles, stiles) : stiles;
+  }
   const uint16_t* kbase = k + (int64_t)b * S * k_ts + (int64_t)g * D;
   const uint16_t* vbase = v + (int64_t)b * S * v_ts + (int64_t)g * D;
 
   bf8 qf[KT];
   {
-    const uint16_t* qp = q + ((int64_t)b * S + qrow) * q_ts + (int64_t)head * D + 8 * h;
+    const uint16_t* qp = q + ((int64_t)b * S + (TAIL ? min(qrow, S - 1) : qrow)) * q_ts + (int64_t)head * D + 8 * h;
 #pragma unroll
     for (int t = 0; t < KT; ++t) qf[t] = as_bf8(*reinterpret_cast<const v4i*>(qp + 16 * t));
   }
@@ -142,8 +167,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
   int kvo[D / 32], vvo[D / 32];
   dma_voffsets<D>(kvo, k_ts, tid);
   dma_voffsets<D>(vvo, v_ts, tid);
-  stage_dma<D>(rsK, kvo, 0, lds, w);
-  stage_dma<D>(rsV, vvo, 0, lds + 2 * TILE, w);
+  stage_tile<D, TAIL>(rsK, kvo, 0, lds, w);
+  stage_tile<D, TAIL>(rsV, vvo, 0, lds + 2 * TILE, w);
   dma_wait_all();
   __syncthreads();
 
@@ -163,11 +188,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
     const char* vt = lds + (2 + (j & 1)) * TILE;
     const bool more = j + 1 < ntiles;
     if (more) {
-      stage_dma<D>(rsK, kvo, (int)((int64_t)(j + 1) * ATT_KB * k_ts * 2), lds + ((j + 1) & 1) * TILE, w);
-      stage_dma<D>(rsV, vvo, (int)((int64_t)(j + 1) * ATT_KB * v_ts * 2), lds + (2 + ((j + 1) & 1)) * TILE, w);
+      stage_tile<D, TAIL>(rsK, kvo, (int)((int64_t)(j + 1) * ATT_KB * k_ts * 2), lds + ((j + 1) & 1) * TILE, w);
+      stage_tile<D, TAIL>(rsV, vvo, (int)((int64_t)(j + 1) * ATT_KB * v_ts * 2), lds + (2 + ((j + 1) & 1)) * TILE, w);
     }
     const int key0 = j * ATT_KB;
-    if (!CAUSAL || key0 <= q_first + 31) {  // wave-uniform: tiles entirely above the diagonal contribute nothing
+    // wave-uniform: tiles entirely above the diagonal contribute nothing (TAIL: nor does a wave whose rows are all past S)
+    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31)) {
       f16v sacc[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -196,6 +222,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
 #pragma unroll
           for (int i = 0; i < 16; ++i)
             if (key0 + 32 * kb + acc_row(i, h) > qrow) sacc[kb][i] = -INFINITY;
+      }
+      if (TAIL && !CAUSAL && key0 + ATT_KB > S) {  // keys at or past S were staged as zeros: a score of 0, not -inf
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (key0 + 32 * kb + acc_row(i, h) >= S) sacc[kb][i] = -INFINITY;
       }
       float mx = sacc[0][0];
 #pragma unroll
@@ -258,7 +291,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
 
   l += __shfl_xor(l, 32);
   const float inv = 1.0f / l;
-  if (h == 0) lse[((int64_t)b * H + head) * S + qrow] = m * c + __builtin_amdgcn_logf(l);  // v_log_f32 = log2
+  if (h == 0 && (!TAIL || qrow < S)) lse[((int64_t)b * H + head) * S + qrow] = m * c + __builtin_amdgcn_logf(l);  // v_log_f32 = log2
   // O^T (d in registers, query on the lane) -> whole rows through this wave's own LDS slice
   char* ot = lds + w * (32 * D * 2);
 #pragma unroll
@@ -278,15 +311,16 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
   for (int it = 0; it < 32 * CPR / 64; ++it) {
     const int idx = it * 64 + lane, row = idx / CPR, ch = idx % CPR;
     const v4i val = *reinterpret_cast<const v4i*>(ot + row * (D * 2) + 16 * (ch ^ (row & (CPR - 1))));
-    *reinterpret_cast<v4i*>(o + ((int64_t)b * S + q_first + row) * o_ts + (int64_t)head * D + ch * 8) = val;
+    if (!TAIL || q_first + row < S) *reinterpret_cast<v4i*>(o + ((int64_t)b * S + q_first + row) * o_ts + (int64_t)head * D + ch * 8) = val;
   }
 }
 
 
 // O^T-style accumulators (d in registers, row index on the lane) -> bf16 rows of `out` through a wave-private LDS slice
-template <int D>
+// (TAIL: only the first `nrows` rows are stored; nrows <= 0 stores nothing)
+template <int D, bool TAIL = false>
 __device__ __forceinline__ void store_rows_from_accT(const f16v (&acc)[D / 32], float mul, char* slice, uint16_t* out,
-                                                     int64_t row_stride, int lane) {
+                                                     int64_t row_stride, int lane, int nrows = 32) {
   const int r = lane & 31, h = lane >> 5;
   constexpr int CPR = D / 8;
 #pragma unroll
@@ -305,14 +339,14 @@ __device__ __forceinline__ void store_rows_from_accT(const f16v (&acc)[D / 32], 
   for (int it = 0; it < 32 * CPR / 64; ++it) {
     const int idx = it * 64 + lane, row = idx / CPR, ch = idx % CPR;
     const v4i val = *reinterpret_cast<const v4i*>(slice + row * (D * 2) + 16 * (ch ^ (row & (CPR - 1))));
-    *reinterpret_cast<v4i*>(out + (int64_t)row * row_stride + ch * 8) = val;
+    if (!TAIL || row < nrows) *reinterpret_cast<v4i*>(out + (int64_t)row * row_stride + ch * 8) = val;
   }
 }
 
 // dQ pass: same walk as the forward (128 query rows per workgroup, 64-key tiles).  S^T and dP^T are recomputed with the
 // query on the lane (LSE and delta are lane constants), dS^T feeds  dQ^T += K^T . dS^T  straight from the accumulators.
 // Also writes delta[b, h, q] = sum_d dO * O for the dK/dV pass.
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, bool TAIL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                              const uint16_t* __restrict__ v, const uint16_t* __restrict__ o,
                                                              const uint16_t* __restrict__ dout, const float* __restrict__ lse,
@@ -326,16 +360,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
   const int qb = gridDim.x - 1 - blockIdx.x, head = blockIdx.y, b = blockIdx.z, g = head / (H / G);
   const int q_first = qb * ATT_QB + w * 32;
   const int qrow = q_first + r;
-  const int ntiles = CAUSAL ? (qb * ATT_QB + ATT_QB) / ATT_KB : S / ATT_KB;
+  int ntiles = CAUSAL ? (qb * ATT_QB + ATT_QB) / ATT_KB : S / ATT_KB;
+  if (TAIL) {  // the last tile is partial; a causal row below S never sees a key at or past S, so the diagonal logic stays
+    const int stiles = (S + ATT_KB - 1) / ATT_KB;
+    ntiles = CAUSAL ? min(ntiles, stiles) : stiles;
+  }
   const uint16_t* kbase = k + (int64_t)b * S * k_ts + (int64_t)g * D;
   const uint16_t* vbase = v + (int64_t)b * S * v_ts + (int64_t)g * D;
 
   bf8 qf[KT], dof[KT];
   float dl = 0.0f;
   {
-    const uint16_t* qp = q + ((int64_t)b * S + qrow) * q_ts + (int64_t)head * D + 8 * h;
-    const uint16_t* dp = dout + ((int64_t)b * S + qrow) * do_ts + (int64_t)head * D + 8 * h;
-    const uint16_t* op = o + ((int64_t)b * S + qrow) * o_ts + (int64_t)head * D + 8 * h;
+    const int lrow = TAIL ? min(qrow, S - 1) : qrow;  // rows at or past S read row S - 1; nothing of theirs is stored
+    const uint16_t* qp = q + ((int64_t)b * S + lrow) * q_ts + (int64_t)head * D + 8 * h;
+    const uint16_t* dp = dout + ((int64_t)b * S + lrow) * do_ts + (int64_t)head * D + 8 * h;
+    const uint16_t* op = o + ((int64_t)b * S + lrow) * o_ts + (int64_t)head * D + 8 * h;
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
       qf[t] = as_bf8(*reinterpret_cast<const v4i*>(qp + 16 * t));
@@ -351,8 +390,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
   }
   dl += __shfl_xor(dl, 32);
   const int64_t stat = ((int64_t)b * H + head) * S + qrow;
-  if (h == 0) delta[stat] = dl;
-  float my_lse = lse[stat];
+  if (h == 0 && (!TAIL || qrow < S)) delta[stat] = dl;
+  float my_lse = lse[TAIL ? ((int64_t)b * H + head) * S + min(qrow, S - 1) : stat];
 #pragma unroll
   for (int t = 0; t < KT; ++t) {
     retire(qf[t]);
@@ -373,8 +412,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
   int kvo[D / 32], vvo[D / 32];
   dma_voffsets<D>(kvo, k_ts, tid);
   dma_voffsets<D>(vvo, v_ts, tid);
-  stage_dma<D>(rsK, kvo, 0, lds, w);
-  stage_dma<D>(rsV, vvo, 0, lds + 2 * TILE, w);
+  stage_tile<D, TAIL>(rsK, kvo, 0, lds, w);
+  stage_tile<D, TAIL>(rsV, vvo, 0, lds + 2 * TILE, w);
   dma_wait_all();
   __syncthreads();
 
@@ -383,8 +422,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
     const char* vt = lds + (2 + (j & 1)) * TILE;
     const bool more = j + 1 < ntiles;
     if (more) {
-      stage_dma<D>(rsK, kvo, (int)((int64_t)(j + 1) * ATT_KB * k_ts * 2), lds + ((j + 1) & 1) * TILE, w);
-      stage_dma<D>(rsV, vvo, (int)((int64_t)(j + 1) * ATT_KB * v_ts * 2), lds + (2 + ((j + 1) & 1)) * TILE, w);
+      stage_tile<D, TAIL>(rsK, kvo, (int)((int64_t)(j + 1) * ATT_KB * k_ts * 2), lds + ((j + 1) & 1) * TILE, w);
+      stage_tile<D, TAIL>(rsV, vvo, (int)((int64_t)(j + 1) * ATT_KB * v_ts * 2), lds + (2 + ((j + 1) & 1)) * TILE, w);
     }
     const int key0 = j * ATT_KB;
     auto block = [&](const int kb) {  // one 32-key block of the tile against this wave's 32 query rows
@@ -416,6 +455,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
       for (int i = 0; i < 16; ++i) {
         float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[i], c, -my_lse));
         if (diag && key0 + 32 * kb + acc_row(i, h) > qrow) p = 0.0f;
+        if (TAIL && !CAUSAL && key0 + 32 * kb + acc_row(i, h) >= S) p = 0.0f;  // keys staged as zeros
         sacc[i] = p * (pacc[i] - dl);
       }
 #pragma unroll
@@ -434,19 +474,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
       }
     };
     // (wave-uniform tests: blocks entirely above the diagonal contribute nothing)
-    if (!CAUSAL || key0 <= q_first + 31) block(0);
-    if (!CAUSAL || key0 + 32 <= q_first + 31) block(1);
+    // (TAIL: nor does a wave whose rows are all past S, nor a block whose keys are)
+    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31)) block(0);
+    if ((!TAIL || (q_first < S && key0 + 32 < S)) && (!CAUSAL || key0 + 32 <= q_first + 31)) block(1);
     dma_wait_all();  // the next tile has landed (this wave's share; the barrier covers the others')
     __syncthreads();
   }
-  store_rows_from_accT<D>(acc, scale, lds + w * (32 * D * 2), dq + ((int64_t)b * S + q_first) * dq_ts + (int64_t)head * D, dq_ts, lane);
+  store_rows_from_accT<D, TAIL>(acc, scale, lds + w * (32 * D * 2), dq + ((int64_t)b * S + q_first) * dq_ts + (int64_t)head * D, dq_ts, lane,
+                                S - q_first);
 }
 
 // dK / dV pass: one workgroup = 4 waves = 128 keys of one (batch, kv head); each wave keeps K and V rows of its 32 keys as
 // B operands (key on the lane) and dK^T, dV^T of those keys in accumulators while the workgroup sweeps the group's query
 // heads x 32-row query slices (Q and dO slices staged once for all four waves; row reads for S and dP, transposed reads
 // for the dV^T and dK^T products).
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, bool TAIL = false>
 __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                                const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
@@ -459,7 +501,7 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
   __shared__ __attribute__((aligned(16))) char lds[(2 * BUF > 4 * SL) ? 2 * BUF : 4 * SL];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
   // heaviest key blocks first: the key-block index is the slowest-varying part of the linear workgroup id
-  const int lin = blockIdx.x, nkb = S / 128;
+  const int lin = blockIdx.x, nkb = TAIL ? (S + 127) / 128 : S / 128;
   const int kbi = CAUSAL ? lin / (G * B) : nkb - 1 - lin / (G * B);
   const int g = (lin / B) % G, b = lin % B;
   const int rep = H / G;
@@ -468,8 +510,9 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
 
   bf8 kf[KT], vf[KT];
   {
-    const uint16_t* kp = k + ((int64_t)b * S + key) * k_ts + (int64_t)g * D + 8 * h;
-    const uint16_t* vp = v + ((int64_t)b * S + key) * v_ts + (int64_t)g * D + 8 * h;
+    const int lkey = TAIL ? min(key, S - 1) : key;  // keys at or past S read key S - 1; nothing of theirs is stored
+    const uint16_t* kp = k + ((int64_t)b * S + lkey) * k_ts + (int64_t)g * D + 8 * h;
+    const uint16_t* vp = v + ((int64_t)b * S + lkey) * v_ts + (int64_t)g * D + 8 * h;
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
       kf[t] = as_bf8(*reinterpret_cast<const v4i*>(kp + 16 * t));
@@ -488,7 +531,7 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
     for (int i = 0; i < 16; ++i) { dka[d][i] = 0.0f; dva[d][i] = 0.0f; }
 
   const int sl0 = CAUSAL ? (kbi * 128) / 32 : 0;  // first query slice that can see this key block
-  const int nsl = S / 32 - sl0;
+  const int nsl = (TAIL ? (S + 31) / 32 : S / 32) - sl0;
   const int nsteps = rep * nsl;
   // staging: thread -> 2 chunks of the Q slice and 2 of the dO slice; threads 0..31 lse, 32..63 delta
   v4i qreg[2], dreg[2];
@@ -501,11 +544,19 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
     for (int i = 0; i < 2; ++i) {
       const int cidx = tid + 256 * i, row = cidx / (D / 8), ch = cidx % (D / 8);
       if (D == 128 || cidx < 32 * (D / 8)) {
-        qreg[i] = *reinterpret_cast<const v4i*>(qp + (int64_t)row * q_ts + ch * 8);
-        dreg[i] = *reinterpret_cast<const v4i*>(dp + (int64_t)row * do_ts + ch * 8);
+        if (TAIL && q0 + row >= S) {  // a query row past S adds exactly nothing: zeros, so that no 0 x NaN reaches the sums
+          qreg[i] = v4i{0, 0, 0, 0};
+          dreg[i] = v4i{0, 0, 0, 0};
+        } else {
+          qreg[i] = *reinterpret_cast<const v4i*>(qp + (int64_t)row * q_ts + ch * 8);
+          dreg[i] = *reinterpret_cast<const v4i*>(dp + (int64_t)row * do_ts + ch * 8);
+        }
       }
     }
-    if (tid < 64) sreg = (tid < 32 ? lse : delta)[((int64_t)b * H + head) * S + q0 + (tid & 31)];
+    if (tid < 64) {
+      if (TAIL && q0 + (tid & 31) >= S) sreg = 0.0f;
+      else sreg = (tid < 32 ? lse : delta)[((int64_t)b * H + head) * S + q0 + (tid & 31)];
+    }
   };
   auto store_step = [&](char* buf) {
 #pragma unroll
@@ -527,7 +578,8 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
     const bool more = step + 1 < nsteps;
     if (more) load_step(step + 1);
     const int q0 = (sl0 + step % nsl) * 32;
-    if (!CAUSAL || q0 + 31 >= key_first) {  // wave-uniform: slices entirely before this wave's keys see none of them
+    // wave-uniform: slices entirely before this wave's keys see none of them (TAIL: a wave whose keys are all past S has no sums)
+    if ((!TAIL || key_first < S) && (!CAUSAL || q0 + 31 >= key_first)) {
       const char* qt = buf;
       const char* dt = buf + SL;
       const float* st = reinterpret_cast<const float*>(buf + 2 * SL);
@@ -550,6 +602,7 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
           const int i = 4 * a + e;
           float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[i], c, -ls[e]));
           if (diag && key > q0 + acc_row(i, h)) p = 0.0f;
+          if (TAIL && q0 + acc_row(i, h) >= S) p = 0.0f;  // a select: p and dS of a row past S are 0 whatever exp2 gave
           sacc[i] = p;
           dsacc[i] = p * (pacc[i] - dl[e]);
         }
@@ -576,9 +629,9 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
     __syncthreads();
   }
   char* slice = lds + w * SL;
-  store_rows_from_accT<D>(dka, scale, slice, dk + ((int64_t)b * S + key_first) * dk_ts + (int64_t)g * D, dk_ts, lane);
+  store_rows_from_accT<D, TAIL>(dka, scale, slice, dk + ((int64_t)b * S + key_first) * dk_ts + (int64_t)g * D, dk_ts, lane, S - key_first);
   __builtin_amdgcn_wave_barrier();
-  store_rows_from_accT<D>(dva, 1.0f, slice, dv + ((int64_t)b * S + key_first) * dv_ts + (int64_t)g * D, dv_ts, lane);
+  store_rows_from_accT<D, TAIL>(dva, 1.0f, slice, dv + ((int64_t)b * S + key_first) * dv_ts + (int64_t)g * D, dv_ts, lane, S - key_first);
 }
 
 }  // namespace mi
@@ -589,23 +642,29 @@ extern "C" int mi_attn_fwd(const void* q, const void* k, const void* v, void* o,
   MI_CHECK_ARG(q && k && v && o && lse, "mi_attn_fwd: null pointer");
   MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "mi_attn_fwd: bad B/H/G (%d, %d, %d)", B, H, G);
   MI_CHECK_ARG(D == 128 || D == 64, "mi_attn_fwd: head_dim %d not supported (64, 128)", D);
-  MI_CHECK_ARG(S >= 128 && S % 128 == 0, "mi_attn_fwd: seq %d must be a multiple of 128", S);
+  MI_CHECK_ARG(S >= 128 && S % 16 == 0, "mi_attn_fwd: seq %d must be a multiple of 16 and at least 128", S);
   MI_CHECK_ARG(q_ts % 8 == 0 && k_ts % 8 == 0 && v_ts % 8 == 0 && o_ts % 8 == 0, "mi_attn_fwd: token strides must be multiples of 8");
   MI_CHECK_ARG((int64_t)S * k_ts * 2 < (1LL << 31) && (int64_t)S * v_ts * 2 < (1LL << 31) && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0,
                "mi_attn_fwd: one batch of K / V must span < 2 GiB and be 16-byte aligned (32-bit buffer offsets of the LDS DMA)");
   MI_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)o % 16) == 0, "mi_attn_fwd: q and o must be 16-byte aligned (16-byte row accesses)");
   MI_CHECK_ARG(H <= 65535 && B <= 65535, "mi_attn_fwd: grid too large");
   const float c = scale * 1.4426950408889634f;
-  dim3 grid(S / mi::ATT_QB, H, B), block(256);
+  const bool tail = S % mi::ATT_QB != 0;  // a partial last block: the TAIL instantiations; full blocks launch the kernels as before
+  dim3 grid((S + mi::ATT_QB - 1) / mi::ATT_QB, H, B), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define MI_ATTN_FWD(DD, CC)                                                                                            \
-  hipLaunchKernelGGL((mi::attn_fwd_kernel<DD, CC>), grid, block, 0, st, (const uint16_t*)q, (const uint16_t*)k,          \
+#define MI_ATTN_FWD_T(DD, CC, TT)                                                                                      \
+  hipLaunchKernelGGL((mi::attn_fwd_kernel<DD, CC, false, TT>), grid, block, 0, st, (const uint16_t*)q, (const uint16_t*)k, \
                      (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, q_ts, k_ts, v_ts, o_ts, c, (unsigned long long*)nullptr)
+#define MI_ATTN_FWD(DD, CC)                                                                                            \
+  do {                                                                                                                 \
+    if (tail) MI_ATTN_FWD_T(DD, CC, true); else MI_ATTN_FWD_T(DD, CC, false);                                          \
+  } while (0)
   if (D == 128) {
     if (causal) MI_ATTN_FWD(128, true); else MI_ATTN_FWD(128, false);
   } else {
     if (causal) MI_ATTN_FWD(64, true); else MI_ATTN_FWD(64, false);
   }
+#undef MI_ATTN_FWD_T
 #undef MI_ATTN_FWD
   MI_CHECK_LAUNCH("mi_attn_fwd launch");
   return MI_OK;
@@ -635,7 +694,7 @@ extern "C" int mi_attn_bwd(const void* q, const void* k, const void* v, const vo
   MI_CHECK_ARG(q && k && v && o && dout && lse && delta && dq && dk && dv, "mi_attn_bwd: null pointer");
   MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "mi_attn_bwd: bad B/H/G (%d, %d, %d)", B, H, G);
   MI_CHECK_ARG(D == 128 || D == 64, "mi_attn_bwd: head_dim %d not supported (64, 128)", D);
-  MI_CHECK_ARG(S >= 128 && S % 128 == 0, "mi_attn_bwd: seq %d must be a multiple of 128", S);
+  MI_CHECK_ARG(S >= 128 && S % 16 == 0, "mi_attn_bwd: seq %d must be a multiple of 16 and at least 128", S);
   MI_CHECK_ARG((q_ts | k_ts | v_ts | o_ts | do_ts | dq_ts | dk_ts | dv_ts) % 8 == 0, "mi_attn_bwd: token strides must be multiples of 8");
   MI_CHECK_ARG((int64_t)S * k_ts * 2 < (1LL << 31) && (int64_t)S * v_ts * 2 < (1LL << 31) && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0,
                "mi_attn_bwd: one batch of K / V must span < 2 GiB and be 16-byte aligned (32-bit buffer offsets of the LDS DMA)");
@@ -644,15 +703,21 @@ extern "C" int mi_attn_bwd(const void* q, const void* k, const void* v, const vo
   MI_CHECK_ARG(H <= 65535 && B <= 65535, "mi_attn_bwd: grid too large");
   const float c = scale * 1.4426950408889634f;
   hipStream_t st = (hipStream_t)stream;
-  dim3 grid_q(S / mi::ATT_QB, H, B), grid_kv((unsigned)((int64_t)(S / 128) * G * B)), block(256);
-#define MI_ATTN_BWD(DD, CC)                                                                                            \
+  const bool tail = S % mi::ATT_QB != 0;  // a partial last block: the TAIL instantiations; full blocks launch the kernels as before
+  const int nblk = (S + mi::ATT_QB - 1) / mi::ATT_QB;
+  dim3 grid_q(nblk, H, B), grid_kv((unsigned)((int64_t)nblk * G * B)), block(256);
+#define MI_ATTN_BWD_T(DD, CC, TT)                                                                                      \
   do {                                                                                                                 \
-    hipLaunchKernelGGL((mi::attn_bwd_dq_kernel<DD, CC>), grid_q, block, 0, st, (const uint16_t*)q, (const uint16_t*)k,   \
+    hipLaunchKernelGGL((mi::attn_bwd_dq_kernel<DD, CC, TT>), grid_q, block, 0, st, (const uint16_t*)q, (const uint16_t*)k, \
                        (const uint16_t*)v, (const uint16_t*)o, (const uint16_t*)dout, lse, delta, (uint16_t*)dq, S, H,  \
                        G, q_ts, k_ts, v_ts, o_ts, do_ts, dq_ts, c, scale);                                               \
-    hipLaunchKernelGGL((mi::attn_bwd_dkdv_kernel<DD, CC>), grid_kv, block, 0, st, (const uint16_t*)q,                    \
+    hipLaunchKernelGGL((mi::attn_bwd_dkdv_kernel<DD, CC, TT>), grid_kv, block, 0, st, (const uint16_t*)q,                \
                        (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)dout, lse, delta, (uint16_t*)dk,        \
                        (uint16_t*)dv, S, H, G, B, q_ts, k_ts, v_ts, do_ts, dk_ts, dv_ts, c, scale);                      \
+  } while (0)
+#define MI_ATTN_BWD(DD, CC)                                                                                            \
+  do {                                                                                                                 \
+    if (tail) MI_ATTN_BWD_T(DD, CC, true); else MI_ATTN_BWD_T(DD, CC, false);                                          \
   } while (0)
   if (D == 128) {
     if (causal) MI_ATTN_BWD(128, true); else MI_ATTN_BWD(128, false);
@@ -660,6 +725,7 @@ extern "C" int mi_attn_bwd(const void* q, const void* k, const void* v, const vo
     if (causal) MI_ATTN_BWD(64, true); else MI_ATTN_BWD(64, false);
   }
 #undef MI_ATTN_BWD
+#undef MI_ATTN_BWD_T
   MI_CHECK_LAUNCH("mi_attn_bwd launch");
   return MI_OK;
 }
