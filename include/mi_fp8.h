@@ -118,13 +118,14 @@ int mi_scale_update(float* amax_history, float* scale, float* scale_inv, const f
  *       5 = the kernel of 4 launched with one workgroup per tile (hardware-balanced: for use while collectives hold part of
  *           the chip), 6 = four-wave kernel (128x128 wave tiles, one wave per SIMD; mi_gemm_w4.hip), one tile per workgroup,
  *       9 = persistent four-wave kernel, 40-43 force one tile shape of 4, 44 = stream-K form of 4 (see mi_gemm_set_workspace),
- *       45 = 4, 47 = auto that takes the persistent four-wave kernel where it is the faster one (no bias, 256-multiples,
- *       K >= 512, and 256 x 256 is the eight-wave kernel's own tile choice), else as 0.
+ *       45 = 4, 47 = auto that takes the persistent four-wave kernel where it is the faster one (256-multiples, K >= 512, and
+ *       256 x 256 is the eight-wave kernel's own tile choice; with or without a bias), else as 0.  Of the four-wave kernels
+ *       only 9 takes a bias: 6 with one is MI_ERR_ARG.
  * 2/3/6 need M,N % 256 == 0 and K % 128 == 0 (6, 9: K % 256 == 0); 4 additionally K % 256 == 0, bf16 output and operands
  * below 2 GiB (M, N may also be multiples of 192: workgroup tiles of 256/192 rows x 256/192 columns are picked per shape).
  * auto picks a persistent kernel when the shape allows, else 3, else 1.  Every algo listed here gives the SAME bits for the
  * same inputs (one fp32 summation order per output element), tests/test_kernels_gpu.py.
- * Not part of this library: the timing / ablation / stamp builds (algos 7, 8, 10-30, 46) live in the lab build
+ * Not part of this library: the timing / ablation / stamp builds (algos 7, 8, 10-30, 46, 50-73) live in the lab build
  * (tools/bin/libmi_fp8_lab.so, `make -C llm_fp8_amd/csrc lab`, compiled with -DMI_DIAG; see tools/README.md); the product
  * library returns MI_ERR_ARG for them.
  * Leading dimensions and pointers (every algo; pinned by tests/test_gemm_contract_gpu.py): A, B and D may be views into larger
@@ -434,12 +435,25 @@ int mi_adamw_bf16(void* p_bf16, const void* g_bf16, void* exp_avg_bf16, void* ex
  */
 int mi_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G, int D,
                 int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal, void* stream);
+/* What the library launches for one mi_gemm_fp8 / mi_gemm_mxfp8 / mi_gemm_fp8_clock call.  No entry point of this library returns
+ * it; the lab library's mi_gemm_plan_diag (below) does.  family 0 = nothing to launch (M or N is 0), 1 = generic, 2 = two-phase,
+ * 3 = eight-phase, 4 = persistent eight-wave, 5 = stream-K, 6 = four-wave, one tile per workgroup, 7 = four-wave persistent;
+ * build / sched = the kernel's ABL / S template values; mx = block-scaled; tile_cfg as in mi_gemm_fp8_grouped (-1: no tile shape to
+ * choose), tiles_m x tiles_n tiles of it (the generic kernel has none and ignores them); bias_use 0 = unused, 1 = added, 2 = a stamp buffer. */
+typedef struct mi_gemm_plan {
+  int algo, family, build, sched, mx, tile_cfg, tiles_m, tiles_n, grid_x, grid_y, block, one_tile_per_wg, sk_units, bias_use;
+} mi_gemm_plan;
 #ifdef MI_DIAG
 /* LAB BUILD ONLY (-DMI_DIAG).  Timing-only diagnostic build of the forward kernel (causal, D = 128): per wave, shader cycles spent in {S^T MFMAs + K fragment
  * reads, softmax arithmetic, P.V MFMAs + V fragment reads, stage stores incl. the wait for the next tile's loads, barrier};
  * dbg [B, H, S/128, 4 waves, 8] u64 (slot 5 = tiles walked).  Shares only: the stamps forbid overlaps the real kernel has. */
 int mi_attn_fwd_diag(const void* q, const void* k, const void* v, void* o, float* lse, unsigned long long* dbg, int B, int S,
                      int H, int G, int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, void* stream);
+/* LAB BUILD ONLY (-DMI_DIAG).  What mi_gemm_fp8 (entry 0), mi_gemm_mxfp8 (1) or mi_gemm_fp8_clock (2) would launch for a call: the
+ * shape and leading-dimension checks and every algo / shape refusal of that entry point, with its return code and mi_last_error
+ * text, and no launch; it takes no operands.  mi_gemm_mxfp8 passes lda = ldb = K, ldd = N.  On MI_OK `out` holds the plan. */
+int mi_gemm_plan_diag(int entry, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldd, int fmt_a, int fmt_b,
+                      int out_dtype, int has_bias, int algo, mi_gemm_plan* out);
 #endif
 /*
  * Backward of mi_attn_fwd: P is recomputed from q, k and `lse`; two launches (dQ pass, which also writes

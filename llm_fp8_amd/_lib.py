@@ -30,6 +30,12 @@ class GemmMxProblem(ctypes.Structure):
     _fields_ = [("A", ctypes.c_void_p), ("SA", ctypes.c_void_p), ("B", ctypes.c_void_p), ("SB", ctypes.c_void_p),
                 ("D", ctypes.c_void_p), ("M", ctypes.c_int64), ("N", ctypes.c_int64), ("K", ctypes.c_int64)]
 
+class GemmPlan(ctypes.Structure):
+    """include/mi_fp8.h `mi_gemm_plan` (filled by the lab library only)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("algo", "family", "build", "sched", "mx", "tile_cfg", "tiles_m", "tiles_n", "grid_x",
+                                            "grid_y", "block", "one_tile_per_wg", "sk_units", "bias_use")]
+
+
 # name -> argtypes (all return int unless noted); mirrors include/mi_fp8.h exactly
 SIGNATURES = {
     "mi_abi_version": [],
@@ -87,6 +93,7 @@ SIGNATURES = {
 # entry points only the lab build exports (#ifdef MI_DIAG in include/mi_fp8.h)
 LAB_SIGNATURES = {
     "mi_attn_fwd_diag": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_float, _p],
+    "mi_gemm_plan_diag": [_c_int] + [_c_i64] * 6 + [_c_int] * 5 + [ctypes.POINTER(GemmPlan)],
 }
 
 _lib = None

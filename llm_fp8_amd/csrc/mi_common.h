@@ -12,13 +12,15 @@ namespace mi {
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 
-#define MI_CHECK_ARG(cond, ...)            \
+#define MI_CHECK_AS(rc, cond, ...)         \
   do {                                     \
     if (!(cond)) {                         \
       mi::set_error(__VA_ARGS__);          \
-      return MI_ERR_ARG;                   \
+      return rc;                           \
     }                                      \
   } while (0)
+#define MI_CHECK_ARG(cond, ...) MI_CHECK_AS(MI_ERR_ARG, cond, __VA_ARGS__)
+#define MI_CHECK_SHAPE(cond, ...) MI_CHECK_AS(MI_ERR_SHAPE, cond, __VA_ARGS__)
 
 #define MI_CHECK_LAUNCH(what)                                   \
   do {                                                          \

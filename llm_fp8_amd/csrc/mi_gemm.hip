@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 namespace mi {
@@ -1277,248 +1278,313 @@ static const SkWorkspace* sk_workspace() {
 }
 
 // stream-K plan for 256x256 tiles: units per workgroup (0 = not applicable / not worth it)
-static int sk_units(int64_t M, int64_t N, int64_t K, bool force) {
+static int sk_units(int64_t M, int64_t N, int64_t K) {
   if (M % 256 || N % 256 || K % 256) return 0;
   const SkWorkspace* ws = sk_workspace();
   const int ncu = num_cus();
   if (!ws || ws->nslots < ncu) return 0;
   const int64_t ntiles = (M / 256) * (N / 256), nk = K / BK;
   if (ntiles <= ncu || ntiles % ncu == 0) return 0;
-  const int64_t rounds = (ntiles + ncu - 1) / ncu;
-  const double waste = 1.0 - (double)ntiles / (double)(rounds * ncu);
-  if (!force && waste < 0.06) return 0;
   int64_t U = (ntiles * nk + ncu - 1) / ncu;
   U += U & 1;
   return U >= nk ? (int)U : 0;
 }
 
-template <int FA, int FB, bool MX, bool BIAS, int ABL, int MA1, int NB1, bool DEPI = true>
-static void launch_p8_cfg(const uint8_t* a, const uint8_t* b, uint16_t* D, const float* sa_inv, const float* sb_inv,
-                          const uint8_t* SA, const uint8_t* SB, const uint16_t* bias, int64_t M, int64_t N, int64_t K,
-                          int64_t lda, int64_t ldb, int64_t ldd, hipStream_t st, bool one_tile_per_wg = false) {
-  constexpr int TBM = 2 * (64 + 16 * MA1), TBN = 4 * (32 + 16 * NB1);
-  const int tiles_m = (int)(M / TBM), tiles_n = (int)(N / TBN);
-  // one_tile_per_wg (algo 5): same kernel, one workgroup per tile, so the hardware dispatcher balances the tiles over whatever
-  // CUs are free -- the form to use while other kernels (RCCL collectives) hold part of the chip
-  int grid = (one_tile_per_wg || tiles_m * tiles_n < num_cus()) ? tiles_m * tiles_n : num_cus();
+// ------------------------------------------------------------------------------------------------
+// What an algo id means, once.  plan_gemm below is the only reader.
+enum ShapeClass { kAnyShape, kFastOk, kP8Ok, kP8Ok256 };  // what each asks: fast_ok, p8_ok, p8_ok_256 and kNeeds in plan_gemm
+constexpr int kPick = -1;     // tile_cfg: pick_tile_cfg decides
+constexpr int kCfgById = -2;  // tile_cfg: id - lo (the ids of such a range count up in tile shape, not in build)
+constexpr int kNoBuild = -1;  // ids inside a lab range that no lab build defines
+
+struct AlgoRow {
+  int lo, hi;  // the ids the row stands for; where two rows hold an id, the first one counts
+  int family, build, sched, tile_cfg;  // build: ABL of id `lo`, the ids of a range count up from it; sched: S
+  bool one_tile_per_wg;
+  bool lab;  // timing / ablation / stamp build: lab library only
+  ShapeClass shape;
+  bool mx_ok;     // may run block-scaled (mi_gemm_mxfp8)
+  BiasUse bias;   // what its builds do with a bias argument, unless they take a stamp buffer in its place (plan_gemm)
+  bool e4m3_only;
+};
+
+constexpr AlgoRow kAlgos[] = {
+    // ids     family       build sched cfg    1/wg lab shape     mx bias          e4m3
+    {1, 1,   kFamGeneric, 0,  0, kPick,    0, 0, kAnyShape, 1, kBiasAdded,   0},
+    {2, 2,   kFam2Phase,  0,  0, kPick,    0, 0, kFastOk,   0, kBiasAdded,   0},
+    {3, 3,   kFam8Phase,  0,  0, kPick,    0, 0, kFastOk,   0, kBiasAdded,   0},
+    {4, 4,   kFamP8,      0,  0, kPick,    0, 0, kP8Ok,     1, kBiasAdded,   0},
+    // 5: the kernel of 4, one workgroup per tile, so the hardware dispatcher balances the tiles over whatever CUs are free -- the
+    // form to use while other kernels (RCCL collectives) hold part of the chip
+    {5, 5,   kFamP8,      0,  0, kPick,    1, 0, kP8Ok,     1, kBiasAdded,   0},
+    // four-wave kernels (mi_gemm_w4.hip).  Of them only the persistent product build takes a bias.
+    {6, 6,   kFamW4,      0,  0, 0,        1, 0, kP8Ok256,  0, kBiasRefused, 0},
+    // 7: no stores; 8: clock stamps, u64[4 * tiles]
+    {7, 8,   kFamW4,      1,  0, 0,        1, 1, kP8Ok256,  0, kBiasRefused, 0},
+    {9, 9,   kFamW4P,     0,  0, 0,        0, 0, kP8Ok256,  0, kBiasAdded,   0},
+    // 10: no stores; 11: clock stamps, u64[4 * grid]: mi_gemm_fp8_clock's build for algo 9; 12: no epilogue
+    {10, 12, kFamW4P,     1,  0, 0,        0, 1, kP8Ok256,  0, kBiasRefused, 1},
+    // eight-phase kernel: 13 no stores, 14 stamps, u64[2 * tiles] (cycles, 100 MHz ticks)
+    {13, 14, kFam8Phase,  1,  0, kPick,    0, 1, kFastOk,   0, kBiasAdded,   0},
+    // timing / diagnostic builds of the persistent eight-wave kernel, ABL 1, 3-9 and 11-17 (no algo 23, no ABL 10):
+    // 15: no stores; 16: start stagger (MI_GEMM_STAGGER); 17: plain (write-back) stores
+    // 18, 19: the MX scale path without its effect.  They read the block scales, so they exist for mi_gemm_mxfp8 only -- through
+    // mi_gemm_fp8 the scale pointers are null and the kernel faults (it did once, from a sweep script).  Wrong results both:
+    // 18 stages the block scales into LDS but does not read them (unit scales); 19 reads them too, the MFMAs still get unit scales
+    // 20: every tile reads the operand panels of tile (0, 0) (L2-resident): wrong results
+    // 21: u64[4 * grid] (cycles, 100 MHz ticks, steps, XCC id): mi_gemm_fp8_clock's build for algo 4
+    // 22: u64[2048]: per-phase s_memtime stamps of waves 0 and 4 of workgroup 0
+    // 24: A/B baseline: half-line epilogue stores (16 rows x 64 B per instruction); 25: nt (streaming) stores; 26: sc1 + nt stores
+    // 27: epilogue woven into the MFMA segments (timing A/B)
+    // 28: no epilogue at all (timing only): what conversion + stores cost together
+    // 29: conversion woven into the MFMA segments, stores one load segment later (timing A/B); needs K >= 512
+    // 30: odd tiles walk K downwards (L2 reuse across tile boundaries; fp32 summation order differs per tile parity)
+    {15, 15, kFamP8,      1,  0, kPick,    0, 1, kP8Ok,     0, kBiasUnused,  1},
+    {16, 22, kFamP8,      3,  0, kPick,    0, 1, kP8Ok,     0, kBiasUnused,  1},
+    {23, 23, kFamP8, kNoBuild, 0, kPick,   0, 1, kP8Ok,     0, kBiasUnused,  1},
+    {24, 30, kFamP8,      11, 0, kPick,    0, 1, kP8Ok,     0, kBiasUnused,  1},
+    {40, 43, kFamP8,      0,  0, kCfgById, 0, 0, kP8Ok,     1, kBiasAdded,   0},
+    // 44: stream-K on 256x256 tiles (needs a registered workspace).  It is NOT part of the automatic choice: measured
+    // (interleaved A/B) it loses 3-15 % to the best whole-tile shape at K <= 8192 and wins 3.5 % only at K = 16384 -- the chip
+    // is power-limited, so a half-empty last round costs less than its CU count suggests (the busy CUs clock higher) while the
+    // partial-accumulator traffic is extra energy.  45 = the whole-tile picker (same as 4).
+    {44, 44, kFamStreamK, 0,  0, 0,        0, 0, kP8Ok,     1, kBiasAdded,   0},
+    {45, 45, kFamP8,      0,  0, kPick,    0, 0, kP8Ok,     1, kBiasAdded,   0},
+    // 46: A/B baseline: block epilogue after each tile (the round-1 form)
+    {46, 46, kFamP8, kP8BlockEpilogue, 0, kPick, 0, 1, kP8Ok, 0, kBiasUnused, 1},
+    // four-wave kernel schedule sweep: 50 + 4 S + {0: product, 1: no stores, 2: stamps}; S = 1, 3, 4 are built, the other ids of
+    // 50-69 fall to the last row
+    {54, 56, kFamW4,      0,  1, 0,        1, 1, kP8Ok256,  0, kBiasUnused,  1},
+    {62, 64, kFamW4,      0,  3, 0,        1, 1, kP8Ok256,  0, kBiasUnused,  1},
+    {66, 68, kFamW4,      0,  4, 0,        1, 1, kP8Ok256,  0, kBiasUnused,  1},
+    {50, 69, kFamW4, kNoBuild, 0, 0,       1, 1, kP8Ok256,  0, kBiasUnused,  1},
+    // persistent four-wave kernel, epilogue store policy: 70 plain, 71 nt, 72 sc1 + nt; 73: per-K-tile stamps
+    {70, 73, kFamW4P,     4,  0, 0,        0, 1, kP8Ok256,  0, kBiasUnused,  1},
+};
+
 #ifdef MI_DIAG
-  if ((ABL == 3 || ABL == 8 || ABL == 9) && getenv("MI_GEMM_GRID")) grid = std::max(1, std::min(grid, atoi(getenv("MI_GEMM_GRID"))));  // experiment knob
-  const int stagger = ((ABL == 3) && getenv("MI_GEMM_STAGGER")) ? atoi(getenv("MI_GEMM_STAGGER")) : 0;  // experiment knob (algo 16)
+constexpr bool kLabLibrary = true;
 #else
-  const int stagger = 0;
+constexpr bool kLabLibrary = false;
 #endif
-  hipLaunchKernelGGL((gemm_256_p8<FA, FB, ABL, MX, BIAS, MA1, NB1, false, DEPI>), dim3(grid), dim3(512), 0, st, a, b, D, sa_inv, sb_inv, (int)K,
-                     (int)lda, (int)ldb, (int)ldd, tiles_m, tiles_n, (int)(M * lda), (int)(N * ldb), (int)(M * ldd * 2), SA, SB,
-                     (int)M, (int)N, bias, (float*)nullptr, (unsigned int*)nullptr, 0u, stagger);
+
+enum GemmEntry { kEntryFp8 = 0, kEntryMx, kEntryClock };
+static const char* const kWho[] = {"mi_gemm_fp8", "mi_gemm_mxfp8", "mi_gemm_fp8_clock"};
+
+// Entry point + shape + algo -> plan, or a refusal (return code + mi_last_error text).  Launches nothing, touches no operand.
+// Runs after check_common and the entry point's null-pointer checks.
+static int plan_gemm(int entry, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldd, int fa, int fb, int out,
+                     bool has_bias, int algo, GemmPlan& p) {
+  const bool mx = entry == kEntryMx, e4m3 = fa == 0 && fb == 0;
+  auto find = [](int id) -> const AlgoRow* {
+    for (const AlgoRow& r : kAlgos)
+      if (id >= r.lo && id <= r.hi) return &r;
+    return nullptr;
+  };
+  auto build_of = [](const AlgoRow& r, int id) { return r.build == kNoBuild || r.tile_cfg == kCfgById ? r.build : r.build + (id - r.lo); };
+  // ABL 5 and 6 of the persistent eight-wave kernel read MXFP8 block scales: they run block-scaled, and only so
+  auto mx_only = [](const AlgoRow& r, int build) { return r.family == kFamP8 && (build == 5 || build == 6); };
+  p = GemmPlan{};
+  if (mx) {
+    MI_CHECK_ARG(K % 32 == 0, "mi_gemm_mxfp8: K must be a multiple of 32");
+    const AlgoRow* r = find(algo);
+    const bool listed = r && (r->mx_ok || mx_only(*r, build_of(*r, algo))) && (kLabLibrary || !r->lab);
+    MI_CHECK_ARG(algo == 0 || listed, "mi_gemm_mxfp8: algo must be 0, 1, 4, 5%s or 40-45", kLabLibrary ? ", 18, 19" : "");
+  }
+  if (entry == kEntryClock) MI_CHECK_ARG(algo == 0 || algo == 4 || algo == 9, "mi_gemm_fp8_clock: algo must be 0, 4 or 9");
+  if (M == 0 || N == 0) return MI_OK;  // before the algo is looked at
+
+  const bool fast_ok = (M % BM == 0) && (N % BN == 0) && (K % BK == 0) && K > 0;
+  // persistent kernels: even K-tile count, bf16 output, 32-bit buffer offsets
+  const bool p8_ok = (M % 256 == 0 || M % 192 == 0) && (N % 256 == 0 || N % 192 == 0) && K > 0 && (K % (2 * BK) == 0) &&
+                     out == 0 && M * lda < (1LL << 31) && N * ldb < (1LL << 31) && M * ldd * 2 < (1LL << 31);
+  const bool p8_ok_256 = p8_ok && M % 256 == 0 && N % 256 == 0;
+  const int ncu = num_cus();
+  const int64_t tiles_256 = (M / 256) * (N / 256);
+  if (algo == 47) {
+    // auto, four-wave kernel where it is the faster one (measured, profiles/r03_w4p_*): 256-multiples, K >= 512, and the
+    // eight-wave kernel's own tile-shape choice is 256 x 256 (where it prefers 192-wide tiles the round count decides)
+    algo = (p8_ok_256 && K >= 512 && pick_tile_cfg(M, N, K) == 0 && (tiles_256 + ncu - 1) / ncu <= 64) ? 9 : 0;
+  }
+  if (algo == 0) algo = p8_ok ? 4 : ((fast_ok && !mx) ? 3 : 1);  // block-scaled: the persistent kernel or the generic one
+  MI_CHECK_SHAPE(entry != kEntryClock || algo == 4 || algo == 9, "mi_gemm_fp8_clock: the shape does not run on a persistent kernel");
+  const AlgoRow* r = find(algo);
+  MI_CHECK_ARG(r == nullptr || !r->lab || kLabLibrary,
+               "%s: algo %d is a timing / diagnostic build; it lives in the lab library (make -C llm_fp8_amd/csrc lab)", kWho[entry], algo);
+  MI_CHECK_ARG(r != nullptr, "%s: unknown algo %d", kWho[entry], algo);
+  const bool shape_ok[] = {true, fast_ok, p8_ok, p8_ok_256};  // by ShapeClass
+  static const char* const kNeeds[] = {"", "M,N % 256 == 0 and K % 128 == 0",
+                                       "M,N % 256 (or 192) == 0, K % 256 == 0, bf16 output, operands < 2 GiB",
+                                       "M,N,K % 256 == 0, bf16 output, operands < 2 GiB"};
+  MI_CHECK_SHAPE(shape_ok[r->shape], "%s: algo %d needs %s", kWho[entry], algo, kNeeds[r->shape]);
+  p.algo = algo;
+  p.family = r->family;
+  p.build = build_of(*r, algo);
+  if (entry == kEntryClock) p.build = r->family == kFamP8 ? 8 : 2;  // the stamped build of the production kernel
+  // the builds that take a u64 stamp buffer where the others take a bias
+  const bool stamps = r->family == kFamP8    ? p.build == 8 || p.build == 9
+                      : r->family == kFamW4P ? p.build == 2 || p.build == 7
+                                             : (r->family == kFamW4 || r->family == kFam8Phase) && p.build == 2;
+  MI_CHECK_ARG(!has_bias || stamps || r->bias != kBiasRefused,
+               "mi_gemm: of the four-wave kernels only the persistent one (algo 9) takes a bias (got algo %d)", algo);
+  p.sched = r->sched;
+  p.mx = mx;
+  p.tile_cfg = r->tile_cfg == kCfgById ? algo - r->lo : r->tile_cfg;  // kPick: chosen below; the generic kernel has no tiles
+  p.tiles_m = (int)(M / 256);
+  p.tiles_n = (int)(N / 256);
+  p.one_tile_per_wg = r->one_tile_per_wg;
+  p.bias_use = stamps ? kBiasIsStamps : (r->bias == kBiasAdded && has_bias) ? kBiasAdded : kBiasUnused;
+  p.grid_x = (int)tiles_256;
+  p.grid_y = 1;
+  p.block = (r->family == kFamGeneric || r->family == kFamW4 || r->family == kFamW4P) ? 256 : 512;
+  // the four-wave lab refusals keep the numbers the launcher once gave its builds: 10 + ABL persistent, 20 + offset into the sweep
+  const int w4_number = r->family == kFamW4P ? 10 + p.build : 20 + (algo - 50);
+
+  switch (r->family) {
+    case kFamGeneric:
+      p.grid_x = (int)((N + 63) / 64);
+      p.grid_y = (int)((M + 63) / 64);
+      break;
+    case kFamStreamK:
+      p.sk_units = sk_units(M, N, K);
+      MI_CHECK_SHAPE(p.sk_units > 0, "mi_gemm: stream-K needs a registered workspace, 256-aligned M/N/K and more tiles than CUs (%lld x %lld x %lld)",
+                     (long long)M, (long long)N, (long long)K);
+      p.grid_x = (int)((tiles_256 * (K / BK) + p.sk_units - 1) / p.sk_units);
+      break;
+    case kFamP8: {
+      const int cfg = p.tile_cfg == kPick ? pick_tile_cfg(M, N, K) : p.tile_cfg;
+      MI_CHECK_SHAPE(cfg >= 0 && M % kTileBm[cfg] == 0 && N % kTileBn[cfg] == 0, "mi_gemm: no persistent tile shape divides %lld x %lld",
+                     (long long)M, (long long)N);
+      MI_CHECK_ARG(e4m3 || !r->e4m3_only, "mi_gemm: diagnostic algo %d is built for E4M3 x E4M3 only", algo);
+      MI_CHECK_ARG(p.build != kNoBuild, "mi_gemm: unknown diagnostic algo %d", algo);
+      MI_CHECK_SHAPE(p.build != 16 || K >= 512, "mi_gemm: algo %d needs K >= 512", algo);  // ABL 16 delays its stores by a segment
+      MI_CHECK_ARG(mx || !mx_only(*r, p.build), "mi_gemm: diagnostic algo %d reads MXFP8 block scales: call it through mi_gemm_mxfp8",
+                   algo);
+      p.tile_cfg = cfg;
+      p.tiles_m = (int)(M / kTileBm[cfg]);
+      p.tiles_n = (int)(N / kTileBn[cfg]);
+      const int tiles = p.tiles_m * p.tiles_n;
+      p.grid_x = (r->one_tile_per_wg || tiles < ncu) ? tiles : ncu;
+#ifdef MI_DIAG
+      if ((p.build == 3 || p.build == 8 || p.build == 9) && getenv("MI_GEMM_GRID"))
+        p.grid_x = std::max(1, std::min(p.grid_x, atoi(getenv("MI_GEMM_GRID"))));  // experiment knob
+#endif
+      break;
+    }
+    case kFamW4:
+      MI_CHECK_ARG(e4m3 || !r->e4m3_only, "mi_gemm (w4): variant %d is a timing build of the lab library", w4_number);
+      MI_CHECK_ARG(p.build != kNoBuild, "mi_gemm (w4): no such schedule variant %d", w4_number);
+      break;
+    case kFamW4P:
+      p.grid_x = (int)(tiles_256 < ncu ? tiles_256 : ncu);
+      MI_CHECK_SHAPE((tiles_256 + p.grid_x - 1) / p.grid_x <= 64 && K >= 512 && M / 256 < 16384 && N / 256 < 16384,
+                     "mi_gemm (w4 persistent): needs K >= 512, at most 64 tiles per workgroup and fewer than 16384 tiles per dimension");
+      MI_CHECK_ARG(e4m3 || p.build != 2, "mi_gemm (w4): the clock-stamp build is E4M3 x E4M3 only");
+      MI_CHECK_ARG(e4m3 || !r->e4m3_only, "mi_gemm (w4): timing variant %d is built for E4M3 x E4M3 only", w4_number);
+      break;
+  }
+  return MI_OK;  // kFam2Phase, kFam8Phase: one workgroup per 256 x 256 tile, nothing more to ask
 }
 
-template <int FA, int FB, bool MX, bool BIAS>
-static void launch_p8_sk(const uint8_t* a, const uint8_t* b, uint16_t* D, const float* sa_inv, const float* sb_inv,
-                         const uint8_t* SA, const uint8_t* SB, const uint16_t* bias, int64_t M, int64_t N, int64_t K,
-                         int64_t lda, int64_t ldb, int64_t ldd, int U, hipStream_t st) {
-  const int tiles_m = (int)(M / 256), tiles_n = (int)(N / 256);
-  const int64_t total = (int64_t)tiles_m * tiles_n * (K / BK);
-  const int grid = (int)((total + U - 1) / U);
-  const SkWorkspace* ws = sk_workspace();
-  const unsigned int epoch = g_sk_epoch.fetch_add(1);
-  hipLaunchKernelGGL((gemm_256_p8<FA, FB, 0, MX, BIAS, 4, 2, true>), dim3(grid), dim3(512), 0, st, a, b, D, sa_inv, sb_inv, (int)K,
-                     (int)lda, (int)ldb, (int)ldd, tiles_m, tiles_n, (int)(M * lda), (int)(N * ldb), (int)(M * ldd * 2), SA, SB,
-                     (int)M, (int)N, bias, ws->slots, ws->flags, epoch == 0 ? g_sk_epoch.fetch_add(1) : epoch, U);
-}
+// ------------------------------------------------------------------------------------------------
+// Plan + operands -> launch.  Refuses nothing; a failed launch is MI_ERR_HIP.
 
-template <int FA, int FB>
-static int launch_p8(const uint8_t* a, const uint8_t* b, uint16_t* D, const float* sa_inv, const float* sb_inv,
-                     const uint8_t* SA, const uint8_t* SB, const uint16_t* bias, int64_t M, int64_t N, int64_t K, int64_t lda,
-                     int64_t ldb, int64_t ldd, int algo, bool mx, hipStream_t st, void* clock_stamps = nullptr) {
-  // algo 44: stream-K on 256x256 tiles (needs a registered workspace).  It is NOT part of the automatic choice: measured
-  // (interleaved A/B) it loses 3-15 % to the best whole-tile shape at K <= 8192 and wins 3.5 % only at K = 16384 -- the chip
-  // is power-limited, so a half-empty last round costs less than its CU count suggests (the busy CUs clock higher) while the
-  // partial-accumulator traffic is extra energy.  45 = the whole-tile picker (same as 4).
-  if (algo == 44) {
-    const int U = sk_units(M, N, K, algo == 44);
-    if (U > 0) {
-      if (mx) {
-        if (bias) launch_p8_sk<FA, FB, true, true>(a, b, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, U, st);
-        else launch_p8_sk<FA, FB, true, false>(a, b, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, U, st);
-      } else {
-        if (bias) launch_p8_sk<FA, FB, false, true>(a, b, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, U, st);
-        else launch_p8_sk<FA, FB, false, false>(a, b, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, U, st);
-      }
-      MI_CHECK_LAUNCH("mi_gemm (stream-K) launch");
-      return MI_OK;
-    }
-    if (algo == 44) {
-      set_error("mi_gemm: stream-K needs a registered workspace, 256-aligned M/N/K and more tiles than CUs (%lld x %lld x %lld)",
-                (long long)M, (long long)N, (long long)K);
-      return MI_ERR_SHAPE;
-    }
-  }
-  int cfg = (algo >= 40 && algo <= 43) ? algo - 40 : pick_tile_cfg(M, N, K);
-  if (cfg < 0 || M % kTileBm[cfg] || N % kTileBn[cfg]) {
-    set_error("mi_gemm: no persistent tile shape divides %lld x %lld", (long long)M, (long long)N);
-    return MI_ERR_SHAPE;
-  }
-#define MI_P8(MXv, BIASv, ABLv, MA1v, NB1v) \
-  launch_p8_cfg<FA, FB, MXv, BIASv, ABLv, MA1v, NB1v>(a, b, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, st, algo == 5)
-#define MI_P8_CFG(MXv, BIASv, ABLv)                                 \
-  switch (cfg) {                                                    \
-    case 0: MI_P8(MXv, BIASv, ABLv, 4, 2); break;                   \
-    case 1: MI_P8(MXv, BIASv, ABLv, 4, 1); break;                   \
-    case 2: MI_P8(MXv, BIASv, ABLv, 2, 2); break;                   \
-    default: MI_P8(MXv, BIASv, ABLv, 2, 1); break;                  \
-  }
+// The builds of gemm_256_p8 beside the product one (ABL 0: every format pair, MX x BIAS), once: X(ABL, MX).  E4M3 x E4M3, no
+// bias.  ABL 8 is in both libraries (mi_gemm_fp8_clock); kAlgos says what each of the others is.
 #ifdef MI_DIAG
-  if (algo == 46 || (algo >= 15 && algo <= 30)) {  // timing-only / diagnostic builds: E4M3 x E4M3 only (compile time)
-    if constexpr (FA == 0 && FB == 0) {
-      if (algo == 46) {  // A/B baseline: block epilogue after each tile (the round-1 form)
-        switch (cfg) {
-          case 0: launch_p8_cfg<FA, FB, false, false, 0, 4, 2, false>(a, b, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, st); break;
-          case 1: launch_p8_cfg<FA, FB, false, false, 0, 4, 1, false>(a, b, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, st); break;
-          case 2: launch_p8_cfg<FA, FB, false, false, 0, 2, 2, false>(a, b, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, st); break;
-          default: launch_p8_cfg<FA, FB, false, false, 0, 2, 1, false>(a, b, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, st); break;
-        }
-      } else if (algo == 15) {  // no stores
-        MI_P8_CFG(false, false, 1)
-      } else if (algo == 16) {  // start stagger (MI_GEMM_STAGGER)
-        MI_P8_CFG(false, false, 3)
-      } else if (algo == 17) {  // plain (write-back) stores
-        MI_P8_CFG(false, false, 4)
-      } else if (algo == 20) {  // every tile reads the operand panels of tile (0, 0) (L2-resident): wrong results
-        MI_P8_CFG(false, false, 7)
-      } else if (algo == 22) {  // `bias` is a u64[2048] buffer: per-phase s_memtime stamps of waves 0 and 4 of workgroup 0
-        MI_P8_CFG(false, false, 9)
-      } else if (algo == 21) {  // `bias` is a u64[4 * grid] stamp buffer (cycles, 100 MHz ticks, steps, XCC id)
-        MI_P8_CFG(false, false, 8)
-      } else if (algo == 30) {  // odd tiles walk K downwards (L2 reuse across tile boundaries; fp32 summation order differs per tile parity)
-        MI_P8_CFG(false, false, 17)
-      } else if (algo == 29) {  // conversion woven into the MFMA segments, stores one load segment later (timing A/B; K >= 512)
-        if (K < 512) { set_error("mi_gemm: algo 29 needs K >= 512"); return MI_ERR_SHAPE; }
-        MI_P8_CFG(false, false, 16)
-      } else if (algo == 28) {  // no epilogue at all (timing only): what conversion + stores cost together
-        MI_P8_CFG(false, false, 15)
-      } else if (algo == 27) {  // epilogue woven into the MFMA segments (timing A/B)
-        MI_P8_CFG(false, false, 14)
-      } else if (algo == 25) {  // nt (streaming) stores
-        MI_P8_CFG(false, false, 12)
-      } else if (algo == 26) {  // sc1 + nt stores
-        MI_P8_CFG(false, false, 13)
-      } else if (algo == 24) {  // A/B baseline: half-line epilogue stores (16 rows x 64 B per instruction)
-        MI_P8_CFG(false, false, 11)
-      } else if (algo == 18 || algo == 19) {
-        // (lab) the MX scale path without its effect: they read the block scales, so they exist for mi_gemm_mxfp8 only -- through
-        // mi_gemm_fp8 the scale pointers are null and the kernel faults (it did once, from a sweep script)
-        if (SA == nullptr || SB == nullptr) {
-          set_error("mi_gemm: diagnostic algo %d reads MXFP8 block scales: call it through mi_gemm_mxfp8", algo);
-          return MI_ERR_ARG;
-        }
-        if (algo == 18) {  // block scales staged into LDS but not read (unit scales): wrong results
-          MI_P8_CFG(true, false, 5)
-        } else {  // block scales staged and read, MFMAs still get unit scales: wrong results
-          MI_P8_CFG(true, false, 6)
-        }
-      } else {
-        set_error("mi_gemm: unknown diagnostic algo %d", algo);
-        return MI_ERR_ARG;
-      }
-    } else {
-      set_error("mi_gemm: diagnostic algo %d is built for E4M3 x E4M3 only", algo);
-      return MI_ERR_ARG;
-    }
-  } else
+#define MI_P8_BUILDS_E4M3(X)                                                                                               \
+  X(1, false) X(3, false) X(4, false) X(5, true) X(6, true) X(7, false) X(8, false) X(9, false) X(11, false) X(12, false) \
+  X(13, false) X(14, false) X(15, false) X(16, false) X(17, false) X(kP8BlockEpilogue, false)
 #else
-  if (algo == 46 || (algo >= 15 && algo <= 30)) {
-    set_error("mi_gemm: algo %d is a timing / diagnostic build; it lives in the lab library (make -C llm_fp8_amd/csrc lab)", algo);
-    return MI_ERR_ARG;
-  } else
+#define MI_P8_BUILDS_E4M3(X) X(8, false)
 #endif
-  if (clock_stamps != nullptr) {  // mi_gemm_fp8_clock: the production kernel's stamped build (E4M3 x E4M3 only)
-    if constexpr (FA == 0 && FB == 0) {
-      bias = (const uint16_t*)clock_stamps;
-      MI_P8_CFG(false, false, 8)
-    } else {
-      set_error("mi_gemm_fp8_clock: built for E4M3 x E4M3 only");
-      return MI_ERR_ARG;
-    }
-  } else if (mx) {
-    if (bias) { MI_P8_CFG(true, true, 0) } else { MI_P8_CFG(true, false, 0) }
+
+template <int FA, int FB, bool MX, bool BIAS, int ABL, bool DEPI = true, bool SK = false>
+static void launch_p8_build(const GemmPlan& p, const GemmArgs& g) {
+  const SkWorkspace* ws = SK ? sk_workspace() : nullptr;
+  unsigned int epoch = SK ? g_sk_epoch.fetch_add(1) : 0u;
+  if (SK && epoch == 0) epoch = g_sk_epoch.fetch_add(1);
+  int last = p.sk_units;  // the kernel's last argument: stream-K units, else the start stagger
+#ifdef MI_DIAG
+  if (ABL == 3 && getenv("MI_GEMM_STAGGER")) last = atoi(getenv("MI_GEMM_STAGGER"));  // experiment knob (algo 16)
+#endif
+#define MI_P8_TILE(MA1, NB1)                                                                                                    \
+  hipLaunchKernelGGL((gemm_256_p8<FA, FB, ABL, MX, BIAS, MA1, NB1, SK, DEPI>), dim3(p.grid_x), dim3(p.block), 0, g.st, g.A, g.B, \
+                     (uint16_t*)g.D, g.sa_inv, g.sb_inv, (int)g.K, (int)g.lda, (int)g.ldb, (int)g.ldd, p.tiles_m, p.tiles_n,     \
+                     (int)(g.M * g.lda), (int)(g.N * g.ldb), (int)(g.M * g.ldd * 2), g.SA, g.SB, (int)g.M, (int)g.N,             \
+                     (const uint16_t*)g.bias, SK ? ws->slots : nullptr, SK ? ws->flags : nullptr, epoch, last)
+  if constexpr (SK) {
+    MI_P8_TILE(4, 2);
   } else {
-    if (bias) { MI_P8_CFG(false, true, 0) } else { MI_P8_CFG(false, false, 0) }
+    switch (p.tile_cfg) {
+      case 0: MI_P8_TILE(4, 2); break;
+      case 1: MI_P8_TILE(4, 1); break;
+      case 2: MI_P8_TILE(2, 2); break;
+      default: MI_P8_TILE(2, 1); break;
+    }
   }
-#undef MI_P8_CFG
-#undef MI_P8
-  MI_CHECK_LAUNCH("mi_gemm (persistent) launch");
+#undef MI_P8_TILE
+}
+
+// families kFamP8 and kFamStreamK
+template <int FA, int FB>
+static int launch_p8(const GemmPlan& p, const GemmArgs& g) {
+  if (p.build != 0 && (FA != 0 || FB != 0)) MI_NOT_COMPILED(p);
+  switch (p.build) {
+    case 0:
+      with_pair(p.mx, p.bias_use == kBiasAdded, [&](auto mx, auto bias) {
+        if (p.family == kFamStreamK) launch_p8_build<FA, FB, mx() != 0, bias() != 0, 0, true, true>(p, g);
+        else launch_p8_build<FA, FB, mx() != 0, bias() != 0, 0>(p, g);
+        return 0;
+      });
+      break;
+#define MI_P8_BUILD(ABLv, MXv) \
+  case ABLv: launch_p8_build<0, 0, MXv, false, (ABLv == kP8BlockEpilogue ? 0 : ABLv), ABLv != kP8BlockEpilogue>(p, g); break;
+      MI_P8_BUILDS_E4M3(MI_P8_BUILD)
+#undef MI_P8_BUILD
+    default: MI_NOT_COMPILED(p);
+  }
+  MI_CHECK_LAUNCH(p.family == kFamStreamK ? "mi_gemm (stream-K) launch" : "mi_gemm (persistent) launch");
   return MI_OK;
 }
 
+// the kernels that also write fp32: generic, 2-phase, 8-phase (builds of it: 1 = no stores, 2 = stamps)
 template <int FA, int FB, int OUT>
-static int launch_fmt(const void* A, const void* B, void* D, const float* sa_inv, const float* sb_inv,
-                      const void* SA, const void* SB, const void* bias, int64_t M, int64_t N, int64_t K,
-                      int64_t lda, int64_t ldb, int64_t ldd, int algo, bool mx, hipStream_t st, void* clock_stamps = nullptr) {
-  const uint8_t *a = (const uint8_t*)A, *b = (const uint8_t*)B;
-  const uint16_t* bp = (const uint16_t*)bias;
-  if (algo == 2 && !mx) {
-    int tiles_m = (int)(M / BM), tiles_n = (int)(N / BN);
-    hipLaunchKernelGGL((gemm_256_2ph<FA, FB, OUT>), dim3(tiles_m * tiles_n), dim3(512), 0, st, a, b, D, sa_inv, sb_inv,
-                       bp, (int)M, (int)N, (int)K, lda, ldb, ldd, tiles_m, tiles_n);
-  } else if (algo == 3 && !mx) {
-    int tiles_m = (int)(M / BM), tiles_n = (int)(N / BN);
-    hipLaunchKernelGGL((gemm_256_8ph<FA, FB, OUT>), dim3(tiles_m * tiles_n), dim3(512), 0, st, a, b, D, sa_inv, sb_inv,
-                       bp, (int)M, (int)N, (int)K, lda, ldb, ldd, tiles_m, tiles_n);
-  } else if (algo == 4 || algo == 5 || (algo >= 15 && algo <= 30) || (algo >= 40 && algo <= 46)) {
-    return launch_p8<FA, FB>(a, b, (uint16_t*)D, sa_inv, sb_inv, (const uint8_t*)SA, (const uint8_t*)SB, bp, M, N, K, lda, ldb, ldd,
-                             algo, mx, st, clock_stamps);
-  } else if (algo >= 6 && algo <= 12 && !mx) {
-    // four-wave kernel (mi_gemm_w4.hip): one tile per workgroup 6 = product, 7 = no stores, 8 = clock stamps; persistent
-    // 9 = product, 10 = no stores, 11 = clock stamps, 12 = no epilogue (7, 8, 10-12: lab library only)
-    const int variant = algo <= 8 ? algo - 6 : algo + 1;
-    if (bp != nullptr && algo != 8 && algo != 9 && algo != 11) {
-      set_error("mi_gemm: of the four-wave kernels only the persistent one (algo 9) takes a bias (got algo %d)", algo);
-      return MI_ERR_ARG;
-    }
-    if (clock_stamps != nullptr) return launch_w4(A, B, D, sa_inv, sb_inv, M, N, K, lda, ldb, ldd, FA, FB, 12, clock_stamps, st);
-    return launch_w4(A, B, D, sa_inv, sb_inv, M, N, K, lda, ldb, ldd, FA, FB, variant, (algo == 8 || algo == 11) ? (void*)bias : nullptr, st,
-                     algo == 9 ? (const void*)bp : nullptr);
+static int launch_plain(const GemmPlan& p, const GemmArgs& g) {
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  const uint16_t* bias = (const uint16_t*)g.bias;
+#define MI_TILED(kernel)                                                                                                  \
+  hipLaunchKernelGGL(kernel, grid, block, 0, g.st, g.A, g.B, g.D, g.sa_inv, g.sb_inv, bias, (int)g.M, (int)g.N, (int)g.K, \
+                     g.lda, g.ldb, g.ldd, p.tiles_m, p.tiles_n)
+#define MI_GENERIC(MXv)                                                                                                    \
+  hipLaunchKernelGGL((gemm_generic<FA, FB, OUT, MXv>), grid, block, 0, g.st, g.A, g.B, g.D, g.sa_inv, g.sb_inv, g.SA, g.SB, \
+                     bias, (int)g.M, (int)g.N, (int)g.K, g.lda, g.ldb, g.ldd)
+  switch (p.family * 4 + p.build) {
+    case kFamGeneric * 4: if (p.mx) MI_GENERIC(true); else MI_GENERIC(false); break;
+    case kFam2Phase * 4: MI_TILED((gemm_256_2ph<FA, FB, OUT>)); break;
+    case kFam8Phase * 4: MI_TILED((gemm_256_8ph<FA, FB, OUT>)); break;
 #ifdef MI_DIAG
-  } else if (algo >= 70 && algo <= 73 && !mx) {  // persistent four-wave kernel, epilogue store policy: 70 plain, 71 nt, 72 sc1 + nt; 73: per-K-tile stamps
-    return launch_w4(A, B, D, sa_inv, sb_inv, M, N, K, lda, ldb, ldd, FA, FB, algo - 56, algo == 73 ? (void*)bias : nullptr, st);
-  } else if (algo >= 50 && algo < 70 && !mx) {  // four-wave kernel schedule sweep: 50 + 4 S + {0: product, 1: no stores, 2: stamps}
-    return launch_w4(A, B, D, sa_inv, sb_inv, M, N, K, lda, ldb, ldd, FA, FB, algo - 30, (algo % 4) == 0 ? (void*)bias : nullptr, st);
-  } else if (algo == 13 && !mx) {
-    int tiles_m = (int)(M / BM), tiles_n = (int)(N / BN);
-    hipLaunchKernelGGL((gemm_256_8ph<FA, FB, OUT, 1>), dim3(tiles_m * tiles_n), dim3(512), 0, st, a, b, D, sa_inv, sb_inv,
-                       bp, (int)M, (int)N, (int)K, lda, ldb, ldd, tiles_m, tiles_n);
-  } else if (algo == 14 && !mx) {  // diagnostic: `bias` is a u64[2 * tiles] debug buffer (cycles, 100 MHz ticks)
-    int tiles_m = (int)(M / BM), tiles_n = (int)(N / BN);
-    hipLaunchKernelGGL((gemm_256_8ph<FA, FB, OUT, 2>), dim3(tiles_m * tiles_n), dim3(512), 0, st, a, b, D, sa_inv, sb_inv,
-                       bp, (int)M, (int)N, (int)K, lda, ldb, ldd, tiles_m, tiles_n);
+    case kFam8Phase * 4 + 1: MI_TILED((gemm_256_8ph<FA, FB, OUT, 1>)); break;
+    case kFam8Phase * 4 + 2: MI_TILED((gemm_256_8ph<FA, FB, OUT, 2>)); break;
 #endif
-  } else {
-    dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
-    if (mx)
-      hipLaunchKernelGGL((gemm_generic<FA, FB, OUT, true>), grid, dim3(256), 0, st, a, b, D, sa_inv, sb_inv,
-                         (const uint8_t*)SA, (const uint8_t*)SB, bp, (int)M, (int)N, (int)K, lda, ldb, ldd);
-    else
-      hipLaunchKernelGGL((gemm_generic<FA, FB, OUT, false>), grid, dim3(256), 0, st, a, b, D, sa_inv, sb_inv,
-                         (const uint8_t*)SA, (const uint8_t*)SB, bp, (int)M, (int)N, (int)K, lda, ldb, ldd);
+    default: MI_NOT_COMPILED(p);
   }
+#undef MI_GENERIC
+#undef MI_TILED
   MI_CHECK_LAUNCH("mi_gemm launch");
   return MI_OK;
 }
 
-static int dispatch(const void* A, const void* B, void* D, const float* sa_inv, const float* sb_inv, const void* SA,
-                    const void* SB, const void* bias, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
-                    int64_t ldd, int fa, int fb, int out, int algo, bool mx, hipStream_t st, void* clock_stamps = nullptr) {
-#define MI_CASE(FA_, FB_, OUT_)                                                                               \
-  if (fa == FA_ && fb == FB_ && out == OUT_)                                                                  \
-    return launch_fmt<FA_, FB_, OUT_>(A, B, D, sa_inv, sb_inv, SA, SB, bias, M, N, K, lda, ldb, ldd, algo, mx, st, clock_stamps);
-  MI_CASE(0, 0, 0) MI_CASE(0, 1, 0) MI_CASE(1, 0, 0) MI_CASE(1, 1, 0)
-  MI_CASE(0, 0, 1) MI_CASE(0, 1, 1) MI_CASE(1, 0, 1) MI_CASE(1, 1, 1)
-#undef MI_CASE
-  set_error("mi_gemm: unsupported format/out combination (%d,%d,%d)", fa, fb, out);
-  return MI_ERR_ARG;
+static int launch_gemm(const GemmPlan& p, const GemmArgs& g) {
+  if (p.family == kFamW4 || p.family == kFamW4P) return launch_w4(p, g);
+  return with_pair(g.fa, g.fb, [&](auto fa, auto fb) -> int {
+    constexpr int FA = fa(), FB = fb();
+    if (p.family == kFamP8 || p.family == kFamStreamK) return launch_p8<FA, FB>(p, g);
+    return g.out == 0 ? launch_plain<FA, FB, 0>(p, g) : launch_plain<FA, FB, 1>(p, g);
+  });
 }
 
-static int check_common(const char* who, const void* A, const void* B, void* D, int64_t M, int64_t N, int64_t K,
+static int check_common(const char* who, const void* A, const void* B, const void* D, int64_t M, int64_t N, int64_t K,
                         int64_t lda, int64_t ldb, int64_t ldd, int fa, int fb, int out) {
   MI_CHECK_ARG(A && B && D, "%s: null operand", who);
   MI_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "%s: negative shape", who);
@@ -1533,53 +1599,16 @@ static int check_common(const char* who, const void* A, const void* B, void* D, 
   return MI_OK;
 }
 
-static int pick_algo(int algo, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldd, int out, bool has_bias,
-                     const char* who) {
-  const bool fast_ok = (M % BM == 0) && (N % BN == 0) && (K % BK == 0) && M > 0 && N > 0 && K > 0;
-  // persistent kernel: even K-tile count, bf16 output, 32-bit buffer offsets
-  (void)has_bias;
-  const bool p8_ok = (M % 256 == 0 || M % 192 == 0) && (N % 256 == 0 || N % 192 == 0) && M > 0 && N > 0 && K > 0 &&
-                     (K % (2 * BK) == 0) && out == 0 && M * lda < (1LL << 31) && N * ldb < (1LL << 31) &&
-                     M * ldd * 2 < (1LL << 31);
-#ifndef MI_DIAG
-  if (algo == 7 || algo == 8 || (algo >= 10 && algo <= 30) || algo == 46 || (algo >= 50 && algo <= 73)) {
-    set_error("%s: algo %d is a timing / diagnostic build; it lives in the lab library (make -C llm_fp8_amd/csrc lab)", who, algo);
-    return MI_ERR_ARG;
-  }
-#endif
-  if (algo == 4 || algo == 5 || (algo >= 15 && algo <= 30) || (algo >= 40 && algo <= 46)) {
-    if (!p8_ok) {
-      set_error("%s: algo %d needs M,N %% 256 (or 192) == 0, K %% 256 == 0, bf16 output, operands < 2 GiB", who, algo);
-      return MI_ERR_SHAPE;
-    }
-    return algo;
-  }
-  if ((algo >= 6 && algo <= 12) || (algo >= 50 && algo <= 73)) {
-    if (!(p8_ok && M % 256 == 0 && N % 256 == 0)) {
-      set_error("%s: algo %d needs M,N,K %% 256 == 0, bf16 output, operands < 2 GiB", who, algo);
-      return MI_ERR_SHAPE;
-    }
-    return algo;
-  }
-  if (algo == 47) {
-    // auto, four-wave kernel where it is the faster one (measured, profiles/r03_w4p_*): 256-multiples, K >= 512, and the
-    // eight-wave kernel's own tile-shape choice is 256 x 256 (where it prefers 192-wide tiles the round count decides)
-    if (p8_ok && M % 256 == 0 && N % 256 == 0 && K >= 512 && pick_tile_cfg(M, N, K) == 0 &&
-        ((M / 256) * (N / 256) + num_cus() - 1) / num_cus() <= 64)
-      return 9;
-    algo = 0;
-  }
-  if (algo == 0) return p8_ok ? 4 : (fast_ok ? 3 : 1);
-  if (algo == 1) return 1;
-  if (algo == 2 || algo == 3 || algo == 13 || algo == 14) {
-    if (!fast_ok) {
-      set_error("%s: algo %d needs M,N %% 256 == 0 and K %% 128 == 0", who, algo);
-      return MI_ERR_SHAPE;
-    }
-    return algo;
-  }
-  set_error("%s: unknown algo %d", who, algo);
-  return MI_ERR_ARG;
+// An entry point: check_common, the entry's null-pointer refusal, the plan, and the launch it names
+static int run_gemm(int entry, const GemmArgs& g, int algo) {
+  int rc = check_common(kWho[entry], g.A, g.B, g.D, g.M, g.N, g.K, g.lda, g.ldb, g.ldd, g.fa, g.fb, g.out);
+  if (rc != MI_OK) return rc;
+  const bool scales = entry == kEntryMx ? g.SA && g.SB : g.sa_inv && g.sb_inv;
+  MI_CHECK_ARG(scales && (entry != kEntryClock || g.bias), "%s: null %spointer", kWho[entry], entry == kEntryClock ? "" : "scale ");
+  GemmPlan p;
+  rc = plan_gemm(entry, g.M, g.N, g.K, g.lda, g.ldb, g.ldd, g.fa, g.fb, g.out, entry != kEntryClock && g.bias != nullptr, algo, p);
+  if (rc != MI_OK || p.family == kFamNone) return rc;  // kFamNone: M or N is 0
+  return launch_gemm(p, g);
 }
 
 }  // namespace mi
@@ -1587,58 +1616,33 @@ static int pick_algo(int algo, int64_t M, int64_t N, int64_t K, int64_t lda, int
 extern "C" int mi_gemm_fp8(const void* A, const void* B, void* D, const float* sa_inv, const float* sb_inv,
                            const void* bias_bf16, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
                            int64_t ldd, int fmt_a, int fmt_b, int out_dtype, int algo, void* stream) {
-  int rc = mi::check_common("mi_gemm_fp8", A, B, D, M, N, K, lda, ldb, ldd, fmt_a, fmt_b, out_dtype);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(sa_inv && sb_inv, "mi_gemm_fp8: null scale pointer");
-  if (M == 0 || N == 0) return MI_OK;
-  int a = mi::pick_algo(algo, M, N, K, lda, ldb, ldd, out_dtype, bias_bf16 != nullptr, "mi_gemm_fp8");
-  if (a < 0) return a;
-  return mi::dispatch(A, B, D, sa_inv, sb_inv, nullptr, nullptr, bias_bf16, M, N, K, lda, ldb, ldd, fmt_a, fmt_b,
-                      out_dtype, a, false, (hipStream_t)stream);
+  return mi::run_gemm(mi::kEntryFp8, {(const uint8_t*)A, (const uint8_t*)B, D, sa_inv, sb_inv, nullptr, nullptr, bias_bf16, M, N, K,
+                                      lda, ldb, ldd, fmt_a, fmt_b, out_dtype, (hipStream_t)stream}, algo);
 }
 
 extern "C" int mi_gemm_fp8_clock(const void* A, const void* B, void* D, const float* sa_inv, const float* sb_inv, int64_t M,
                                  int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldd, int algo, unsigned long long* stamps,
                                  void* stream) {
-  int rc = mi::check_common("mi_gemm_fp8_clock", A, B, D, M, N, K, lda, ldb, ldd, 0, 0, 0);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(sa_inv && sb_inv && stamps, "mi_gemm_fp8_clock: null pointer");
-  MI_CHECK_ARG(algo == 0 || algo == 4 || algo == 9, "mi_gemm_fp8_clock: algo must be 0, 4 or 9");
-  if (M == 0 || N == 0) return MI_OK;
-  int a = mi::pick_algo(algo, M, N, K, lda, ldb, ldd, 0, false, "mi_gemm_fp8_clock");
-  if (a < 0) return a;
-  if (a != 4 && a != 9) {
-    mi::set_error("mi_gemm_fp8_clock: the shape does not run on a persistent kernel");
-    return MI_ERR_SHAPE;
-  }
-  return mi::dispatch(A, B, D, sa_inv, sb_inv, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldd, 0, 0, 0, a, false,
-                      (hipStream_t)stream, (void*)stamps);
+  return mi::run_gemm(mi::kEntryClock, {(const uint8_t*)A, (const uint8_t*)B, D, sa_inv, sb_inv, nullptr, nullptr, stamps, M, N, K,
+                                        lda, ldb, ldd, 0, 0, 0, (hipStream_t)stream}, algo);
 }
 
 extern "C" int mi_gemm_mxfp8(const void* A, const void* SA, const void* B, const void* SB, void* D,
                              const void* bias_bf16, int64_t M, int64_t N, int64_t K, int fmt_a, int fmt_b,
                              int out_dtype, int algo, void* stream) {
-  int rc = mi::check_common("mi_gemm_mxfp8", A, B, D, M, N, K, K, K, N, fmt_a, fmt_b, out_dtype);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(SA && SB, "mi_gemm_mxfp8: null scale pointer");
-  MI_CHECK_ARG(K % 32 == 0, "mi_gemm_mxfp8: K must be a multiple of 32");
-#ifdef MI_DIAG
-  MI_CHECK_ARG(algo == 0 || algo == 1 || algo == 4 || algo == 5 || algo == 18 || algo == 19 || (algo >= 40 && algo <= 45), "mi_gemm_mxfp8: algo must be 0, 1, 4, 5, 18, 19 or 40-45");
-#else
-  MI_CHECK_ARG(algo == 0 || algo == 1 || algo == 4 || algo == 5 || (algo >= 40 && algo <= 45), "mi_gemm_mxfp8: algo must be 0, 1, 4, 5 or 40-45");
-#endif
-  if (M == 0 || N == 0) return MI_OK;
-  int a = algo == 0 ? 4 : algo;
-  if (a != 1) {
-    a = mi::pick_algo(a, M, N, K, K, K, N, out_dtype, bias_bf16 != nullptr, "mi_gemm_mxfp8");
-    if (a < 0) {
-      if (algo != 0) return a;
-      a = 1;  // auto: fall back to the generic kernel
-    }
-  }
-  return mi::dispatch(A, B, D, nullptr, nullptr, SA, SB, bias_bf16, M, N, K, K, K, N, fmt_a, fmt_b, out_dtype, a, true,
-                      (hipStream_t)stream);
+  return mi::run_gemm(mi::kEntryMx, {(const uint8_t*)A, (const uint8_t*)B, D, nullptr, nullptr, (const uint8_t*)SA, (const uint8_t*)SB,
+                                     bias_bf16, M, N, K, K, K, N, fmt_a, fmt_b, out_dtype, (hipStream_t)stream}, algo);
 }
+
+#ifdef MI_DIAG
+extern "C" int mi_gemm_plan_diag(int entry, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldd, int fmt_a,
+                                 int fmt_b, int out_dtype, int has_bias, int algo, mi_gemm_plan* out) {
+  MI_CHECK_ARG(entry >= 0 && entry <= 2 && out != nullptr, "mi_gemm_plan_diag: bad entry or null plan");
+  const void* aligned = (const void*)16;  // stands for the operands: only check_common's shape and leading-dimension checks apply
+  int rc = mi::check_common(mi::kWho[entry], aligned, aligned, aligned, M, N, K, lda, ldb, ldd, fmt_a, fmt_b, out_dtype);
+  return rc != MI_OK ? rc : mi::plan_gemm(entry, M, N, K, lda, ldb, ldd, fmt_a, fmt_b, out_dtype, has_bias != 0, algo, *out);
+}
+#endif
 
 extern "C" int64_t mi_gemm_workspace_bytes(void) { return 4096 + (int64_t)mi::num_cus() * (8 * 32 * 1024); }
 

@@ -2,6 +2,7 @@
 // LDS-DMA staging through buffer descriptors, the XCD-aware tile map.  See mi_gemm.hip for the design notes.
 #pragma once
 #include "mi_common.h"
+#include <type_traits>
 
 namespace mi {
 
@@ -143,9 +144,40 @@ struct GroupArgs {
 // the grouped launch of the four-wave kernel (tile shape 256 x 256, every problem K >= 512)
 int launch_w4_grouped(const GroupArgs& ga, int fa, int fb, int grid, hipStream_t st);
 
-// mi_gemm_w4.hip: the four-wave (128x128 wave tile) kernel.  variant 0 = product, 1 = no stores, 2 = clock stamps (dbg)
-int launch_w4(const void* A, const void* B, void* D, const float* sa_inv, const float* sb_inv, int64_t M, int64_t N, int64_t K,
-              int64_t lda, int64_t ldb, int64_t ldd, int fa, int fb, int variant, void* dbg, hipStream_t st, const void* bias = nullptr);
+// Host dispatch of mi_gemm_fp8 / mi_gemm_mxfp8 / mi_gemm_fp8_clock: plan_gemm (mi_gemm.hip) turns an algo id into a GemmPlan or a
+// refusal; launch_gemm / launch_w4 instantiate and launch what the plan names and refuse nothing.
+enum GemmFamily { kFamNone = 0, kFamGeneric, kFam2Phase, kFam8Phase, kFamP8, kFamStreamK, kFamW4, kFamW4P };
+// mi_gemm_plan.bias_use; in the algo table, what a build does with a bias argument (kBiasRefused reaches no plan)
+enum BiasUse { kBiasUnused = 0, kBiasAdded, kBiasIsStamps, kBiasRefused };
+using GemmPlan = ::mi_gemm_plan;  // include/mi_fp8.h says what the fields hold
+constexpr int kP8BlockEpilogue = 100;  // build of kFamP8: ABL 0 with DEPI = false (block epilogue after each tile)
+
+struct GemmArgs {
+  const uint8_t *A, *B;
+  void* D;
+  const float *sa_inv, *sb_inv;  // per-tensor entry points
+  const uint8_t *SA, *SB;        // mi_gemm_mxfp8: E8M0 block scales (null otherwise)
+  const void* bias;              // bf16 [N], or the u64 stamp buffer (plan.bias_use)
+  int64_t M, N, K, lda, ldb, ldd;
+  int fa, fb, out;
+  hipStream_t st;
+};
+
+// The one place two runtime 0 / 1 choices become template arguments: f(integral_constant<int, a>, integral_constant<int, b>), in
+// f read as a() and b().  For the format pair (fa, fb) -> <FA, FB> of every GEMM launcher, and for MX x BIAS.
+template <class F>
+static inline int with_pair(int a, int b, F&& f) {
+  using c0 = std::integral_constant<int, 0>;
+  using c1 = std::integral_constant<int, 1>;
+  if (a == 0) return b == 0 ? f(c0{}, c0{}) : f(c0{}, c1{});
+  return b == 0 ? f(c1{}, c0{}) : f(c1{}, c1{});
+}
+
+// mi_gemm_w4.hip: the four-wave (128x128 wave tile) kernels, families kFamW4 (one tile per workgroup) and kFamW4P (persistent)
+int launch_w4(const GemmPlan& p, const GemmArgs& g);
+// A plan that names a build outside a launcher's list (the algo table and the build lists disagree; plan_gemm lets none through)
+#define MI_NOT_COMPILED(p) \
+  MI_CHECK_ARG(false, "mi_gemm: family %d build %d schedule %d is not compiled into this library", p.family, p.build, p.sched)
 
 static inline int num_cus() {
   static int n = 0;  // benign race: every thread computes the same value

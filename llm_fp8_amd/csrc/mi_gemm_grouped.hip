@@ -572,10 +572,7 @@ static int launch_grouped(const GroupArgs& ga, int cfg, int grid, hipStream_t st
 
 template <bool MX>
 static int launch_grouped_fmt(const GroupArgs& ga, int fmt_a, int fmt_b, int cfg, int grid, hipStream_t st) {
-  if (fmt_a == 0 && fmt_b == 0) return launch_grouped<0, 0, MX>(ga, cfg, grid, st);
-  if (fmt_a == 1 && fmt_b == 0) return launch_grouped<1, 0, MX>(ga, cfg, grid, st);
-  if (fmt_a == 0 && fmt_b == 1) return launch_grouped<0, 1, MX>(ga, cfg, grid, st);
-  return launch_grouped<1, 1, MX>(ga, cfg, grid, st);
+  return with_pair(fmt_a, fmt_b, [&](auto a, auto b) { return launch_grouped<a(), b(), MX>(ga, cfg, grid, st); });
 }
 
 // One problem of a group as the host path below takes it.  Each entry point fills it from its own ABI struct and runs its own

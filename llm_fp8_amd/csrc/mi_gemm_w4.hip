@@ -867,98 +867,60 @@ __global__ __launch_bounds__(256, 1) void gemm_w4p(const std::conditional_t<MODE
   });
 }
 
-template <int FA, int FB>
-static int launch_w4_fmt(const uint8_t* a, const uint8_t* b, uint16_t* D, const float* sa_inv, const float* sb_inv, int64_t M,
-                         int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldd, int variant, void* dbg, hipStream_t st,
-                         const void* bias) {
-  const int tiles_m = (int)(M / 256), tiles_n = (int)(N / 256);
-  const dim3 grid(tiles_m * tiles_n), block(256);
-#define MI_W4(ABLv)                                                                                                      \
-  hipLaunchKernelGGL((gemm_w4<FA, FB, ABLv>), grid, block, 0, st, a, b, D, sa_inv, sb_inv, (int)K, (int)lda, (int)ldb,    \
-                     (int)ldd, tiles_m, tiles_n, (int)(M * lda), (int)(N * ldb), (int)(M * ldd * 2), (unsigned long long*)dbg)
-  W4Single ws;
-  ws.A = a; ws.B = b; ws.D = D; ws.sa_inv = sa_inv; ws.sb_inv = sb_inv; ws.bias = (const uint16_t*)bias; ws.dbg = (unsigned long long*)dbg;
-  ws.K = (int)K; ws.lda = (int)lda; ws.ldb = (int)ldb; ws.ldd = (int)ldd; ws.tiles_m = tiles_m; ws.tiles_n = tiles_n;
-  ws.a_bytes = (int)(M * lda); ws.b_bytes = (int)(N * ldb); ws.d_bytes = (int)(M * ldd * 2); ws.n_cols = (int)N;
-#define MI_W4P(ABLv) hipLaunchKernelGGL((gemm_w4p<FA, FB, ABLv, 0>), pgrid, block, 0, st, ws)
-  const int ntiles = tiles_m * tiles_n;
-  const dim3 pgrid(ntiles < num_cus() ? ntiles : num_cus());
-  if (variant >= 10 && variant < 20 && ((ntiles + (int)pgrid.x - 1) / (int)pgrid.x > 64 || K < 512 || tiles_m >= 16384 || tiles_n >= 16384)) {
-    set_error("mi_gemm (w4 persistent): needs K >= 512, at most 64 tiles per workgroup and fewer than 16384 tiles per dimension");
-    return MI_ERR_SHAPE;
-  }
-  if (bias != nullptr && variant != 10) {
-    set_error("mi_gemm (w4): only the persistent product kernel takes a bias");
-    return MI_ERR_ARG;
-  }
-  if (variant == 0) MI_W4(0);
-  else if (variant == 10 && bias != nullptr) hipLaunchKernelGGL((gemm_w4p<FA, FB, 0, 1>), pgrid, block, 0, st, ws);
-  else if (variant == 10) MI_W4P(0);
-  else if (variant == 12) {
-    if constexpr (FA == 0 && FB == 0) MI_W4P(2);
-    else {
-      set_error("mi_gemm (w4): the clock-stamp build is E4M3 x E4M3 only");
-      return MI_ERR_ARG;
-    }
-  }
+// The builds that exist, once: X(ABL, S) of gemm_w4 and X(ABL) of gemm_w4p.  ABL 0 = product, 1 = no stores, 2 = clock stamps
+// (gemm_w4: u64[4 * tiles], gemm_w4p: u64[4 * grid]); gemm_w4p also 3 = no epilogue, 4-6 = epilogue store policy plain / nt /
+// sc1 + nt, 7 = per-K-tile stamps.  Every format pair has gemm_w4's S = 0 builds and gemm_w4p's product build; the others are
+// E4M3 x E4M3 only.
 #ifdef MI_DIAG
-  else if (variant == 1) MI_W4(1);
-  else if (variant == 2) MI_W4(2);
-#define MI_W4S(ABLv, Sv)                                                                                                 \
-  hipLaunchKernelGGL((gemm_w4<FA, FB, ABLv, Sv>), grid, block, 0, st, a, b, D, sa_inv, sb_inv, (int)K, (int)lda, (int)ldb, \
-                     (int)ldd, tiles_m, tiles_n, (int)(M * lda), (int)(N * ldb), (int)(M * ldd * 2), (unsigned long long*)dbg)
-  else if (variant >= 20 && variant < 40 && FA == 0 && FB == 0) {  // schedule sweep (E4M3 x E4M3): 20 + 4 S + {0: product, 1: no stores, 2: stamps}
-    const int S = (variant - 20) / 4, kind = (variant - 20) % 4;
-    if constexpr (FA == 0 && FB == 0) {
-      switch (S * 4 + kind) {
-        case 4: MI_W4S(0, 1); break;
-        case 5: MI_W4S(1, 1); break;
-        case 6: MI_W4S(2, 1); break;
-        case 12: MI_W4S(0, 3); break;
-        case 13: MI_W4S(1, 3); break;
-        case 14: MI_W4S(2, 3); break;
-        case 16: MI_W4S(0, 4); break;
-        case 17: MI_W4S(1, 4); break;
-        case 18: MI_W4S(2, 4); break;
-        default: set_error("mi_gemm (w4): no such schedule variant %d", variant); return MI_ERR_ARG;
-      }
-    }
-  }
-#undef MI_W4S
-  else if ((variant == 11 || (variant >= 13 && variant <= 17)) && !(FA == 0 && FB == 0)) {
-    set_error("mi_gemm (w4): timing variant %d is built for E4M3 x E4M3 only", variant);
-    return MI_ERR_ARG;
-  }
-#define MI_W4P_LAB(ABLv) do { if constexpr (FA == 0 && FB == 0) MI_W4P(ABLv); } while (0)
-  else if (variant == 11) MI_W4P_LAB(1);
-  else if (variant == 13) MI_W4P_LAB(3);
-  else if (variant == 14) MI_W4P_LAB(4);
-  else if (variant == 15) MI_W4P_LAB(5);
-  else if (variant == 16) MI_W4P_LAB(6);
-  else if (variant == 17) MI_W4P_LAB(7);
-#undef MI_W4P_LAB
+#define MI_W4_BUILDS(X) X(0, 0) X(1, 0) X(2, 0) X(0, 1) X(1, 1) X(2, 1) X(0, 3) X(1, 3) X(2, 3) X(0, 4) X(1, 4) X(2, 4)
+#define MI_W4P_BUILDS_E4M3(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+#else
+#define MI_W4_BUILDS(X) X(0, 0)
+#define MI_W4P_BUILDS_E4M3(X) X(2)
 #endif
-  else {
-    set_error("mi_gemm (w4): variant %d is a timing build of the lab library", variant);
-    return MI_ERR_ARG;
-  }
-#undef MI_W4P
-#undef MI_W4
-  MI_CHECK_LAUNCH("mi_gemm (w4) launch");
-  return MI_OK;
-}
 
-// variant: one tile per workgroup: 0 = product, 1 = no stores, 2 = clock stamps (dbg = u64[4 * tiles]); persistent (gemm_w4p):
-// 10 = product, 11 = no stores, 12 = clock stamps (dbg = u64[4 * grid]), 13 = no epilogue.  Shapes: M, N % 256 == 0, K % 256 == 0,
-// operands below 2 GiB (the dispatcher in mi_gemm.hip checks).
-int launch_w4(const void* A, const void* B, void* D, const float* sa_inv, const float* sb_inv, int64_t M, int64_t N, int64_t K,
-              int64_t lda, int64_t ldb, int64_t ldd, int fa, int fb, int variant, void* dbg, hipStream_t st, const void* bias) {
-  const uint8_t *a = (const uint8_t*)A, *b = (const uint8_t*)B;
-  uint16_t* d = (uint16_t*)D;
-  if (fa == 0 && fb == 0) return launch_w4_fmt<0, 0>(a, b, d, sa_inv, sb_inv, M, N, K, lda, ldb, ldd, variant, dbg, st, bias);
-  if (fa == 0 && fb == 1) return launch_w4_fmt<0, 1>(a, b, d, sa_inv, sb_inv, M, N, K, lda, ldb, ldd, variant, dbg, st, bias);
-  if (fa == 1 && fb == 0) return launch_w4_fmt<1, 0>(a, b, d, sa_inv, sb_inv, M, N, K, lda, ldb, ldd, variant, dbg, st, bias);
-  return launch_w4_fmt<1, 1>(a, b, d, sa_inv, sb_inv, M, N, K, lda, ldb, ldd, variant, dbg, st, bias);
+// Shapes: M, N % 256 == 0, K % 256 == 0, operands below 2 GiB; persistent: K >= 512, at most 64 tiles per workgroup (plan_gemm in
+// mi_gemm.hip checks, and refuses what is not built).
+int launch_w4(const GemmPlan& p, const GemmArgs& g) {
+  return with_pair(g.fa, g.fb, [&](auto fa, auto fb) -> int {
+    constexpr int FA = fa(), FB = fb();
+    const dim3 grid(p.grid_x), block(p.block);
+    unsigned long long* dbg = p.bias_use == kBiasIsStamps ? (unsigned long long*)g.bias : nullptr;
+    uint16_t* D = (uint16_t*)g.D;
+    if (p.family == kFamW4) {
+#define MI_W4(ABLv, Sv)                                                                                                   \
+  case ABLv * 8 + Sv:                                                                                                     \
+    hipLaunchKernelGGL((gemm_w4<(Sv ? 0 : FA), (Sv ? 0 : FB), ABLv, Sv>), grid, block, 0, g.st, g.A, g.B, D, g.sa_inv,     \
+                       g.sb_inv, (int)g.K, (int)g.lda, (int)g.ldb, (int)g.ldd, p.tiles_m, p.tiles_n, (int)(g.M * g.lda),  \
+                       (int)(g.N * g.ldb), (int)(g.M * g.ldd * 2), dbg);                                                  \
+    break;
+      if (p.sched != 0 && (FA != 0 || FB != 0)) MI_NOT_COMPILED(p);
+      switch (p.build * 8 + p.sched) {
+        MI_W4_BUILDS(MI_W4)
+        default: MI_NOT_COMPILED(p);
+      }
+#undef MI_W4
+    } else {
+      W4Single ws;
+      ws.A = g.A; ws.B = g.B; ws.D = D; ws.sa_inv = g.sa_inv; ws.sb_inv = g.sb_inv; ws.dbg = dbg;
+      ws.bias = p.bias_use == kBiasAdded ? (const uint16_t*)g.bias : nullptr;
+      ws.K = (int)g.K; ws.lda = (int)g.lda; ws.ldb = (int)g.ldb; ws.ldd = (int)g.ldd; ws.tiles_m = p.tiles_m; ws.tiles_n = p.tiles_n;
+      ws.a_bytes = (int)(g.M * g.lda); ws.b_bytes = (int)(g.N * g.ldb); ws.d_bytes = (int)(g.M * g.ldd * 2); ws.n_cols = (int)g.N;
+      if (p.build != 0 && (FA != 0 || FB != 0)) MI_NOT_COMPILED(p);
+#define MI_W4P(ABLv) case ABLv: hipLaunchKernelGGL((gemm_w4p<0, 0, ABLv, 0>), grid, block, 0, g.st, ws); break;
+      switch (p.build) {
+        case 0:
+          if (ws.bias) hipLaunchKernelGGL((gemm_w4p<FA, FB, 0, 1>), grid, block, 0, g.st, ws);
+          else hipLaunchKernelGGL((gemm_w4p<FA, FB, 0, 0>), grid, block, 0, g.st, ws);
+          break;
+        MI_W4P_BUILDS_E4M3(MI_W4P)
+        default: MI_NOT_COMPILED(p);
+      }
+#undef MI_W4P
+    }
+    MI_CHECK_LAUNCH("mi_gemm (w4) launch");
+    return MI_OK;
+  });
 }
 
 // grouped launch (mi_gemm_fp8_grouped, tile_cfg 4): the schedule in `ga` is the eight-wave kernel's (256 x 256 tiles)
@@ -968,10 +930,10 @@ int launch_w4_grouped(const GroupArgs& ga, int fa, int fb, int grid, hipStream_t
       set_error("mi_gemm_fp8_grouped (four-wave kernel): every problem needs K >= 512 and K %% 256 == 0");
       return MI_ERR_SHAPE;
     }
-  if (fa == 0 && fb == 0) hipLaunchKernelGGL((gemm_w4p<0, 0, 0, 2>), dim3(grid), dim3(256), 0, st, ga);
-  else if (fa == 0 && fb == 1) hipLaunchKernelGGL((gemm_w4p<0, 1, 0, 2>), dim3(grid), dim3(256), 0, st, ga);
-  else if (fa == 1 && fb == 0) hipLaunchKernelGGL((gemm_w4p<1, 0, 0, 2>), dim3(grid), dim3(256), 0, st, ga);
-  else hipLaunchKernelGGL((gemm_w4p<1, 1, 0, 2>), dim3(grid), dim3(256), 0, st, ga);
+  with_pair(fa, fb, [&](auto a, auto b) {
+    hipLaunchKernelGGL((gemm_w4p<a(), b(), 0, 2>), dim3(grid), dim3(256), 0, st, ga);
+    return 0;
+  });
   MI_CHECK_LAUNCH("mi_gemm_fp8_grouped (four-wave) launch");
   return MI_OK;
 }

@@ -152,21 +152,24 @@ def scale_update(amax_history: torch.Tensor, scale: torch.Tensor, scale_inv: tor
     _lib.check(rc, "mi_scale_update")
 
 
+def _default_algo_for(M: int, N: int, K: int, out: Optional[torch.Tensor], out_dtype: torch.dtype, mx: bool) -> int:
+    """What a call without an algo runs: default_gemm_algo(), or 0 (the library's own choice) where that default does not take the
+    call -- the library refuses an explicit algo on a shape it does not run, and a default must not be refused."""
+    algo = default_gemm_algo()
+    bf16 = out_dtype == torch.bfloat16 and (out is None or out.dtype == torch.bfloat16)
+    if ((mx and algo not in (0, 1, 4, 5)) or (algo == 3 and (M % 256 or N % 256 or K % 128)) or (algo == 47 and not bf16)
+            or (algo == 5 and ((M % 256 and M % 192) or (N % 256 and N % 192) or K % 256 or not bf16))):
+        return 0
+    return algo
+
+
 def gemm_fp8(a8: torch.Tensor, b8: torch.Tensor, sa_inv: torch.Tensor, sb_inv: torch.Tensor,
              fmt_a: int, fmt_b: int, bias: Optional[torch.Tensor] = None,
              out: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.bfloat16,
              algo: Optional[int] = None) -> torch.Tensor:
     """K4-K6.  D[M,N] = (A[M,K] . B[N,K]^T) * sa_inv * sb_inv (+ bias)."""
     if algo is None:
-        algo = default_gemm_algo()
-        M_, N_, K_ = a8.shape[0], b8.shape[0], a8.shape[1]
-        if algo == 3 and (M_ % 256 or N_ % 256 or K_ % 128):
-            algo = 0
-        if algo == 47 and (out_dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16)):
-            algo = 0
-        if algo == 5 and ((M_ % 256 and M_ % 192) or (N_ % 256 and N_ % 192) or K_ % 256 or out_dtype != torch.bfloat16
-                          or (out is not None and out.dtype != torch.bfloat16)):
-            algo = 0
+        algo = _default_algo_for(a8.shape[0], b8.shape[0], a8.shape[1], out, out_dtype, mx=False)
     _dev(a8, b8, sa_inv, sb_inv, bias, out)
     if algo == 44:
         ensure_gemm_workspace(a8.device)
@@ -245,11 +248,7 @@ def gemm_mxfp8(a8, sa, b8, sb, fmt_a: int = E4M3, fmt_b: int = E4M3, bias=None, 
     """K8.  Block-scaled D[M,N] = sum_blk 2^(sa+sb-254) sum_32 A.B (+bias)."""
     _dev(a8, sa, b8, sb, bias, out)
     if algo is None:
-        algo = default_gemm_algo()
-        M_, N_, K_ = a8.shape[0], b8.shape[0], a8.shape[1]
-        if algo not in (0, 1, 4, 5) or (algo == 5 and ((M_ % 256 and M_ % 192) or (N_ % 256 and N_ % 192) or K_ % 256
-                                                      or out_dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16))):
-            algo = 0
+        algo = _default_algo_for(a8.shape[0], b8.shape[0], a8.shape[1], out, out_dtype, mx=True)
     if algo == 44:
         ensure_gemm_workspace(a8.device)
     M, K = a8.shape

@@ -49,6 +49,7 @@ def test_product_library_has_no_lab_surface():
     from llm_fp8_amd import _lib
     lib = _lib.load()
     assert not hasattr(lib, "mi_attn_fwd_diag")
+    assert not hasattr(lib, "mi_gemm_plan_diag")
     fake = 0x10000  # non-null, 16-byte aligned; the algo is rejected before anything is launched or dereferenced
     for algo in (7, 8, 10, 11, 12, 13, 14, 15, 20, 21, 22, 27, 28, 29, 30, 46):
         rc = lib.mi_gemm_fp8(fake, fake, fake, fake, fake, None, 256, 256, 256, 256, 256, 256, 0, 0, 0, algo, None)
