@@ -49,9 +49,12 @@ extern "C" {
 #define MI_AMAX_ALGO_MAX 0
 #define MI_AMAX_ALGO_MOST_RECENT 1
 
-/* ABI version: bumped whenever an entry point is added, removed or changes its signature or the meaning of an argument.
- * mi_abi_version() returns the value the library was built with; a binding compares it with the header it was written
- * against (llm_fp8_amd/_lib.py does at load time).
+/* ABI version and revision.  The VERSION changes when an existing entry point changes its signature or the meaning of an
+ * argument, or goes away: a binding written against another version must not call the library (llm_fp8_amd/_lib.py compares at
+ * load time).  The REVISION counts the entry points added since that version: every caller of revision r works unchanged with a
+ * library of the same version and a revision >= r, and a binding that finds a lower revision knows which entry points are missing.
+ * mi_abi_version() / mi_abi_revision() return the values the library was built with.  (Up to version 5 an added entry point
+ * bumped the version; the history below records that.)
  *   1  round 1 (the surface of SURVEY.md 8b + fused neighbours)
  *   2  round 2: mi_gemm_fp8 algo values 20-30, 46 (diagnostic builds), mi_adamw_cast_bf16_multi, mi_transpose_u8,
  *      mi_gemm_fp8_grouped
@@ -60,9 +63,13 @@ extern "C" {
  *      mi_gemm_fp8_grouped tile_cfg 4 (four-wave kernel); mi_gemm_fp8_clock; mi_swiglu_cast_bias, mi_dswiglu_cast_bias,
  *      mi_add_bias_rmsnorm_stats (bias fused into the consumer of the GEMM output)
  *   5  mi_gemm_mxfp8_grouped (a Linear's block-scaled dgrad + wgrad in one persistent launch)
+ * Revisions of version 5:
+ *   1  mi_adamw_f32_multi (fp32 master weights and moments in the fused AdamW + FP8 cast pass), mi_abi_revision
  */
 #define MI_ABI_VERSION 5
+#define MI_ABI_REVISION 1
 int mi_abi_version(void);
+int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
 const char* mi_last_error(void);
 /* 1 if the current HIP device is gfx950 (MI355X), else 0; <0 on HIP error. */
@@ -407,6 +414,25 @@ int mi_adamw_cast_bf16_multi(const int64_t* table, int n_tensors, const int32_t*
 int mi_adamw_mxcast_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                                const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                                int64_t step, void* stream);
+
+/*
+ * The two calls above with fp32 optimiser state (ABI 5 revision 1): the update is carried by an fp32 MASTER weight and fp32
+ * exp_avg / exp_avg_sq, so a step smaller than half a bf16 ulp of the weight is kept instead of rounded away.
+ * table: int64 [13, n_tensors].  Rows 0-11 as for mi_adamw_cast_bf16_multi (sink_kind 0) or mi_adamw_mxcast_bf16_multi
+ * (sink_kind 1), except that rows 2 and 3 point at FP32 exp_avg / exp_avg_sq and row 0 (p, bf16) is OUTPUT ONLY; row 12 is the
+ * fp32 master weight.  Per element: w = master[i]; the AdamW update of the bf16 calls (one formula) runs on w, evaluated in fp64 --
+ * fp32 evaluation loses exp_avg where its two terms cancel, which would show in fp32 state -- and master, exp_avg and exp_avg_sq
+ * are each rounded once to fp32 and stored; p[i] = RNE_bf16(master[i]); the FP8 copies (y / yT / amax, or y_row / s_row / y_colT / s_colT) are
+ * quantised from that ROUNDED bf16 value, exactly as the bf16 calls do -- bitwise the bytes of mi_cast_amax / mi_mxfp8_quantize
+ * on the updated p.  Non-finite values follow from the arithmetic.  A tensor with cols == 0 takes the flat chunks (16-byte
+ * accesses where p, g and the three fp32 arrays are all 16-byte aligned, element-wise otherwise); a tensor with cols > 0 is walked
+ * in 128 x 128 tiles and needs all five arrays 16-byte aligned (the caller sends anything else down the flat chunks).
+ * MI_ERR_ARG before any launch: null table / chunks, n_tensors < 1, chunk_elems not a positive multiple of 8, sink_kind outside
+ * {0, 1}, step < 1.  n_chunks == 0 is MI_OK (nothing to do).
+ */
+int mi_adamw_f32_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
+                       const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int64_t step, int sink_kind, void* stream);
 
 /*
  * Embedding weight gradient added in place: grad[id, :] += alpha * sum_{tokens t with ids[t] == id} dY[t, :]   (bf16, fp32

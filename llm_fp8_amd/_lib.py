@@ -13,6 +13,7 @@ LAB_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "bin", "libmi_fp8_l
 MI_FMT_E4M3 = 0
 MI_FMT_E5M2 = 1
 ABI_VERSION = 5
+ABI_REVISION = 1  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -90,6 +91,15 @@ SIGNATURES = {
     "mi_add_bias_rmsnorm_stats": [_p, _p, _p, _p, _p, _c_i64, _c_i64, ctypes.c_float, _p],
     "mi_gemm_fp8_clock": [_p, _p, _p, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _p, _p],
 }
+# entry points added since ABI_VERSION (include/mi_fp8.h: the revision).  They are part of SIGNATURES; a library of the same
+# version that predates them (LLM_FP8_AMD_LIB pointing at an older build for A/B timing) still loads, and `require()` raises for
+# the caller that needs one.
+REVISION_SIGNATURES = {
+    "mi_abi_revision": [],
+    "mi_adamw_f32_multi": [_p, _c_int, _p, _c_int, _c_int, _p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                           ctypes.c_float, _c_i64, _c_int, _p],
+}
+SIGNATURES.update(REVISION_SIGNATURES)
 # entry points only the lab build exports (#ifdef MI_DIAG in include/mi_fp8.h)
 LAB_SIGNATURES = {
     "mi_attn_fwd_diag": [_p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_float, _p],
@@ -102,6 +112,8 @@ _lib = None
 def _bind(path: str, signatures) -> ctypes.CDLL:
     lib = ctypes.CDLL(path)
     for name, argtypes in signatures.items():
+        if name in REVISION_SIGNATURES and not hasattr(lib, name):
+            continue  # a build of an earlier revision: everything it has is bound, `require()` names what it lacks
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = ctypes.c_char_p if name == "mi_last_error" else (_c_i64 if name == "mi_gemm_workspace_bytes" else _c_int)
@@ -138,6 +150,22 @@ def use_lab_library() -> ctypes.CDLL:
     _lib = _bind(LAB_LIB_PATH, {**SIGNATURES, **LAB_SIGNATURES})
     _lib._mi_is_lab = True
     return _lib
+
+
+def revision(lib=None) -> int:
+    """MI_ABI_REVISION of the loaded library (0: a build from before revisions were counted)."""
+    lib = load() if lib is None else lib
+    return int(lib.mi_abi_revision()) if hasattr(lib, "mi_abi_revision") else 0
+
+
+def require(name: str, why: str):
+    """The entry point `name` of REVISION_SIGNATURES, or a RuntimeError that says which library lacks it and what needed it."""
+    lib = load()
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{why} needs {name}, which {LIB_PATH} (ABI {ABI_VERSION} revision {revision(lib)}) does not export: "
+                           f"it was built before revision {ABI_REVISION}; rebuild it, or unset LLM_FP8_AMD_LIB")
+    return fn
 
 
 def check(rc: int, what: str = "") -> None:

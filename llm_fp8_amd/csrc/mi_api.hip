@@ -21,6 +21,7 @@ int hip_fail(hipError_t e, const char* what) {
 }  // namespace mi
 
 extern "C" int mi_abi_version(void) { return MI_ABI_VERSION; }
+extern "C" int mi_abi_revision(void) { return MI_ABI_REVISION; }
 
 extern "C" const char* mi_last_error(void) { return mi::g_err; }
 

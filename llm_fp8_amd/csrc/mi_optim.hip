@@ -62,13 +62,23 @@ struct AdamArgs {
   float lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt;
 };
 
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamArgs& a) {
-  p *= (1.0f - a.lr * a.weight_decay);
-  m = m + (1.0f - a.beta1) * (g - m);
-  v = a.beta2 * v + (1.0f - a.beta2) * g * g;
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  p -= a.step_size * (m / denom);
+__device__ __forceinline__ float adam_sqrt(float x) { return sqrtf(x); }
+__device__ __forceinline__ double adam_sqrt(double x) { return sqrt(x); }
+
+// The one AdamW formula.  T = float: the arithmetic of the bf16-state kernels (state of 8 significand bits: fp32 evaluation error is
+// far below its rounding).  T = double: fp32 state, where fp32 evaluation would itself be the error -- exp_avg = m + (1 - b1)(g - m)
+// cancels where m and g oppose, its fp32 error is then large against the result, and it goes into the weight through the update.
+template <typename T>
+__device__ __forceinline__ void adam_one(T& p, T g, T& m, T& v, const AdamArgs& a) {
+  p *= (T(1) - T(a.lr) * T(a.weight_decay));
+  m = m + (T(1) - T(a.beta1)) * (g - m);
+  v = T(a.beta2) * v + (T(1) - T(a.beta2)) * g * g;
+  const T denom = adam_sqrt(v) / T(a.bc2_sqrt) + T(a.eps);
+  p -= T(a.step_size) * (m / denom);
 }
+// arithmetic type of a state type (Vec8<ST> below)
+template <typename ST> struct AdamMath { typedef float T; };
+template <> struct AdamMath<float> { typedef double T; };
 
 __global__ __launch_bounds__(256) void adamw_kernel(uint16_t* __restrict__ p, const uint16_t* __restrict__ g,
                                                     uint16_t* __restrict__ m, uint16_t* __restrict__ v, int64_t n,
@@ -172,51 +182,139 @@ __global__ __launch_bounds__(256) void sumsq_multi_kernel(const int64_t* __restr
   if (tid == 0) partial[blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
-                                                          int chunk_elems, const float* __restrict__ grad_scale, AdamArgs a) {
-  const ChunkRef cr = chunks[blockIdx.x];
-  uint16_t* p = reinterpret_cast<uint16_t*>(tab[cr.tensor]);
-  const uint16_t* g = reinterpret_cast<const uint16_t*>(tab[(int64_t)1 * T + cr.tensor]);
-  uint16_t* m = reinterpret_cast<uint16_t*>(tab[(int64_t)2 * T + cr.tensor]);
-  uint16_t* v = reinterpret_cast<uint16_t*>(tab[(int64_t)3 * T + cr.tensor]);
-  const int64_t n = tab[(int64_t)4 * T + cr.tensor];
-  const int64_t lo = (int64_t)cr.chunk * chunk_elems, hi = min(n, lo + chunk_elems);
-  const float gs = grad_scale ? *grad_scale : 1.0f;
-  const int tid = threadIdx.x;
-  const bool aligned = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
+// ---- state type of the multi-tensor AdamW kernels.  ST = uint16_t: bf16 parameter, exp_avg and exp_avg_sq (torch's fused AdamW
+// layout; the weight is read from and written to p).  ST = float: fp32 exp_avg / exp_avg_sq and an fp32 MASTER weight (table row 12)
+// that carries the update unrounded; p is then output only, p = RNE_bf16(master).  Vec8<ST> = one lane's 8 consecutive values.
+template <typename ST>
+struct Vec8;
+template <>
+struct Vec8<uint16_t> {
+  v4i x;
+  __device__ __forceinline__ void load(const uint16_t* b, int64_t i) { x = reinterpret_cast<const v4i*>(b)[i]; }
+  __device__ __forceinline__ void store(uint16_t* b, int64_t i) const { reinterpret_cast<v4i*>(b)[i] = x; }
+  __device__ __forceinline__ float lo(int j) const { return __uint_as_float((u32)x[j] << 16); }
+  __device__ __forceinline__ float hi(int j) const { return __uint_as_float((u32)x[j] & 0xFFFF0000u); }
+  __device__ __forceinline__ void set(int j, float l, float h) { x[j] = (int)pack_bf16x2(l, h); }
+};
+template <>
+struct Vec8<float> {  // 32 bytes: two 16-byte accesses
+  v4f x[2];
+  __device__ __forceinline__ void load(const float* b, int64_t i) {
+    x[0] = reinterpret_cast<const v4f*>(b)[2 * i];
+    x[1] = reinterpret_cast<const v4f*>(b)[2 * i + 1];
+  }
+  __device__ __forceinline__ void store(float* b, int64_t i) const {
+    reinterpret_cast<v4f*>(b)[2 * i] = x[0];
+    reinterpret_cast<v4f*>(b)[2 * i + 1] = x[1];
+  }
+  __device__ __forceinline__ float lo(int j) const { return x[j >> 1][(2 * j) & 3]; }
+  __device__ __forceinline__ float hi(int j) const { return x[j >> 1][((2 * j) & 3) + 1]; }
+  __device__ __forceinline__ void set(int j, float l, float h) {
+    x[j >> 1][(2 * j) & 3] = l;
+    x[j >> 1][((2 * j) & 3) + 1] = h;
+  }
+};
+__device__ __forceinline__ float state_load(const uint16_t* b, int64_t k) { return bf16_bits_to_float(b[k]); }
+__device__ __forceinline__ float state_load(const float* b, int64_t k) { return b[k]; }
+__device__ __forceinline__ void state_store(uint16_t* b, int64_t k, float f) { b[k] = (uint16_t)float_to_bf16_bits(f); }
+__device__ __forceinline__ void state_store(float* b, int64_t k, float f) { b[k] = f; }
+
+// The tensor's addresses out of the table: `w` is what the update reads and writes at full state precision (p itself for bf16
+// state, the fp32 master of row 12 otherwise).
+template <typename ST>
+struct AdamPtrs {
+  uint16_t* p;
+  const uint16_t* g;
+  ST *w, *m, *v;
+  __device__ __forceinline__ AdamPtrs(const int64_t* __restrict__ tab, int T, int t) {
+    p = reinterpret_cast<uint16_t*>(tab[t]);
+    g = reinterpret_cast<const uint16_t*>(tab[(int64_t)1 * T + t]);
+    m = reinterpret_cast<ST*>(tab[(int64_t)2 * T + t]);
+    v = reinterpret_cast<ST*>(tab[(int64_t)3 * T + t]);
+    if constexpr (sizeof(ST) == 4) w = reinterpret_cast<ST*>(tab[(int64_t)12 * T + t]);
+    else w = p;
+  }
+  __device__ __forceinline__ bool aligned16() const {
+    if constexpr (sizeof(ST) == 4)
+      return ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)w)) & 15) == 0;
+    else
+      return ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
+  }
+};
+
+// AdamW on one lane's 8 consecutive elements (vector index i): load, update, store.  f = the 8 weights as stored in p -- the
+// ROUNDED bf16 values, which is what the FP8 sinks quantise.
+template <typename ST>
+__device__ __forceinline__ void adam_vec8(const AdamPtrs<ST>& t, int64_t i, float gs, const AdamArgs& a, float (&f)[8]) {
+  Vec8<ST> wv, mv, vv;
+  u32 pw[4];
+  wv.load(t.w, i);
+  const v4i gv = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(t.g) + i);
+  mv.load(t.m, i);
+  vv.load(t.v, i);
+  typedef typename AdamMath<ST>::T T;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    T pl = wv.lo(j), ph = wv.hi(j);
+    const T gl = T(gs) * T(__uint_as_float((u32)gv[j] << 16)), gh = T(gs) * T(__uint_as_float((u32)gv[j] & 0xFFFF0000u));
+    T ml = mv.lo(j), mh = mv.hi(j);
+    T vl = vv.lo(j), vh = vv.hi(j);
+    adam_one(pl, gl, ml, vl, a);
+    adam_one(ph, gh, mh, vh, a);
+    if constexpr (sizeof(ST) == 4) {
+      wv.set(j, (float)pl, (float)ph);           // the master: the fp64 result rounded once to fp32 ...
+      pw[j] = pack_bf16x2(wv.lo(j), wv.hi(j));   // ... and p = RNE_bf16 of that STORED value
+    } else {
+      pw[j] = pack_bf16x2(pl, ph);
+      wv.x[j] = (int)pw[j];
+    }
+    mv.set(j, (float)ml, (float)mh);
+    vv.set(j, (float)vl, (float)vh);
+    f[2 * j] = __uint_as_float(pw[j] << 16);
+    f[2 * j + 1] = __uint_as_float(pw[j] & 0xFFFF0000u);
+  }
+  wv.store(t.w, i);
+  if constexpr (sizeof(ST) == 4) {
+    const v4i pv = {(int)pw[0], (int)pw[1], (int)pw[2], (int)pw[3]};
+    reinterpret_cast<v4i*>(t.p)[i] = pv;
+  }
+  mv.store(t.m, i);
+  vv.store(t.v, i);
+}
+
+// Flat walk of one chunk: elements [chunk * chunk_elems, + chunk_elems) of the tensor, 8 per lane where every array is 16-byte
+// aligned, one per lane otherwise and on the tail.
+template <typename ST>
+__device__ __forceinline__ void adam_flat_chunk(const AdamPtrs<ST>& t, int64_t n, int chunk, int chunk_elems, float gs,
+                                                const AdamArgs& a, int tid) {
+  const int64_t lo = (int64_t)chunk * chunk_elems, hi = min(n, lo + chunk_elems);
   int64_t done = lo;
-  if (aligned) {
+  if (t.aligned16()) {
     const int64_t v0 = lo >> 3, v1 = hi >> 3;
     for (int64_t i = v0 + tid; i < v1; i += 256) {
-      v4i pv = reinterpret_cast<const v4i*>(p)[i];
-      const v4i gv = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(g) + i);
-      v4i mv = reinterpret_cast<const v4i*>(m)[i];
-      v4i vv = reinterpret_cast<const v4i*>(v)[i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float pl = __uint_as_float((u32)pv[j] << 16), ph = __uint_as_float((u32)pv[j] & 0xFFFF0000u);
-        const float gl = gs * __uint_as_float((u32)gv[j] << 16), gh = gs * __uint_as_float((u32)gv[j] & 0xFFFF0000u);
-        float ml = __uint_as_float((u32)mv[j] << 16), mh = __uint_as_float((u32)mv[j] & 0xFFFF0000u);
-        float vl = __uint_as_float((u32)vv[j] << 16), vh = __uint_as_float((u32)vv[j] & 0xFFFF0000u);
-        adam_one(pl, gl, ml, vl, a);
-        adam_one(ph, gh, mh, vh, a);
-        pv[j] = (int)pack_bf16x2(pl, ph);
-        mv[j] = (int)pack_bf16x2(ml, mh);
-        vv[j] = (int)pack_bf16x2(vl, vh);
-      }
-      reinterpret_cast<v4i*>(p)[i] = pv;
-      reinterpret_cast<v4i*>(m)[i] = mv;
-      reinterpret_cast<v4i*>(v)[i] = vv;
+      float f[8];
+      adam_vec8(t, i, gs, a, f);
     }
     done = v1 << 3;
   }
   for (int64_t k = done + tid; k < hi; k += 256) {
-    float pf = bf16_bits_to_float(p[k]), mf = bf16_bits_to_float(m[k]), vf = bf16_bits_to_float(v[k]);
-    adam_one(pf, gs * bf16_bits_to_float(g[k]), mf, vf, a);
-    p[k] = (uint16_t)float_to_bf16_bits(pf);
-    m[k] = (uint16_t)float_to_bf16_bits(mf);
-    v[k] = (uint16_t)float_to_bf16_bits(vf);
+    typedef typename AdamMath<ST>::T T;
+    T pf = state_load(t.w, k), mf = state_load(t.m, k), vf = state_load(t.v, k);
+    adam_one(pf, T(gs) * T(bf16_bits_to_float(t.g[k])), mf, vf, a);
+    state_store(t.w, k, (float)pf);
+    if constexpr (sizeof(ST) == 4) t.p[k] = (uint16_t)float_to_bf16_bits((float)pf);
+    state_store(t.m, k, (float)mf);
+    state_store(t.v, k, (float)vf);
   }
+}
+
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
+                                                          int chunk_elems, const float* __restrict__ grad_scale, AdamArgs a) {
+  const ChunkRef cr = chunks[blockIdx.x];
+  const AdamPtrs<uint16_t> t(tab, T, cr.tensor);
+  const int64_t n = tab[(int64_t)4 * T + cr.tensor];
+  const float gs = grad_scale ? *grad_scale : 1.0f;
+  adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, threadIdx.x);
 }
 
 // AdamW + FP8 weight cast in one pass (the weight-cast hand-off): under delayed scaling the scale the NEXT
@@ -227,54 +325,19 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restr
 // (y = sat(float(bf16) * scale), amax = max |bf16|), into y [rows, ld_y] and the transposed copy yT [cols, ld_yT].
 // Tensors without a sink (cols == 0) take the flat path of adamw_multi_kernel.  Table rows (int64 each, T columns):
 //   0 p  1 g  2 exp_avg  3 exp_avg_sq  4 numel  5 cols  6 y  7 yT  8 ld_y  9 ld_yT  10 scale ptr  11 amax ptr
+//   12 fp32 master weight (ST = float only: rows 2, 3 are then fp32 too and p is output only)
+template <typename ST>
 __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
                                                                int chunk_elems, const float* __restrict__ grad_scale, AdamArgs a) {
   __shared__ float s_amax[4];
   const ChunkRef cr = chunks[blockIdx.x];
-  uint16_t* p = reinterpret_cast<uint16_t*>(tab[cr.tensor]);
-  const uint16_t* g = reinterpret_cast<const uint16_t*>(tab[(int64_t)1 * T + cr.tensor]);
-  uint16_t* m = reinterpret_cast<uint16_t*>(tab[(int64_t)2 * T + cr.tensor]);
-  uint16_t* v = reinterpret_cast<uint16_t*>(tab[(int64_t)3 * T + cr.tensor]);
+  const AdamPtrs<ST> t(tab, T, cr.tensor);
   const int64_t n = tab[(int64_t)4 * T + cr.tensor];
   const int64_t cols = tab[(int64_t)5 * T + cr.tensor];
   const float gs = grad_scale ? *grad_scale : 1.0f;
   const int tid = threadIdx.x;
-  if (cols == 0) {  // flat chunk (same arithmetic and traversal as adamw_multi_kernel)
-    const int64_t lo = (int64_t)cr.chunk * chunk_elems, hi = min(n, lo + chunk_elems);
-    const bool aligned = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
-    int64_t done = lo;
-    if (aligned) {
-      const int64_t v0 = lo >> 3, v1 = hi >> 3;
-      for (int64_t i = v0 + tid; i < v1; i += 256) {
-        v4i pv = reinterpret_cast<const v4i*>(p)[i];
-        const v4i gv = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(g) + i);
-        v4i mv = reinterpret_cast<const v4i*>(m)[i];
-        v4i vv = reinterpret_cast<const v4i*>(v)[i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float pl = __uint_as_float((u32)pv[j] << 16), ph = __uint_as_float((u32)pv[j] & 0xFFFF0000u);
-          const float gl = gs * __uint_as_float((u32)gv[j] << 16), gh = gs * __uint_as_float((u32)gv[j] & 0xFFFF0000u);
-          float ml = __uint_as_float((u32)mv[j] << 16), mh = __uint_as_float((u32)mv[j] & 0xFFFF0000u);
-          float vl = __uint_as_float((u32)vv[j] << 16), vh = __uint_as_float((u32)vv[j] & 0xFFFF0000u);
-          adam_one(pl, gl, ml, vl, a);
-          adam_one(ph, gh, mh, vh, a);
-          pv[j] = (int)pack_bf16x2(pl, ph);
-          mv[j] = (int)pack_bf16x2(ml, mh);
-          vv[j] = (int)pack_bf16x2(vl, vh);
-        }
-        reinterpret_cast<v4i*>(p)[i] = pv;
-        reinterpret_cast<v4i*>(m)[i] = mv;
-        reinterpret_cast<v4i*>(v)[i] = vv;
-      }
-      done = v1 << 3;
-    }
-    for (int64_t k = done + tid; k < hi; k += 256) {
-      float pf = bf16_bits_to_float(p[k]), mf = bf16_bits_to_float(m[k]), vf = bf16_bits_to_float(v[k]);
-      adam_one(pf, gs * bf16_bits_to_float(g[k]), mf, vf, a);
-      p[k] = (uint16_t)float_to_bf16_bits(pf);
-      m[k] = (uint16_t)float_to_bf16_bits(mf);
-      v[k] = (uint16_t)float_to_bf16_bits(vf);
-    }
+  if (cols == 0) {  // flat chunk (the walk of adamw_multi_kernel)
+    adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, tid);
     return;
   }
   // tile of a weight with an FP8 sink
@@ -294,30 +357,8 @@ __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __
     u32 lo[8], hi[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const int64_t idx = ((r0 + i) * cols + c0) >> 3;
-      v4i pv = reinterpret_cast<const v4i*>(p)[idx];
-      const v4i gv = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(g) + idx);
-      v4i mv = reinterpret_cast<const v4i*>(m)[idx];
-      v4i vv = reinterpret_cast<const v4i*>(v)[idx];
-      float f[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float pl = __uint_as_float((u32)pv[j] << 16), ph = __uint_as_float((u32)pv[j] & 0xFFFF0000u);
-        const float gl = gs * __uint_as_float((u32)gv[j] << 16), gh = gs * __uint_as_float((u32)gv[j] & 0xFFFF0000u);
-        float ml = __uint_as_float((u32)mv[j] << 16), mh = __uint_as_float((u32)mv[j] & 0xFFFF0000u);
-        float vl = __uint_as_float((u32)vv[j] << 16), vh = __uint_as_float((u32)vv[j] & 0xFFFF0000u);
-        adam_one(pl, gl, ml, vl, a);
-        adam_one(ph, gh, mh, vh, a);
-        const u32 pw = pack_bf16x2(pl, ph);
-        pv[j] = (int)pw;
-        mv[j] = (int)pack_bf16x2(ml, mh);
-        vv[j] = (int)pack_bf16x2(vl, vh);
-        f[2 * j] = __uint_as_float(pw << 16);          // the ROUNDED weight: what the next forward's cast would read
-        f[2 * j + 1] = __uint_as_float(pw & 0xFFFF0000u);
-      }
-      reinterpret_cast<v4i*>(p)[idx] = pv;
-      reinterpret_cast<v4i*>(m)[idx] = mv;
-      reinterpret_cast<v4i*>(v)[idx] = vv;
+      float f[8];  // the ROUNDED weight: what the next forward's cast would read
+      adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) amax = fmaxf(amax, (f[j] != f[j]) ? 0.0f : fabsf(f[j]));
       lo[i] = cvt4_fp8<MI_FMT_E4M3>(f[0] * scale, f[1] * scale, f[2] * scale, f[3] * scale);
@@ -368,56 +409,20 @@ __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __
 // mxfp8_quant_kernel's, operation for operation (bitwise the bytes mi_mxfp8_quantize would produce from the updated weight).
 // Table rows (int64 each, T columns):
 //   0 p  1 g  2 exp_avg  3 exp_avg_sq  4 numel  5 cols (0 = no sink: flat path)  6 y_row  7 s_row  8 y_colT  9 s_colT
-//   10 ldr (rows of the whole operand the tensor is a row-block of)  11 unused
+//   10 ldr (rows of the whole operand the tensor is a row-block of)  11 unused  12 fp32 master weight (ST = float only)
 // y_row / s_row / y_colT / s_colT point at the tensor's first row inside the operand's buffers: y_row [rows, cols],
 // s_row [cols/32, ldr], y_colT [cols, ldr], s_colT [rows/32, cols].
+template <typename ST>
 __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
                                                                  int chunk_elems, const float* __restrict__ grad_scale, AdamArgs a) {
   const ChunkRef cr = chunks[blockIdx.x];
-  uint16_t* p = reinterpret_cast<uint16_t*>(tab[cr.tensor]);
-  const uint16_t* g = reinterpret_cast<const uint16_t*>(tab[(int64_t)1 * T + cr.tensor]);
-  uint16_t* m = reinterpret_cast<uint16_t*>(tab[(int64_t)2 * T + cr.tensor]);
-  uint16_t* v = reinterpret_cast<uint16_t*>(tab[(int64_t)3 * T + cr.tensor]);
+  const AdamPtrs<ST> t(tab, T, cr.tensor);
   const int64_t n = tab[(int64_t)4 * T + cr.tensor];
   const int64_t cols = tab[(int64_t)5 * T + cr.tensor];
   const float gs = grad_scale ? *grad_scale : 1.0f;
   const int tid = threadIdx.x;
-  if (cols == 0) {  // flat chunk (same arithmetic and traversal as adamw_multi_kernel)
-    const int64_t lo = (int64_t)cr.chunk * chunk_elems, hi = min(n, lo + chunk_elems);
-    const bool aligned = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
-    int64_t done = lo;
-    if (aligned) {
-      const int64_t v0 = lo >> 3, v1 = hi >> 3;
-      for (int64_t i = v0 + tid; i < v1; i += 256) {
-        v4i pv = reinterpret_cast<const v4i*>(p)[i];
-        const v4i gv = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(g) + i);
-        v4i mv = reinterpret_cast<const v4i*>(m)[i];
-        v4i vv = reinterpret_cast<const v4i*>(v)[i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float pl = __uint_as_float((u32)pv[j] << 16), ph = __uint_as_float((u32)pv[j] & 0xFFFF0000u);
-          const float gl = gs * __uint_as_float((u32)gv[j] << 16), gh = gs * __uint_as_float((u32)gv[j] & 0xFFFF0000u);
-          float ml = __uint_as_float((u32)mv[j] << 16), mh = __uint_as_float((u32)mv[j] & 0xFFFF0000u);
-          float vl = __uint_as_float((u32)vv[j] << 16), vh = __uint_as_float((u32)vv[j] & 0xFFFF0000u);
-          adam_one(pl, gl, ml, vl, a);
-          adam_one(ph, gh, mh, vh, a);
-          pv[j] = (int)pack_bf16x2(pl, ph);
-          mv[j] = (int)pack_bf16x2(ml, mh);
-          vv[j] = (int)pack_bf16x2(vl, vh);
-        }
-        reinterpret_cast<v4i*>(p)[i] = pv;
-        reinterpret_cast<v4i*>(m)[i] = mv;
-        reinterpret_cast<v4i*>(v)[i] = vv;
-      }
-      done = v1 << 3;
-    }
-    for (int64_t k = done + tid; k < hi; k += 256) {
-      float pf = bf16_bits_to_float(p[k]), mf = bf16_bits_to_float(m[k]), vf = bf16_bits_to_float(v[k]);
-      adam_one(pf, gs * bf16_bits_to_float(g[k]), mf, vf, a);
-      p[k] = (uint16_t)float_to_bf16_bits(pf);
-      m[k] = (uint16_t)float_to_bf16_bits(mf);
-      v[k] = (uint16_t)float_to_bf16_bits(vf);
-    }
+  if (cols == 0) {  // flat chunk (the walk of adamw_multi_kernel)
+    adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, tid);
     return;
   }
   uint8_t* y_row = reinterpret_cast<uint8_t*>(tab[(int64_t)6 * T + cr.tensor]);
@@ -438,29 +443,7 @@ __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* 
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     if (active) {
-      const int64_t idx = ((r0 + i) * cols + c0) >> 3;
-      v4i pv = reinterpret_cast<const v4i*>(p)[idx];
-      const v4i gv = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(g) + idx);
-      v4i mv = reinterpret_cast<const v4i*>(m)[idx];
-      v4i vv = reinterpret_cast<const v4i*>(v)[idx];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float pl = __uint_as_float((u32)pv[j] << 16), ph = __uint_as_float((u32)pv[j] & 0xFFFF0000u);
-        const float gl = gs * __uint_as_float((u32)gv[j] << 16), gh = gs * __uint_as_float((u32)gv[j] & 0xFFFF0000u);
-        float ml = __uint_as_float((u32)mv[j] << 16), mh = __uint_as_float((u32)mv[j] & 0xFFFF0000u);
-        float vl = __uint_as_float((u32)vv[j] << 16), vh = __uint_as_float((u32)vv[j] & 0xFFFF0000u);
-        adam_one(pl, gl, ml, vl, a);
-        adam_one(ph, gh, mh, vh, a);
-        const u32 pw = pack_bf16x2(pl, ph);
-        pv[j] = (int)pw;
-        mv[j] = (int)pack_bf16x2(ml, mh);
-        vv[j] = (int)pack_bf16x2(vl, vh);
-        f[i][2 * j] = __uint_as_float(pw << 16);  // the ROUNDED weight: what the next forward's quantiser would read
-        f[i][2 * j + 1] = __uint_as_float(pw & 0xFFFF0000u);
-      }
-      reinterpret_cast<v4i*>(p)[idx] = pv;
-      reinterpret_cast<v4i*>(m)[idx] = mv;
-      reinterpret_cast<v4i*>(v)[idx] = vv;
+      adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, f[i]);  // the ROUNDED weight: what the next forward's quantiser would read
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) f[i][j] = 0.0f;
@@ -627,7 +610,7 @@ extern "C" int mi_adamw_cast_bf16_multi(const int64_t* table, int n_tensors, con
                                         int64_t step, void* stream) {
   MI_CHECK_ARG(table && chunks, "mi_adamw_cast_bf16_multi: null pointer");
   MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 1 && chunk_elems >= 8 && chunk_elems % 8 == 0 && step >= 1, "mi_adamw_cast_bf16_multi: bad sizes");
-  hipLaunchKernelGGL(mi::adamw_cast_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
+  hipLaunchKernelGGL(mi::adamw_cast_multi_kernel<uint16_t>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
                      (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, make_adam_args(lr, beta1, beta2, eps, weight_decay, step));
   MI_CHECK_LAUNCH("mi_adamw_cast_bf16_multi launch");
   return MI_OK;
@@ -638,9 +621,30 @@ extern "C" int mi_adamw_mxcast_bf16_multi(const int64_t* table, int n_tensors, c
                                           int64_t step, void* stream) {
   MI_CHECK_ARG(table && chunks, "mi_adamw_mxcast_bf16_multi: null pointer");
   MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 1 && chunk_elems >= 8 && chunk_elems % 8 == 0 && step >= 1, "mi_adamw_mxcast_bf16_multi: bad sizes");
-  hipLaunchKernelGGL(mi::adamw_mxcast_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
+  hipLaunchKernelGGL(mi::adamw_mxcast_multi_kernel<uint16_t>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
                      (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, make_adam_args(lr, beta1, beta2, eps, weight_decay, step));
   MI_CHECK_LAUNCH("mi_adamw_mxcast_bf16_multi launch");
+  return MI_OK;
+}
+
+// fp32 optimiser state: the walks, the arithmetic and the FP8 emitters of the two kernels above, instantiated for an fp32 master
+// weight (table row 12) and fp32 moments.  sink_kind 0 = the per-tensor table layout, 1 = the MXFP8 one.
+extern "C" int mi_adamw_f32_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
+                                  const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                  int64_t step, int sink_kind, void* stream) {
+  MI_CHECK_ARG(table && chunks, "mi_adamw_f32_multi: null pointer");
+  MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 0 && step >= 1, "mi_adamw_f32_multi: bad sizes");
+  MI_CHECK_ARG(chunk_elems >= 8 && chunk_elems % 8 == 0, "mi_adamw_f32_multi: chunk_elems must be a positive multiple of 8");
+  MI_CHECK_ARG(sink_kind == 0 || sink_kind == 1, "mi_adamw_f32_multi: sink_kind must be 0 (per-tensor FP8) or 1 (MXFP8)");
+  if (n_chunks == 0) return MI_OK;
+  const mi::AdamArgs a = make_adam_args(lr, beta1, beta2, eps, weight_decay, step);
+  if (sink_kind == 0)
+    hipLaunchKernelGGL(mi::adamw_cast_multi_kernel<float>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table,
+                       n_tensors, (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, a);
+  else
+    hipLaunchKernelGGL(mi::adamw_mxcast_multi_kernel<float>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table,
+                       n_tensors, (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, a);
+  MI_CHECK_LAUNCH("mi_adamw_f32_multi launch");
   return MI_OK;
 }
 

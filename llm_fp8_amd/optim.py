@@ -2,7 +2,8 @@
 (train_fp8.py:288-291) as two streaming HIP passes: one reproducible squared-norm reduction over the gradients and one
 AdamW update with the clip coefficient folded in (the gradients are never rescaled in place), each ONE multi-tensor launch
 per parameter group (device tables of tensor addresses + a chunk list).  bf16 parameters with bf16
-`exp_avg` / `exp_avg_sq`, fp32 math -- the state layout of torch's fused AdamW, so `state_dict()` is interchangeable."""
+`exp_avg` / `exp_avg_sq`, fp32 math -- the state layout of torch's fused AdamW, so `state_dict()` is interchangeable.
+`state_dtype=torch.float32` keeps an fp32 master weight and fp32 moments behind the same passes instead (`ClippedAdamW`)."""
 from __future__ import annotations
 
 import os
@@ -15,10 +16,30 @@ from .pytorch.module import stepped_tensor
 
 
 class ClippedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm: Optional[float] = 1.0):
+    """`state_dtype` is the precision the optimiser state is KEPT in between steps (a step is evaluated in fp32 for bf16 state and in fp64 for fp32 state).
+
+    `torch.bfloat16` (default): torch's fused-AdamW layout.  The updated weight is rounded straight back into the bf16 parameter,
+    so an update below half a bf16 ulp of the weight (most of them at lr ~ 1e-5) is lost, and `exp_avg_sq` stalls likewise.
+
+    `torch.float32`: per parameter an fp32 `master` weight and fp32 `exp_avg` / `exp_avg_sq` (+8 bytes per parameter).  Every
+    parameter of the optimiser is handled this way.  The update reads and writes the master; the bf16 parameter becomes an
+    OUTPUT of the step, `p = RNE_bf16(master)`, and the FP8 copies of the weight sinks are quantised from that rounded value
+    as in the default mode.  The master is seeded from `p.float()` when the state is created, and again whenever somebody else
+    wrote the parameter since this optimiser's last step (a checkpoint load, `copy_` from another model): that is detected by
+    `p._version`, and such a write DISCARDS the fp32 residue of that tensor -- the step starts from the value written.  A write
+    that autograd's version counter does not see (`p.data.copy_(...)`, a raw kernel) is not detected, here as for the FP8 weight
+    copies: the next step overwrites it from the master.  `load_state_dict` keeps the three tensors in fp32 and trusts a loaded
+    master (load the model's weights BEFORE the optimiser state, or the load counts as an external write)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm: Optional[float] = 1.0,
+                 state_dtype: torch.dtype = torch.bfloat16):
+        if state_dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"ClippedAdamW: state_dtype must be torch.bfloat16 or torch.float32, not {state_dtype!r}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self.max_grad_norm = max_grad_norm
+        self.state_dtype = state_dtype
+        self._f32 = state_dtype == torch.float32
         self._plans = {}
         self.last_grad_norm: Optional[torch.Tensor] = None
 
@@ -54,10 +75,11 @@ class ClippedAdamW(torch.optim.Optimizer):
         return s
 
     def _aligned16(self, p) -> bool:
-        """The tile path of the *_cast kernels issues 16-byte loads / stores on the parameter, its gradient and both moments
-        unconditionally; a tensor at an odd storage offset (a loaded optimiser state, a `.grad` view) takes the flat path."""
+        """The tile path of the *_cast kernels issues 16-byte loads / stores on the parameter, its gradient, both moments and
+        (fp32 state) the master unconditionally; a tensor at an odd storage offset (a loaded optimiser state, a `.grad` view)
+        takes the flat path."""
         st = self.state.get(p, {})
-        others = (p.grad, st.get("exp_avg"), st.get("exp_avg_sq"))
+        others = (p.grad, st.get("exp_avg"), st.get("exp_avg_sq"), st.get("master") if self._f32 else None)
         return p.data_ptr() % 16 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in others)
 
     def _mx_sink_of(self, p):
@@ -99,15 +121,18 @@ class ClippedAdamW(torch.optim.Optimizer):
                     tr, tc = (p.shape[0] + self.TILE - 1) // self.TILE, (p.shape[1] + self.TILE - 1) // self.TILE
                     refs_cast.extend((t, c) for c in range(tr * tc))
             chunks = torch.tensor(refs, dtype=torch.int32).to(dev)
-            any_sink = any(s is not None for s in sinks)
+            any_sink = self._f32 or any(s is not None for s in sinks)  # mi_adamw_f32_multi always walks the cast list
+            nrows = 13 if self._f32 else 12
             plan = {"sizes": sizes, "sink_sig": sink_sig, "chunks": chunks, "n_chunks": len(refs), "addr": None,
                     "chunks_cast": torch.tensor(refs_cast, dtype=torch.int32).to(dev) if any_sink else None, "n_chunks_cast": len(refs_cast),
-                    "table": torch.empty((12, len(sizes)), dtype=torch.int64, device=dev),
-                    "host": [torch.empty((12, len(sizes)), dtype=torch.int64).pin_memory() for _ in range(2)], "flip": 0,
+                    "table": torch.empty((nrows, len(sizes)), dtype=torch.int64, device=dev),
+                    "host": [torch.empty((nrows, len(sizes)), dtype=torch.int64).pin_memory() for _ in range(2)], "flip": 0,
                     "uploaded": [None, None],
                     "partials": torch.empty(len(refs), dtype=torch.float64, device=dev)}
             self._plans[key] = plan
         rows = [[], [], [], [], list(sizes), [], [], [], [], [], [], []]
+        if self._f32:
+            rows.append([self.state[p]["master"].data_ptr() for _, p in group_items])  # 12: the fp32 master weight
         for (_, p), s in zip(group_items, sinks):
             st = self.state[p]
             rows[0].append(p.data_ptr())
@@ -157,6 +182,45 @@ class ClippedAdamW(torch.optim.Optimizer):
             plan["addr"] = rows
         return plan
 
+    def _seed_master(self, p, state):
+        """fp32 state: the master exists, is fp32, and goes with the parameter as it is now.  An external write of `p` since our
+        last step (its version moved) re-seeds the master IN PLACE from the value written: the fp32 residue is gone."""
+        master = state.get("master")
+        if master is None or master.dtype != torch.float32 or master.shape != p.shape or master.device != p.device:
+            state["master"] = p.detach().to(torch.float32, memory_format=torch.preserve_format, copy=True)
+        elif state.get("master_version") != p._version:
+            master.copy_(p.detach())
+        else:
+            return
+        state["master_version"] = p._version
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict casts every floating state tensor to the PARAMETER's dtype, which would turn an
+        fp32 master and fp32 moments back into bf16.  fp32 mode takes the three tensors from `state_dict` itself, in fp32 (a bf16-mode
+        state is upcast and the master seeded from `p`); bf16 mode keeps torch's behaviour and drops the master of an fp32-mode
+        state.  A loaded master is trusted: it is taken to go with the parameters as they are at this moment."""
+        super().load_state_dict(state_dict)
+        if not self._f32:
+            for st in self.state.values():
+                st.pop("master", None)
+                st.pop("master_version", None)
+            return
+        saved_ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        ours = [p for g in self.param_groups for p in g["params"]]
+        for pid, p in zip(saved_ids, ours):
+            src = state_dict["state"].get(pid)
+            if src is None:
+                continue
+            st = self.state[p]
+            for k in ("exp_avg", "exp_avg_sq", "master"):
+                if torch.is_tensor(src.get(k)):
+                    st[k] = src[k].to(device=p.device, dtype=torch.float32)
+            if "master" in st:
+                st["master_version"] = p._version
+            else:
+                self._seed_master(p, st)
+
     @torch.no_grad()
     def step(self, closure=None):
         assert closure is None
@@ -164,6 +228,7 @@ class ClippedAdamW(torch.optim.Optimizer):
         if not items:
             return None
         lib = _lib.load()
+        f32_step = _lib.require("mi_adamw_f32_multi", "ClippedAdamW(state_dtype=torch.float32)") if self._f32 else None
         dev = items[0][1].device
         st = torch.cuda.current_stream().cuda_stream
         by_group = {}
@@ -171,8 +236,13 @@ class ClippedAdamW(torch.optim.Optimizer):
             state = self.state[p]
             if not state:
                 state["step"] = 0
-                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["exp_avg"] = torch.zeros_like(p, dtype=self.state_dtype, memory_format=torch.preserve_format)
+                state["exp_avg_sq"] = torch.zeros_like(p, dtype=self.state_dtype, memory_format=torch.preserve_format)
+            if self._f32:
+                for k in ("exp_avg", "exp_avg_sq"):  # the kernel reads 4 bytes per element: never hand it a narrower moment
+                    if state[k].dtype != torch.float32:
+                        state[k] = state[k].to(torch.float32)
+                self._seed_master(p, state)
             if torch.is_tensor(state["step"]):  # a state_dict written by torch's AdamW keeps `step` as a tensor
                 state["step"] = int(state["step"].item())
             if not p.grad.is_contiguous():
@@ -226,7 +296,12 @@ class ClippedAdamW(torch.optim.Optimizer):
             for _, p in gi:
                 self.state[p]["step"] += 1
             b1, b2 = group["betas"]
-            if plan["chunks_cast"] is not None:  # some weights of this partition have FP8 sinks: update + cast in one pass
+            if self._f32:  # fp32 master + moments: one entry point, the sink layout of the partition as an argument
+                rc = f32_step(plan["table"].data_ptr(), len(gi), plan["chunks_cast"].data_ptr(), plan["n_chunks_cast"], self.CHUNK,
+                              coef_ptr, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
+                              int(self.state[gi[0][1]]["step"]), 1 if plan["mx"] else 0, st)
+                _lib.check(rc, "mi_adamw_f32_multi")
+            elif plan["chunks_cast"] is not None:  # some weights of this partition have FP8 sinks: update + cast in one pass
                 fn = lib.mi_adamw_mxcast_bf16_multi if plan["mx"] else lib.mi_adamw_cast_bf16_multi
                 rc = fn(plan["table"].data_ptr(), len(gi), plan["chunks_cast"].data_ptr(), plan["n_chunks_cast"],
                                                   self.CHUNK, coef_ptr, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
@@ -239,6 +314,9 @@ class ClippedAdamW(torch.optim.Optimizer):
                 _lib.check(rc, "mi_adamw_bf16_multi")
             # the kernels write through raw addresses: tell autograd (and every cache keyed on `_version`, wcast.py)
             torch.autograd.graph.increment_version([p for _, p in gi])
+            if self._f32:
+                for _, p in gi:
+                    self.state[p]["master_version"] = p._version  # a later mismatch = somebody else wrote p: re-seed
             touched.update(id(p) for _, p in gi)
             for s in plan["sinks"]:
                 if s is not None:

@@ -45,6 +45,7 @@ class TrainingConfig:
     vocab_size: Optional[int] = None
     output_dir: Optional[str] = None      # ModelSaver.save_model (train_fp8.py:657-681)
     load_dir: Optional[str] = None        # local checkpoint directory (from_pretrained_local, te_llama.py:100-178)
+    optimizer_state: Optional[str] = None  # "bf16" | "fp32" (optim.ClippedAdamW state_dtype); None: resolve_optimizer_state
 
 
 def create_model(cfg: TrainingConfig, device) -> torch.nn.Module:
@@ -111,17 +112,33 @@ def prepare_model(model: torch.nn.Module, cfg: TrainingConfig) -> torch.nn.Modul
     return model
 
 
+OPTIMIZER_STATES = ("bf16", "fp32")
+
+
+def resolve_optimizer_state(cfg_or_value=None) -> str:
+    """Precision the optimiser state is kept in: `TrainingConfig.optimizer_state` / `--optimizer_state`, else the environment
+    variable LLM_FP8_AMD_OPT_STATE (so a worker script can be driven in either mode unedited), else `bf16` (the reference's
+    layout: torch's fused AdamW on bf16 parameters).  `fp32` = fp32 master weights and moments (optim.ClippedAdamW)."""
+    v = getattr(cfg_or_value, "optimizer_state", cfg_or_value)
+    if v is None:
+        v = os.environ.get("LLM_FP8_AMD_OPT_STATE") or "bf16"
+    if v not in OPTIMIZER_STATES:
+        raise ValueError(f"optimizer state {v!r}: one of {OPTIMIZER_STATES}")
+    return v
+
+
 # auto: replicated (gradient arena) while the replicated training state fits the device, else fsdp_fp8; replicated:
 # distributed.GradArenaDP; fsdp_fp8: distributed.ShardedFP8DP (FULL_SHARD counterpart with FP8 all-gather); fsdp_full / ddp: the
 # torch wrappers the reference uses (train_multi_gpu.py:414-445, :447-470); none: no wrapper
 SHARDING_MODES = ("auto", "replicated", "fsdp_fp8", "fsdp_full", "ddp", "none")
 
 
-def resolve_sharding_mode(mode: str, model: torch.nn.Module, device) -> str:
+def resolve_sharding_mode(mode: str, model: torch.nn.Module, device, optimizer_state: Optional[str] = None) -> str:
     """`auto` (DistributedConfig._auto_detect_sharding, train_multi_gpu.py:137-146, picks FSDP FULL_SHARD whenever there is
     more than one GPU): here the run shards only when it has to -- the replicated state of every BASELINE.json model fits
     one MI355X (3B: 39 GB, 8B: 96 GB of 288 GB), so `auto` = gradient-arena data parallelism (distributed.GradArenaDP),
-    and the full-shard mode (`fsdp_fp8`) only for a model whose replicated state would take more than half of the device.  An explicit
+    and the full-shard mode (`fsdp_fp8`) only for a model whose replicated state would take more than half of the device
+    (`optimizer_state` "fp32" adds 8 bytes per trainable parameter to that state: +25.6 GB for 3B, +64 GB for 8B).  An explicit
     ddp / fsdp_full / replicated request is honoured even at world size 1 (rehearsal on a one-GPU box)."""
     import torch.distributed as dist
     if mode != "auto":
@@ -131,7 +148,7 @@ def resolve_sharding_mode(mode: str, model: torch.nn.Module, device) -> str:
     from .distributed import fits_replicated
     # does not fit: the FULL_SHARD counterpart with FP8 all-gathers (distributed.ShardedFP8DP; masters, gradients and AdamW
     # moments of every GEMM weight at 1/world per rank), not torch FSDP (bf16 gathers in forward and backward, a cast after each)
-    return "replicated" if fits_replicated(model, device) else "fsdp_fp8"
+    return "replicated" if fits_replicated(model, device, optimizer_state=resolve_optimizer_state(optimizer_state)) else "fsdp_fp8"
 
 
 def _single_process(model: torch.nn.Module, device) -> torch.nn.Module:
@@ -147,7 +164,7 @@ def wrap_distributed(model: torch.nn.Module, cfg: TrainingConfig, device) -> tor
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()) or cfg.sharding_mode == "none":
         return _single_process(model, device)
-    mode = resolve_sharding_mode(cfg.sharding_mode, model, device)
+    mode = resolve_sharding_mode(cfg.sharding_mode, model, device, cfg.optimizer_state)
     if mode == "none":
         return _single_process(model, device)
     if mode == "replicated":
@@ -187,11 +204,20 @@ def create_optimizer(model, cfg: TrainingConfig):
         # registered: the decoder weights' gradients would never enter the norm; and no FP8 copy would be kept current
         raise RuntimeError("LLM_FP8_AMD_TORCH_ADAMW=1 is not supported with --sharding_mode fsdp_fp8 (ShardedFP8DP): its row "
                            "shards need ClippedAdamW's clip over the ranks -- unset the variable or use another sharding mode")
+    opt_state = resolve_optimizer_state(cfg)
     if (fused and not wrapped and all(p.dtype == torch.bfloat16 for p in params)
             and os.environ.get("LLM_FP8_AMD_TORCH_ADAMW") != "1"):
         from .optim import ClippedAdamW
-        opt = ClippedAdamW(groups if groups is not None else params, lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm)
+        opt = ClippedAdamW(groups if groups is not None else params, lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm,
+                           state_dtype=torch.float32 if opt_state == "fp32" else torch.bfloat16)
     else:
+        if opt_state == "fp32":  # torch's AdamW keeps its state in the parameters' dtype: no silent downgrade to bf16 state
+            why = ("the parameters are not all on the GPU" if not fused else
+                   f"the model is wrapped in {type(model).__name__}" if wrapped else
+                   "LLM_FP8_AMD_TORCH_ADAMW=1 selects torch's AdamW" if os.environ.get("LLM_FP8_AMD_TORCH_ADAMW") == "1" else
+                   "the parameters are not all bf16")
+            raise RuntimeError(f"optimizer_state='fp32' needs ClippedAdamW (fp32 master weights and moments), but {why}: "
+                               "torch.optim.AdamW would be built instead, with its state in the parameters' dtype")
         opt = torch.optim.AdamW(params, lr=cfg.learning_rate, fused=fused)
 
     def lr_lambda(step):
@@ -285,7 +311,7 @@ def setup_distributed():
     return rank, local, world, device
 
 
-def main(argv=None):
+def build_arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="FP8 fine-tuning harness (synthetic data) on llm_fp8_amd")
     ap.add_argument("--model_name", default="meta-llama/Llama-3.2-3B")
     ap.add_argument("--batch_size", type=int, default=16)
@@ -304,12 +330,23 @@ def main(argv=None):
     ap.add_argument("--load_dir", default=None, help="local checkpoint directory (model.safetensors[.index.json]) to start from")
     ap.add_argument("--save_layout", choices=["hf", "te"], default="hf")
     ap.add_argument("--repeat_batch", action="store_true", help="debug: train on one fixed synthetic batch")
-    a = ap.parse_args(argv)
-    cfg = TrainingConfig(model_name=a.model_name, batch_size=a.batch_size, max_seq_length=a.max_seq_length,
+    ap.add_argument("--optimizer_state", choices=OPTIMIZER_STATES, default=None,
+                    help="precision of the AdamW state: bf16 (default; or $LLM_FP8_AMD_OPT_STATE) | fp32 master weights + moments")
+    return ap
+
+
+def config_from_args(a) -> TrainingConfig:
+    return TrainingConfig(model_name=a.model_name, batch_size=a.batch_size, max_seq_length=a.max_seq_length,
                          mixed_precision=a.mixed_precision, fp8_scenario=a.fp8_scenario, use_te=a.use_te,
                          sharding_mode=a.sharding_mode, learning_rate=a.learning_rate,
                          num_hidden_layers=a.num_hidden_layers, vocab_size=a.vocab_size, num_warmup_steps=a.num_warmup_steps,
-                         gradient_accumulation_steps=a.gradient_accumulation_steps, output_dir=a.output_dir, load_dir=a.load_dir)
+                         gradient_accumulation_steps=a.gradient_accumulation_steps, output_dir=a.output_dir, load_dir=a.load_dir,
+                         optimizer_state=a.optimizer_state)
+
+
+def main(argv=None):
+    a = build_arg_parser().parse_args(argv)
+    cfg = config_from_args(a)
     rank, local, world, device = setup_distributed()
     torch.manual_seed(cfg.seed + rank)
     model = prepare_model(create_model(cfg, device), cfg)
