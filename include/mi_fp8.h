@@ -65,9 +65,11 @@ extern "C" {
  *   5  mi_gemm_mxfp8_grouped (a Linear's block-scaled dgrad + wgrad in one persistent launch)
  * Revisions of version 5:
  *   1  mi_adamw_f32_multi (fp32 master weights and moments in the fused AdamW + FP8 cast pass), mi_abi_revision
+ *   2  mi_amax_bf16, mi_amax_norm, mi_amax_swiglu, mi_amax_dswiglu, mi_current_scale (Float8CurrentScaling: the amax of a tensor
+ *      before its cast, and the scale from it)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 1
+#define MI_ABI_REVISION 2
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -348,6 +350,34 @@ int mi_norm_cast(const void* x_bf16, const float* rstd, const void* gamma_bf16, 
 int mi_rmsnorm_bwd(const void* dy_bf16, const void* x_bf16, const float* rstd, const void* gamma_bf16,
                    const void* dres_bf16, void* dx_bf16, float* dgamma_partial, int n_partials, int64_t rows,
                    int64_t cols, void* stream);
+
+/*
+ * Current scaling (ABI 5 revision 2; TE's Float8CurrentScaling): a tensor is quantised with a scale computed from its OWN amax, so
+ * the amax exists before the cast.  An amax pass reads what the matching cast kernel reads and reduces |v|, v being the fp32 value
+ * that kernel multiplies by *scale (same device code, so the same bits):
+ *   mi_amax_bf16     v of mi_cast_amax:                  x[r,c]
+ *   mi_amax_norm     v of mi_norm_cast:                  (x[r,c] * rstd[r]) * gamma[c]
+ *   mi_amax_swiglu   v of mi_swiglu_cast(_bias):         silu(g) * u, g | u = h[r,c] | h[r,F+c] (+ bias, fp32, if bias != NULL)
+ *   mi_amax_dswiglu  v of mi_dswiglu_cast(_bias):        both halves, dact * dsilu(g) * u and dact * silu(g)
+ * The launch has exactly n_partial workgroups (1..1024, the caller's choice) and workgroup i stores partial[i] = max |v| over the
+ * elements it walked, 0 if it walked none: all n_partial entries are written, nothing has to be zeroed first and there are no
+ * atomics.  NaN elements are ignored, an Inf gives Inf (the cast kernels' own amax).  Shapes and alignment as for the matching cast
+ * kernel (rows, cols / F multiples of 8; bf16 inputs, rstd, gamma and bias 16-byte aligned); a violation is MI_ERR_ARG and nothing is
+ * launched.  An empty tensor still launches and writes zeros.
+ *   mi_current_scale (one workgroup): amax = max_i partial[i]; a = amax < amax_epsilon ? amax_epsilon : amax;
+ *     scale = 1 if a == 0 or a is infinite, else fp8_max / a (one IEEE division), FLT_MAX if that is infinite, 1 if it is NaN;
+ *     pow2 != 0 clears the scale's mantissa bits (rounds it down to a power of two); out3 = {amax, scale, 1 / scale}.
+ *   Several amax passes may fill segments of one partial buffer (query | key | value weights forming one operand) and one
+ *   mi_current_scale then covers the whole buffer (n_partial up to 2^20 there).
+ * The casts themselves are the kernels above with `scale` = out3 + 1.
+ */
+int mi_amax_bf16(const void* x_bf16, float* partial, int n_partial, int64_t rows, int64_t cols, void* stream);
+int mi_amax_norm(const void* x_bf16, const float* rstd, const void* gamma_bf16, float* partial, int n_partial, int64_t rows,
+                 int64_t cols, void* stream);
+int mi_amax_swiglu(const void* h_bf16, const void* bias_bf16, float* partial, int n_partial, int64_t rows, int64_t F, void* stream);
+int mi_amax_dswiglu(const void* h_bf16, const void* bias_bf16, const void* dact_bf16, float* partial, int n_partial, int64_t rows,
+                    int64_t F, void* stream);
+int mi_current_scale(const float* partial, int n_partial, float fp8_max, float amax_epsilon, int pow2, float* out3, void* stream);
 
 /*
  * Token cross-entropy on the bf16 logits of the FP8 lm_head (the loss of the reference loop, HF ForCausalLMLoss:

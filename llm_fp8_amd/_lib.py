@@ -13,7 +13,7 @@ LAB_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "bin", "libmi_fp8_l
 MI_FMT_E4M3 = 0
 MI_FMT_E5M2 = 1
 ABI_VERSION = 5
-ABI_REVISION = 1  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
+ABI_REVISION = 2  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -98,6 +98,12 @@ REVISION_SIGNATURES = {
     "mi_abi_revision": [],
     "mi_adamw_f32_multi": [_p, _c_int, _p, _c_int, _c_int, _p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                            ctypes.c_float, _c_i64, _c_int, _p],
+    # revision 2: current scaling (amax passes that write workgroup partials, and the scale kernel)
+    "mi_amax_bf16": [_p, _p, _c_int, _c_i64, _c_i64, _p],
+    "mi_amax_norm": [_p, _p, _p, _p, _c_int, _c_i64, _c_i64, _p],
+    "mi_amax_swiglu": [_p, _p, _p, _c_int, _c_i64, _c_i64, _p],
+    "mi_amax_dswiglu": [_p, _p, _p, _p, _c_int, _c_i64, _c_i64, _p],
+    "mi_current_scale": [_p, _c_int, ctypes.c_float, ctypes.c_float, _c_int, _p, _p],
 }
 SIGNATURES.update(REVISION_SIGNATURES)
 # entry points only the lab build exports (#ifdef MI_DIAG in include/mi_fp8.h)

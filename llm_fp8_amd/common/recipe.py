@@ -27,6 +27,9 @@ class Recipe:
     def delayed(self) -> bool:
         return isinstance(self, DelayedScaling)
 
+    def current(self) -> bool:
+        return isinstance(self, Float8CurrentScaling)
+
 
 @dataclass(frozen=True)
 class DelayedScaling(Recipe):
@@ -68,6 +71,40 @@ class MXFP8BlockScaling(Recipe):
         assert self.fp8_format in (Format.E4M3, Format.E5M2, Format.HYBRID)
         if self.margin != 0:
             raise ValueError("MXFP8BlockScaling margin must be 0")
+
+
+@dataclass(frozen=True)
+class QParams:
+    """How one class of tensors is quantised under Float8CurrentScaling (TE's QParams)."""
+    power_2_scale: bool = False
+    amax_epsilon: float = 0.0
+
+
+@dataclass(frozen=True)
+class MMParams:
+    """TE's MMParams.  Accepted and ignored: the FP8 GEMM here has one accumulation order."""
+    use_split_accumulator: bool = True
+
+
+@dataclass(frozen=True)
+class Float8CurrentScaling(Recipe):
+    """Per-tensor scaling from the live amax: every tensor is quantised with scale = fp8_max / amax of that very tensor, no history
+    (TE's Float8CurrentScaling: same fields and defaults)."""
+    fp8_format: Format = Format.HYBRID
+    fp8_quant_fwd_inp: QParams = QParams(power_2_scale=False, amax_epsilon=0.0)
+    fp8_quant_fwd_weight: QParams = QParams(power_2_scale=False, amax_epsilon=0.0)
+    fp8_quant_bwd_grad: QParams = QParams(power_2_scale=False, amax_epsilon=0.0)
+    fp8_gemm_fprop: MMParams = MMParams(use_split_accumulator=False)
+    fp8_gemm_dgrad: MMParams = MMParams(use_split_accumulator=True)
+    fp8_gemm_wgrad: MMParams = MMParams(use_split_accumulator=True)
+    fp8_dpa: bool = False
+    fp8_mha: bool = False
+
+    def __post_init__(self):
+        assert self.fp8_format in (Format.E4M3, Format.E5M2, Format.HYBRID)
+        for q in (self.fp8_quant_fwd_inp, self.fp8_quant_fwd_weight, self.fp8_quant_bwd_grad):
+            if not (q.amax_epsilon >= 0.0):
+                raise ValueError("amax_epsilon must be non-negative")
 
 
 def fmt_codes(fmt: Format) -> Tuple[int, int]:

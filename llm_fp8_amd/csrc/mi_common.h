@@ -138,6 +138,43 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// The fp32 value `v` a fused cast kernel multiplies by *scale, per element.  The cast kernels (mi_fused.hip) and the amax passes of
+// current scaling (mi_current.hip) both call these: an amax pass must see exactly the value the cast that follows will quantise.
+__device__ __forceinline__ float sigmoidf_(float g) { return 1.0f / (1.0f + __expf(-g)); }
+
+// mi_norm_cast: the two bf16 halves of the packed word `w` of row statistics `rs`, times their gamma
+__device__ __forceinline__ void norm_value2(u32 w, float rs, float g0, float g1, float& v0, float& v1) {
+  v0 = (__uint_as_float(w << 16) * rs) * g0;
+  v1 = (__uint_as_float(w & 0xFFFF0000u) * rs) * g1;
+}
+
+// mi_swiglu_cast(_bias) (MODE 0): v0 = silu(g) * u.  mi_dswiglu_cast(_bias) (MODE 1): v0 = d * dsilu(g) * u (gate half),
+// v1 = d * silu(g) (up half).  For the two bf16 halves of the packed words wg (gate), wu (up), wd (dact); `has_bias` (wave-uniform):
+// the fc1 bias bg[0..1] / bu[0..1] is added, in fp32, to the unpacked gate / up values first.  MODE 0 leaves v1 alone.
+template <int MODE>
+__device__ __forceinline__ void swiglu_value2(u32 wg, u32 wu, u32 wd, bool has_bias, const float* bg, const float* bu, float* v0,
+                                              float* v1) {
+  float g2[2] = {__uint_as_float(wg << 16), __uint_as_float(wg & 0xFFFF0000u)};
+  float u2[2] = {__uint_as_float(wu << 16), __uint_as_float(wu & 0xFFFF0000u)};
+  const float d2[2] = {__uint_as_float(wd << 16), __uint_as_float(wd & 0xFFFF0000u)};
+  if (has_bias) {
+    g2[0] += bg[0];
+    g2[1] += bg[1];
+    u2[0] += bu[0];
+    u2[1] += bu[1];
+  }
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const float sg = sigmoidf_(g2[e]);
+    if (MODE == 0) {
+      v0[e] = g2[e] * sg * u2[e];
+    } else {
+      v0[e] = d2[e] * u2[e] * (sg * (1.0f + g2[e] * (1.0f - sg)));
+      v1[e] = d2[e] * (g2[e] * sg);
+    }
+  }
+}
+
 }  // namespace mi
 // 8-byte FP8 stores of the cast / quantise kernels (one 8 x 8 block per lane: 8 lanes = one 64-byte row segment).
 // MI_NT_Y / MI_NT_YT (build-time, timing experiments): nontemporal stores for the row-major / the transposed copy.

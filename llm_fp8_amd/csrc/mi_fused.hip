@@ -184,8 +184,7 @@ __global__ __launch_bounds__(256) void rope_bwd_cast_kernel(const uint16_t* __re
 }
 
 // ------------------------------------------------------------------------------------------------ SwiGLU (+cast)
-__device__ __forceinline__ float sigmoidf_(float g) { return 1.0f / (1.0f + __expf(-g)); }
-
+// (the per-element value is swiglu_value2, mi_common.h: shared with the amax pass of current scaling)
 // Same tiling as the one-shot cast: a 128x128 tile of the [rows, F] GATE space per workgroup, 8x8 block per lane.
 // MODE 0 (fwd):  in = h [rows, 2F];            val(r,c) = silu(h[r,c]) * h[r,F+c],   c in [0,F)  -> out [rows, F]
 // MODE 1 (bwd):  in = h [rows, 2F], d [rows,F]; val(r,c) = d[r,c]*dsilu(g)*u (c < F) | d[r,c-F]*silu(g) (c >= F) -> out [rows, 2F]
@@ -248,25 +247,7 @@ __global__ __launch_bounds__(256) void swiglu_cast_kernel(const uint16_t* __rest
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const u32 wg = (u32)gv[i][j], wu = (u32)uv[i][j], wd = (u32)dv[i][j];
-          float g2[2] = {__uint_as_float(wg << 16), __uint_as_float(wg & 0xFFFF0000u)};
-          float u2[2] = {__uint_as_float(wu << 16), __uint_as_float(wu & 0xFFFF0000u)};
-          const float d2[2] = {__uint_as_float(wd << 16), __uint_as_float(wd & 0xFFFF0000u)};
-          if (bias != nullptr) {
-            g2[0] += bg[2 * j];
-            g2[1] += bg[2 * j + 1];
-            u2[0] += bu[2 * j];
-            u2[1] += bu[2 * j + 1];
-          }
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const float sg = sigmoidf_(g2[e]);
-            if (MODE == 0) {
-              f[0][2 * j + e] = g2[e] * sg * u2[e];
-            } else {
-              f[0][2 * j + e] = d2[e] * u2[e] * (sg * (1.0f + g2[e] * (1.0f - sg)));
-              f[NOUT - 1][2 * j + e] = d2[e] * (g2[e] * sg);
-            }
-          }
+          swiglu_value2<MODE>(wg, wu, wd, bias != nullptr, bg + 2 * j, bu + 2 * j, f[0] + 2 * j, f[NOUT - 1] + 2 * j);
         }
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) {
@@ -436,11 +417,7 @@ __global__ __launch_bounds__(256) void norm_cast_kernel(const uint16_t* __restri
         const float rs = i < 4 ? rs0[i] : rs1[i - 4];
         float f[8];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const u32 w = (u32)raw[i][j];
-          f[2 * j] = (__uint_as_float(w << 16) * rs) * g[2 * j];
-          f[2 * j + 1] = (__uint_as_float(w & 0xFFFF0000u) * rs) * g[2 * j + 1];
-        }
+        for (int j = 0; j < 4; ++j) norm_value2((u32)raw[i][j], rs, g[2 * j], g[2 * j + 1], f[2 * j], f[2 * j + 1]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) amax = fmaxf(amax, (f[j] != f[j]) ? 0.0f : fabsf(f[j]));
         lo[i] = cvt4_fp8<FMT>(f[0] * scale, f[1] * scale, f[2] * scale, f[3] * scale);

@@ -304,6 +304,18 @@ class _ShardHandle:
         self.dp, self.shard, self.r0, self.rows = dp, shard, r0, rows
 
 
+def uses_current_scaling(model: torch.nn.Module) -> bool:
+    """Does any part of `model` run under Float8CurrentScaling?  The recipes a model carries: the decoder layers' per-region ones
+    (llama.TELlamaDecoderLayer.attn_recipe / mlp_recipe) and the outer one of llama.apply_fp8_autowrap."""
+    from .common.recipe import Float8CurrentScaling
+    mods = [model] + list(model.modules())
+    inner = getattr(model, "module", None)  # a data-parallel wrapper keeps the autowrapped model here
+    if isinstance(inner, torch.nn.Module):
+        mods.append(inner)
+    return any(isinstance(getattr(m, a, None), Float8CurrentScaling) for m in mods
+               for a in ("attn_recipe", "mlp_recipe", "_fp8_outer_recipe"))
+
+
 class ShardedFP8DP(GradArenaDP):
     """The FSDP FULL_SHARD counterpart with an FP8 all-gather (`--sharding_mode fsdp_fp8`).
 
@@ -338,6 +350,12 @@ class ShardedFP8DP(GradArenaDP):
 
     def __init__(self, module: torch.nn.Module, process_group=None, bucket_mb: float = 256.0, broadcast: bool = True,
                  sparse_embedding_grads: bool = True):
+        if uses_current_scaling(module):
+            # (a recipe handed to fp8_autocast by hand is caught at the first forward instead: module._CurrentQ.no_sink)
+            raise RuntimeError("ShardedFP8DP (--sharding_mode fsdp_fp8) cannot run Float8CurrentScaling (--fp8_scenario current): its "
+                               "row shards are quantised by the optimiser into FP8 weight sinks, and a current-scaled weight needs the "
+                               "amax of the whole updated weight before any row can be cast.  Use --sharding_mode replicated "
+                               "(GradArenaDP), which works as is: ranks scale their own activations and the weights are identical")
         self._rs_bucket_bytes = int(bucket_mb * (1 << 20))
         super().__init__(module, process_group, bucket_mb, broadcast, sparse_embedding_grads)
         self._shard_now()

@@ -3,12 +3,13 @@
 accelerate steps train_fp8.py relies on (`convert_model`, `apply_fp8_autowrap`).
 
 The three reference files differ only in the recipe objects, so one
-file serves all three scenarios:
+file serves all three scenarios, and a fourth the reference does not have:
 
   scenario   attention region                         MLP region                               reference
   default    DelayedScaling(HYBRID, 16, "max")        DelayedScaling(E4M3, 16, "max")          te_llama.py:39-40
   hybrid     DelayedScaling(HYBRID, 16, "max")        same recipe object                       te_llama_hybrid.py:39
   mxfp8      MXFP8BlockScaling(E4M3)                  same recipe object                       te_llama_mxfp8.py:28-29
+  current    Float8CurrentScaling(HYBRID)             same recipe object (the lm_head too)     -- (TE's third per-tensor recipe)
 
 No weights, tokenizer or dataset exist offline: configs are hard-coded from the public model cards
  and models are random-initialised.
@@ -23,7 +24,7 @@ from typing import Dict, Optional
 import torch
 
 from . import pytorch as te
-from .common.recipe import DelayedScaling, Format, MXFP8BlockScaling
+from .common.recipe import DelayedScaling, Float8CurrentScaling, Format, MXFP8BlockScaling
 from .pytorch.fp8 import FP8GlobalStateManager
 from .pytorch.module import _can_fuse_norm, residual_add_stats
 
@@ -66,6 +67,9 @@ def scenario_recipes(scenario: str):
         return r, r
     if scenario == "mxfp8":
         r = MXFP8BlockScaling(fp8_format=Format.E4M3)
+        return r, r
+    if scenario == "current":
+        r = Float8CurrentScaling()
         return r, r
     raise ValueError(f"unknown fp8 scenario {scenario!r}")
 
@@ -417,5 +421,7 @@ def outer_recipe_for_scenario(scenario: str):
     """FP8Handler.create_fp8_kwargs (train_fp8.py:126-165): the OUTER (accelerate) recipe -- used by lm_head."""
     if scenario == "default":
         return DelayedScaling(fp8_format=Format.HYBRID, amax_history_len=1024, amax_compute_algo="most_recent")
+    if scenario == "current":  # per-tensor scales from the live amax everywhere, the lm_head included
+        return Float8CurrentScaling()
     # scenarios mxfp8 / hybrid: E4M3, history 16, "max", margin 0 (never MXFP8 for the outer recipe: Appendix C.9)
     return DelayedScaling(fp8_format=Format.E4M3, amax_history_len=16, amax_compute_algo="max", margin=0)

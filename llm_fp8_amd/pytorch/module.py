@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from ..common.recipe import DelayedScaling, Format, MXFP8BlockScaling, Recipe, fmt_codes
+from ..common.recipe import DelayedScaling, Float8CurrentScaling, Format, MXFP8BlockScaling, Recipe, fmt_codes
 from . import ops
 from .fp8 import FP8GlobalStateManager, ModuleMeta
 
@@ -110,7 +110,12 @@ class _GemmSpec:
         self.recipe, self.meta_fwd, self.meta_bwd, self.g = recipe, meta_fwd, meta_bwd, g
         self.fmt_fwd, self.fmt_bwd = fmt_codes(recipe.fp8_format)
         # q: what differs between the recipes at a GEMM site (the only place that chooses)
-        self.q = _MXQ(self.fmt_fwd, self.fmt_bwd) if recipe.mxfp8() else _DelayedQ(meta_fwd, meta_bwd, self.fmt_fwd, self.fmt_bwd)
+        if recipe.mxfp8():
+            self.q = _MXQ(self.fmt_fwd, self.fmt_bwd)
+        elif recipe.current():
+            self.q = _CurrentQ(recipe, self.fmt_fwd, self.fmt_bwd)
+        else:
+            self.q = _DelayedQ(meta_fwd, meta_bwd, self.fmt_fwd, self.fmt_bwd)
         self.trigger_bwd_update = trigger_bwd_update
         self.training = training
 
@@ -227,10 +232,10 @@ def _weight_ok_for_sink(w, K: int) -> bool:
             and (w.is_contiguous() or getattr(w, "_mi_sharded", None) is not None))
 
 
-# What differs between the two recipes at a GEMM site, behind the same few methods (`_GemmSpec.q` is one or the other).  A quantised
+# What differs between the recipes at a GEMM site, behind the same few methods (`_GemmSpec.q` is one of the three classes below).  A quantised
 # operand has one shape under both: (row, col), the row-wise copy [R, C] and the column-wise one, stored transposed [C, R], each a
-# (data, scale) pair -- None data where the copy was not asked for.  `scale` is the one-element scale-inverse under delayed scaling
-# and the block-major E8M0 tensor under MXFP8.  A GEMM contracts the row-wise copies of its operands: the forward takes `row` of
+# (data, scale) pair -- None data where the copy was not asked for.  `scale` is the one-element scale-inverse under delayed and
+# current scaling and the block-major E8M0 tensor under MXFP8.  A GEMM contracts the row-wise copies of its operands: the forward takes `row` of
 # the input and the weight, the backward pair takes `col` of both with the two copies of grad_output.  `g` is the GEMM's index in
 # its module.
 
@@ -401,6 +406,99 @@ class _MXQ:
 
     def sink_flat(self, sink, g: int):
         return sink.w8, sink.sc, sink.wt8, sink.sct
+
+
+class _CurrentQ:
+    """Current scaling (Float8CurrentScaling): every quantisation is an amax pass over the tensor (ops.amax_*: the value the cast
+    will see, recomputed where the producer is fused), the scale kernel (ops.current_scale -> a fresh [amax, scale, scale_inv]) and
+    the cast kernel delayed scaling uses, reading that scale and publishing no amax.  No history, no meta slots, nothing to update
+    at autocast exit.  Operands are those of delayed scaling -- FP8 bytes with a one-element scale-inverse, here a view of the
+    quantisation's own triple, which is what the saved column-wise copies carry into backward -- so the GEMMs, the grouped
+    dgrad + wgrad launch and the algorithm table apply unchanged."""
+    __slots__ = ("recipe", "fmt_f", "fmt_b")
+    mx = False
+    cache_key, sink_key = "cs", "cssink"
+    # the optimiser cannot emit current-scaled bytes in its single pass over a weight (the scale needs the updated weight's amax
+    # first): no sink, the forward quantises the weights (the is_first_microbatch cache still keeps them across a window) -- and
+    # distributed.ShardedFP8DP, which lives on optimiser-filled sinks, cannot run this recipe
+    no_sink = ("Float8CurrentScaling keeps no optimiser-filled FP8 weight copies, which row-sharded weights (distributed.ShardedFP8DP, "
+               "--sharding_mode fsdp_fp8) depend on: use --sharding_mode replicated (GradArenaDP) with this recipe")
+    swiglu_adds_bias = True
+    colsum_dtypes = None
+
+    def __init__(self, recipe: Float8CurrentScaling, fmt_f: int, fmt_b: int):
+        self.recipe, self.fmt_f, self.fmt_b = recipe, fmt_f, fmt_b
+
+    @staticmethod
+    def _triple(part, fmt: int, qp):
+        return ops.current_scale(part, ops.FP8_MAX[fmt], qp.amax_epsilon, qp.power_2_scale)
+
+    def quantize(self, x2, g: int, want_t: bool, norm=None):
+        part = ops.amax_partial(x2.device, ops.amax_grid(*x2.shape))
+        if norm is None:
+            ops.amax_bf16(x2, part)
+        else:
+            ops.amax_norm(x2, norm[0], norm[1], part)
+        t3 = self._triple(part, self.fmt_f, self.recipe.fp8_quant_fwd_inp)
+        if norm is None:
+            y, yT = ops.cast_amax(x2, t3[1:2], None, self.fmt_f, want_t=want_t)
+        else:
+            y, yT = ops.norm_cast(x2, norm[0], norm[1], t3[1:2], None, self.fmt_f, want_t=want_t)
+        return (y, t3[2:3]), (yT, t3[2:3])
+
+    def swiglu(self, h, g: int, want_t: bool, bias):
+        part = ops.amax_partial(h.device, ops.amax_grid(h.shape[0], h.shape[1] // 2, 32))
+        ops.amax_swiglu(h, bias, part)
+        t3 = self._triple(part, self.fmt_f, self.recipe.fp8_quant_fwd_inp)
+        y, yT = ops.swiglu_cast(h, t3[1:2], None, self.fmt_f, want_t=want_t, bias=bias)
+        return (y, t3[2:3]), (yT, t3[2:3])
+
+    def quantize_grad(self, g2, g: int, want_y: bool, want_t: bool, colsum: bool = False):
+        part = ops.amax_partial(g2.device, ops.amax_grid(*g2.shape))
+        ops.amax_bf16(g2, part)
+        t3 = self._triple(part, self.fmt_b, self.recipe.fp8_quant_bwd_grad)
+        out = ops.cast_amax(g2, t3[1:2], None, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum)
+        return (out[0], t3[2:3]), (out[1], t3[2:3]), out[2] if colsum else None
+
+    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
+        part = ops.amax_partial(h.device, ops.amax_grid(h.shape[0], h.shape[1] // 2, 32))
+        ops.amax_dswiglu(h, bias, dact, part)
+        t3 = self._triple(part, self.fmt_b, self.recipe.fp8_quant_bwd_grad)
+        y, yT, cs = ops.dswiglu_cast(h, dact, t3[1:2], None, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum, bias=bias)
+        return (y, t3[2:3]), (yT, t3[2:3]), cs
+
+    def offer(self, handoff: DyHandoff, g: int, want_y: bool, want_t: bool) -> None:
+        """Nothing: a DyHandoff producer needs the scale of grad_output before it has produced it.  RoPE backward and cross-entropy
+        backward take their bf16 route and the Linear quantises the gradient it receives."""
+
+    def taken(self, fp8, g: int):
+        raise RuntimeError("Float8CurrentScaling offers no DyHandoff, so no producer can have put FP8 copies into one")
+
+    operands = _DelayedQ.operands
+    gemm = _DelayedQ.gemm
+    unflat = _DelayedQ.unflat
+
+    def quantize_weights(self, weights, ns, N: int, K: int, dev, g: int, want_t: bool):
+        """One scale for the whole operand (query | key | value): every part's amax pass fills its own segment of the partial
+        buffer, ONE scale kernel covers all segments, then every part is cast into its row-block."""
+        ws_ = [(w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous() for w in weights]
+        grids = [ops.amax_grid(n, K) for n in ns]
+        part = ops.amax_partial(dev, sum(grids))
+        o = 0
+        for w, n in zip(ws_, grids):
+            ops.amax_bf16(w, part[o:o + n])
+            o += n
+        t3 = self._triple(part, self.fmt_f, self.recipe.fp8_quant_fwd_weight)
+        w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
+        w8t = torch.empty((K, N), dtype=torch.uint8, device=dev) if want_t else None
+        r = 0
+        for w, n in zip(ws_, ns):
+            ops.cast_amax(w, t3[1:2], None, self.fmt_f, y=w8[r:r + n], yT=None if w8t is None else w8t[:, r:r + n], want_t=want_t)
+            r += n
+        return w8, w8t, t3[2:3]
+
+    def new_sink(self, weights, ns, N: int, K: int, dev, g: int):
+        return None
 
 
 def _weight_operand(spec: _GemmSpec, g: int, weights, ns, N: int, K: int, dev, need_t: bool):
@@ -735,7 +833,7 @@ class _FP8Module(torch.nn.Module):
             return None
         recipe = FP8GlobalStateManager.get_fp8_recipe()
         first = FP8GlobalStateManager.is_first_fp8_module()
-        if recipe.mxfp8():
+        if recipe.mxfp8() or recipe.current():  # no state: no meta windows, no arenas, an empty _extra_state
             return recipe, None, None, first
         key = (recipe.fp8_format, recipe.amax_history_len, recipe.amax_compute_algo, recipe.margin, str(device))
         if self._meta_key != key:
@@ -938,10 +1036,10 @@ def _usable_rstd(handoff, inp: torch.Tensor, eps: float):
 
 
 def _can_fuse_norm(mod, recipe, inp) -> bool:
-    """K9 applies to RMSNorm (delayed scaling and MXFP8); the backward kernel keeps a whole row per wave (cols % 512, <= 8192)."""
+    """K9 applies to RMSNorm (every recipe); the backward kernel keeps a whole row per wave (cols % 512, <= 8192)."""
     h = inp.shape[-1]
     return (getattr(mod, "fused_norm", True) and mod.normalization == "RMSNorm" and not mod.zero_centered_gamma
-            and (recipe.delayed() or recipe.mxfp8()) and h % 512 == 0 and h // 512 in (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16))
+            and (recipe.delayed() or recipe.mxfp8() or recipe.current()) and h % 512 == 0 and h // 512 in (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16))
 
 
 def _swiglu(a: torch.Tensor) -> torch.Tensor:
@@ -1011,7 +1109,7 @@ class LayerNormMLP(_FP8Module):
             return F.linear(self.act_fn(h), _master(self.fc2_weight).to(ln.dtype),
                             None if self.fc2_bias is None else self.fc2_bias.to(ln.dtype))
         recipe = st[0]
-        if self.activation == "swiglu" and self.fused_swiglu and (recipe.delayed() or inp.numel() // inp.shape[-1] % 32 == 0):
+        if self.activation == "swiglu" and self.fused_swiglu and (not recipe.mxfp8() or inp.numel() // inp.shape[-1] % 32 == 0):
             return _FP8SwiGLUMLPFn.apply(ln, self.fc1_weight, self.fc1_bias, self.fc2_weight, self.fc2_bias,
                                          self._spec(st, is_first_microbatch))
         h = _FP8LinearFn.apply(ln, self.fc1_bias, self._spec(st, is_first_microbatch), None, self.fc1_weight)

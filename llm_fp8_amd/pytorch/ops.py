@@ -138,6 +138,100 @@ def cast_amax(x: torch.Tensor, scale: torch.Tensor, amax: Optional[torch.Tensor]
     return (y, yT, cs) if want_colsum else (y, yT)
 
 
+# ---- current scaling (Float8CurrentScaling): amax pass -> scale kernel -> the cast kernels above with scale = out3[1:2] ----
+AMAX_MAX_PARTIALS = 1024
+_AMAX_PARTIAL: dict = {}   # device index -> the reusable fp32 buffer the amax passes write their workgroup partials into
+_CU_COUNT: dict = {}
+
+
+def amax_grid(rows: int, cols: int, tile_rows: int = 64) -> int:
+    """Default n_partial (= workgroups) of an amax pass over a [rows, cols] space walked in tile_rows x 64 tiles, one tile per wave
+    and step: two workgroups per CU (the cast kernels' grid), fewer when there are fewer tiles, at most AMAX_MAX_PARTIALS."""
+    idx = torch.cuda.current_device()
+    if idx not in _CU_COUNT:
+        _CU_COUNT[idx] = int(torch.cuda.get_device_properties(idx).multi_processor_count) or 256
+    tiles = -(-rows // tile_rows) * -(-cols // 64)
+    return max(1, min(-(-tiles // 4), 2 * _CU_COUNT[idx], AMAX_MAX_PARTIALS))
+
+
+def amax_partial(device: torch.device, n: int) -> torch.Tensor:
+    """[n] fp32 view of the device's partial buffer.  ONE buffer per device, reused by every quantisation: the amax pass that fills
+    it and the scale kernel that reads it are neighbours on the current stream, and the next user is ordered behind both."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    buf = _AMAX_PARTIAL.get(idx)
+    if buf is None or buf.numel() < n:
+        buf = _AMAX_PARTIAL[idx] = torch.empty(max(n, 4 * AMAX_MAX_PARTIALS), dtype=torch.float32, device=torch.device("cuda", idx))
+    return buf[:n]
+
+
+def _amax_call(name: str, args, label: str, elems: float, nbytes: float) -> None:
+    fn = _lib.require(name, "Float8CurrentScaling")
+    t = KernelTimer.active
+    if t is None:
+        rc = fn(*args)
+    else:
+        with t.span("amax", label, elems, nbytes):
+            rc = fn(*args)
+    _lib.check(rc, name)
+
+
+def _partial_ok(partial: torch.Tensor) -> int:
+    _dev(partial)
+    assert partial.dtype == torch.float32 and partial.dim() == 1 and partial.is_contiguous() and 1 <= partial.numel() <= AMAX_MAX_PARTIALS
+    return partial.numel()
+
+
+def amax_bf16(x: torch.Tensor, partial: torch.Tensor) -> None:
+    """partial[i] = max |x| over what workgroup i of partial.numel() walked (0 if nothing); every entry is written."""
+    _dev(x)
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
+    R, C = x.shape
+    _amax_call("mi_amax_bf16", (x.data_ptr(), partial.data_ptr(), _partial_ok(partial), R, C, _stream()), f"{R}x{C}", float(R * C),
+               2.0 * R * C)
+
+
+def amax_norm(x: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, partial: torch.Tensor) -> None:
+    """amax_bf16 of the value norm_cast quantises, (x * rstd[:, None]) * gamma in fp32."""
+    _dev(x, rstd, gamma)
+    assert x.dtype == torch.bfloat16 and gamma.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous() and gamma.is_contiguous()
+    assert rstd.dtype == torch.float32 and rstd.is_contiguous() and rstd.numel() == x.shape[0] and gamma.numel() == x.shape[1]
+    R, C = x.shape
+    _amax_call("mi_amax_norm", (x.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), partial.data_ptr(), _partial_ok(partial), R, C, _stream()),
+               f"norm {R}x{C}", float(R * C), 2.0 * R * C)
+
+
+def amax_swiglu(h: torch.Tensor, bias: Optional[torch.Tensor], partial: torch.Tensor) -> None:
+    """amax_bf16 of the value swiglu_cast quantises: silu(gate) * up of h [R, 2F] (+ `bias` [2F], as swiglu_cast adds it)."""
+    _dev(h, bias)
+    assert h.dtype == torch.bfloat16 and h.dim() == 2 and h.is_contiguous() and h.shape[1] % 2 == 0
+    R, F = h.shape[0], h.shape[1] // 2
+    assert bias is None or (bias.dtype == torch.bfloat16 and bias.numel() == 2 * F and bias.is_contiguous())
+    _amax_call("mi_amax_swiglu", (h.data_ptr(), _ptr(bias), partial.data_ptr(), _partial_ok(partial), R, F, _stream()),
+               f"swiglu {R}x{F}", float(R * F), 4.0 * R * F)
+
+
+def amax_dswiglu(h: torch.Tensor, bias: Optional[torch.Tensor], dact: torch.Tensor, partial: torch.Tensor) -> None:
+    """amax_bf16 of the value dswiglu_cast quantises: both halves of dh [R, 2F]."""
+    _dev(h, bias, dact)
+    assert h.dtype == torch.bfloat16 and dact.dtype == torch.bfloat16 and h.dim() == 2 and h.is_contiguous() and dact.is_contiguous()
+    R, F = h.shape[0], h.shape[1] // 2
+    assert dact.shape == (R, F) and (bias is None or (bias.dtype == torch.bfloat16 and bias.numel() == 2 * F and bias.is_contiguous()))
+    _amax_call("mi_amax_dswiglu", (h.data_ptr(), _ptr(bias), dact.data_ptr(), partial.data_ptr(), _partial_ok(partial), R, F, _stream()),
+               f"dswiglu {R}x{F}", float(2 * R * F), 6.0 * R * F)
+
+
+def current_scale(partial: torch.Tensor, fp8_max: float, amax_epsilon: float = 0.0, pow2: bool = False) -> torch.Tensor:
+    """[amax, scale, scale_inv] (a fresh fp32 [3]) from the partials of one operand's amax passes: TE's compute_scale_from_amax.
+    `partial` may span the segments several passes filled (the parts of one weight operand)."""
+    _dev(partial)
+    assert partial.dtype == torch.float32 and partial.dim() == 1 and partial.is_contiguous() and partial.numel() >= 1
+    out3 = torch.empty(3, dtype=torch.float32, device=partial.device)
+    fn = _lib.require("mi_current_scale", "Float8CurrentScaling")
+    _lib.check(fn(partial.data_ptr(), partial.numel(), float(fp8_max), float(amax_epsilon), int(bool(pow2)), out3.data_ptr(), _stream()),
+               "mi_current_scale")
+    return out3
+
+
 def scale_update(amax_history: torch.Tensor, scale: torch.Tensor, scale_inv: torch.Tensor,
                  fp8_max: torch.Tensor, margin: int = 0, algo: str = "max") -> None:
     """K3, in place on [H, S] history and [S] scale / scale_inv."""
