@@ -28,7 +28,6 @@ __global__ __launch_bounds__(256) void cast_amax_kernel(const uint16_t* __restri
                                                         uint8_t* __restrict__ yT, const float* __restrict__ scale_p,
                                                         float* amax_out, int rows, int cols, int64_t ld_y,
                                                         int64_t ld_yT, int tiles_c, float* __restrict__ colsum = nullptr) {
-  __shared__ float s_amax[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntiles = ((rows + 63) / 64) * tiles_c;
   const int stride = gridDim.x * 4;
@@ -90,24 +89,8 @@ __global__ __launch_bounds__(256) void cast_amax_kernel(const uint16_t* __restri
       hi[i] = cvt4_fp8<FMT>(f[4] * scale, f[5] * scale, f[6] * scale, f[7] * scale);
     }
     if (active) {
-      if (WRITE_Y) {
-        uint8_t* dst = y + (int64_t)r0 * ld_y + c0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) mi::st8<MI_NT_Y>(dst + (int64_t)i * ld_y, lo[i], hi[i]);
-      }
-      if (WRITE_T) {
-        u32 a[4], b[4], c[4], d[4];
-        transpose4x4(lo[0], lo[1], lo[2], lo[3], a[0], a[1], a[2], a[3]);  // cols 0..3, rows 0..3
-        transpose4x4(lo[4], lo[5], lo[6], lo[7], b[0], b[1], b[2], b[3]);  // cols 0..3, rows 4..7
-        transpose4x4(hi[0], hi[1], hi[2], hi[3], c[0], c[1], c[2], c[3]);  // cols 4..7, rows 0..3
-        transpose4x4(hi[4], hi[5], hi[6], hi[7], d[0], d[1], d[2], d[3]);  // cols 4..7, rows 4..7
-        uint8_t* dst = yT + (int64_t)c0 * ld_yT + r0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          mi::st8<MI_NT_YT>(dst + (int64_t)j * ld_yT, a[j], b[j]);
-          mi::st8<MI_NT_YT>(dst + (int64_t)(j + 4) * ld_yT, c[j], d[j]);
-        }
-      }
+      if (WRITE_Y) store_rows8<MI_NT_Y>(y + (int64_t)r0 * ld_y + c0, ld_y, lo, hi);
+      if (WRITE_T) store_cols8<MI_NT_YT>(yT + (int64_t)c0 * ld_yT + r0, ld_yT, lo, hi);
     }
     if (COLSUM) {  // inactive lanes carry zeros; lanes 0..7 end up with the 64-row sums of their 8 columns
 #pragma unroll
@@ -124,17 +107,7 @@ __global__ __launch_bounds__(256) void cast_amax_kernel(const uint16_t* __restri
     }
     t = tn;
   }
-  if (amax_out != nullptr) {
-    amax = wave_max(amax);
-    if (lane == 0) s_amax[wave] = amax;
-    __syncthreads();
-    if (tid == 0) {
-      float m = fmaxf(fmaxf(s_amax[0], s_amax[1]), fmaxf(s_amax[2], s_amax[3]));
-      // only a workgroup that would raise the value goes to the atomic unit: same-address atomics are served one at a time and a
-      // wave cannot retire before its atomic has returned
-      if (m > 0.0f && m > __builtin_nontemporal_load(amax_out)) atomicMax(reinterpret_cast<unsigned int*>(amax_out), __float_as_uint(m));
-    }
-  }
+  publish_amax(amax, amax_out);
 }
 
 static int cast_num_cus() {
@@ -198,8 +171,7 @@ __global__ __launch_bounds__(256) void colsum_finish_multi_kernel(FinishArgs a, 
   colsum_finish_block(a.d[i].part, a.d[i].P, a.d[i].C, a.d[i].out, a.d[i].out_bf16, (int)blockIdx.x - first);
 }
 
-template <int FMT>
-static int launch_cast(const void* x, void* y, void* yT, const float* scale, float* amax, int64_t rows,
+static int launch_cast(int fmt, const void* x, void* y, void* yT, const float* scale, float* amax, int64_t rows,
                        int64_t cols, int64_t ld_y, int64_t ld_yT, hipStream_t st, float* colsum = nullptr) {
   const int tiles_r = (int)((rows + 63) / 64), tiles_c = (int)((cols + 63) / 64);
   const int64_t wgs = ((int64_t)tiles_r * tiles_c + 3) / 4;
@@ -211,27 +183,13 @@ static int launch_cast(const void* x, void* y, void* yT, const float* scale, flo
   const uint16_t* xp = (const uint16_t*)x;
   uint8_t *yp = (uint8_t*)y, *tp = (uint8_t*)yT;
   if (colsum) {
-    if (y && yT)
-      hipLaunchKernelGGL((cast_amax_kernel<FMT, true, true, true>), grid, block, 0, st, xp, yp, tp, scale, amax, (int)rows,
-                         (int)cols, ld_y, ld_yT, tiles_c, colsum);
-    else if (y)
-      hipLaunchKernelGGL((cast_amax_kernel<FMT, true, false, true>), grid, block, 0, st, xp, yp, tp, scale, amax, (int)rows,
-                         (int)cols, ld_y, ld_yT, tiles_c, colsum);
-    else
-      hipLaunchKernelGGL((cast_amax_kernel<FMT, false, true, true>), grid, block, 0, st, xp, yp, tp, scale, amax, (int)rows,
-                         (int)cols, ld_y, ld_yT, tiles_c, colsum);
+    MI_LAUNCH_FMT_YT(fmt, y, yT, cast_amax_kernel, (), (, true), grid, block, 0, st, xp, yp, tp, scale, amax, (int)rows, (int)cols,
+                     ld_y, ld_yT, tiles_c, colsum);
     MI_CHECK_LAUNCH("mi_cast_amax_colsum launch");
     return MI_OK;
   }
-  if (y && yT)
-    hipLaunchKernelGGL((cast_amax_kernel<FMT, true, true>), grid, block, 0, st, xp, yp, tp, scale, amax, (int)rows,
-                       (int)cols, ld_y, ld_yT, tiles_c, (float*)nullptr);
-  else if (y)
-    hipLaunchKernelGGL((cast_amax_kernel<FMT, true, false>), grid, block, 0, st, xp, yp, tp, scale, amax, (int)rows,
-                       (int)cols, ld_y, ld_yT, tiles_c, (float*)nullptr);
-  else
-    hipLaunchKernelGGL((cast_amax_kernel<FMT, false, true>), grid, block, 0, st, xp, yp, tp, scale, amax, (int)rows,
-                       (int)cols, ld_y, ld_yT, tiles_c, (float*)nullptr);
+  MI_LAUNCH_FMT_YT(fmt, y, yT, cast_amax_kernel, (), (), grid, block, 0, st, xp, yp, tp, scale, amax, (int)rows, (int)cols, ld_y,
+                   ld_yT, tiles_c, (float*)nullptr);
   MI_CHECK_LAUNCH("mi_cast_amax launch");
   return MI_OK;
 }
@@ -253,9 +211,7 @@ static int cast_amax_impl(const void* x_bf16, void* y_fp8, void* yT_fp8, const f
                "mi_cast_amax: x must be 16-byte aligned, y/yT 8-byte aligned");
   MI_CHECK_ARG(fmt == MI_FMT_E4M3 || fmt == MI_FMT_E5M2, "mi_cast_amax: bad fmt %d", fmt);
   if (rows == 0 || cols == 0) return MI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (fmt == MI_FMT_E4M3) return mi::launch_cast<MI_FMT_E4M3>(x_bf16, y_fp8, yT_fp8, scale, amax, rows, cols, ld_y, ld_yT, st, colsum);
-  return mi::launch_cast<MI_FMT_E5M2>(x_bf16, y_fp8, yT_fp8, scale, amax, rows, cols, ld_y, ld_yT, st, colsum);
+  return mi::launch_cast(fmt, x_bf16, y_fp8, yT_fp8, scale, amax, rows, cols, ld_y, ld_yT, (hipStream_t)stream, colsum);
 }
 
 namespace mi {
@@ -276,17 +232,7 @@ __global__ __launch_bounds__(256) void transpose_u8_kernel(const uint8_t* __rest
     lo[i] = v.x;
     hi[i] = v.y;
   }
-  u32 a[4], b[4], c[4], d[4];
-  transpose4x4(lo[0], lo[1], lo[2], lo[3], a[0], a[1], a[2], a[3]);
-  transpose4x4(lo[4], lo[5], lo[6], lo[7], b[0], b[1], b[2], b[3]);
-  transpose4x4(hi[0], hi[1], hi[2], hi[3], c[0], c[1], c[2], c[3]);
-  transpose4x4(hi[4], hi[5], hi[6], hi[7], d[0], d[1], d[2], d[3]);
-  uint8_t* dst = yT + c0 * ld_yT + r0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    mi::st8<MI_NT_YT>(dst + (int64_t)j * ld_yT, a[j], b[j]);
-    mi::st8<MI_NT_YT>(dst + (int64_t)(j + 4) * ld_yT, c[j], d[j]);
-  }
+  store_cols8<MI_NT_YT>(yT + c0 * ld_yT + r0, ld_yT, lo, hi);
 }
 }  // namespace mi
 

@@ -193,6 +193,135 @@ __device__ __forceinline__ void st8(uint8_t* p, unsigned int a, unsigned int b) 
   if (NT) __builtin_nontemporal_store(w, reinterpret_cast<v2u_st8*>(p));
   else *reinterpret_cast<v2u_st8*>(p) = w;
 }
+
+// A lane's 8 x 8 block of FP8 bytes (row i: lo[i] = columns 0..3, hi[i] = columns 4..7), row-major: row i at dst + i * ld.
+template <bool NT>
+__device__ __forceinline__ void store_rows8(uint8_t* dst, int64_t ld, const u32 (&lo)[8], const u32 (&hi)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) st8<NT>(dst + i * ld, lo[i], hi[i]);
+}
+// The same block transposed in registers and stored column-major: column j (its 8 rows = 8 bytes) at dst + j * ld.
+template <bool NT>
+__device__ __forceinline__ void store_cols8(uint8_t* dst, int64_t ld, const u32 (&lo)[8], const u32 (&hi)[8]) {
+  u32 a[4], b[4], c[4], d[4];
+  transpose4x4(lo[0], lo[1], lo[2], lo[3], a[0], a[1], a[2], a[3]);  // cols 0..3, rows 0..3
+  transpose4x4(lo[4], lo[5], lo[6], lo[7], b[0], b[1], b[2], b[3]);  // cols 0..3, rows 4..7
+  transpose4x4(hi[0], hi[1], hi[2], hi[3], c[0], c[1], c[2], c[3]);  // cols 4..7, rows 0..3
+  transpose4x4(hi[4], hi[5], hi[6], hi[7], d[0], d[1], d[2], d[3]);  // cols 4..7, rows 4..7
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    st8<NT>(dst + j * ld, a[j], b[j]);
+    st8<NT>(dst + (j + 4) * ld, c[j], d[j]);
+  }
+}
+
+// max of `v` over the 4 waves of a 256-thread workgroup.  Holds a barrier: every thread of the workgroup calls it.
+__device__ __forceinline__ float block_max(float v) {
+  __shared__ float s_max[4];
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+}
+// Per-tensor amax of a cast kernel: the workgroup's max goes into *amax_out with ONE atomicMax on the float's bit pattern
+// (non-negative floats order like unsigned ints).  Every thread of the workgroup calls it; amax_out is workgroup-uniform.
+__device__ __forceinline__ void publish_amax(float amax, float* amax_out) {
+  if (amax_out == nullptr) return;
+  const float m = block_max(amax);
+  // only a workgroup that would raise the value goes to the atomic unit: same-address atomics are served one at a time and a
+  // wave cannot retire before its atomic has returned (thousands of workgroups per launch)
+  if (threadIdx.x == 0 && m > 0.0f && m > __builtin_nontemporal_load(amax_out))
+    atomicMax(reinterpret_cast<unsigned int*>(amax_out), __float_as_uint(m));
+}
+
+// ---- MXFP8 block quantiser of a lane's 8 x 8 value block f (mxfp8_quant_kernel, adamw_mxcast_multi_kernel): one E8M0 scale per
+// 32 elements, which span 4 neighbouring lanes.  The shuffles are executed by every lane (inactive lanes carry zeros).
+// NaN -> 0 in f, recorded in the returned mask (bit 8 i + j): the block amax then needs no per-element test (fmaxf semantics:
+// NaN ignored) and the byte is patched to 0x7F after the cast.
+__device__ __forceinline__ unsigned long long mx_take_nans(float (&f)[8][8]) {
+  unsigned long long nanmask = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (f[i][j] != f[i][j]) {
+        nanmask |= 1ull << (8 * i + j);
+        f[i][j] = 0.0f;
+      }
+  return nanmask;
+}
+// bytes of a packed fp8 word (elements (i, j0..j0+3), bit0 = 8 i + j0) -> 0x7F where the mask says the source was a NaN (rare path)
+__device__ __forceinline__ u32 mx_patch4(u32 w, unsigned long long nanmask, int bit0) {
+  if (__builtin_expect(nanmask != 0, 0)) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((nanmask >> (bit0 + k)) & 1) w = (w & ~(0xFFu << (8 * k))) | (0x7Fu << (8 * k));
+  }
+  return w;
+}
+// row-wise blocks (32 columns = lanes l, l^1, l^2, l^3): bytes lo / hi and the scale byte of each of the lane's 8 rows
+template <int FMT>
+__device__ __forceinline__ void mx_quant_rows(const float (&f)[8][8], unsigned long long nanmask, u32 (&lo)[8], u32 (&hi)[8],
+                                              u32 (&sbytes)[8]) {
+  const float rcp = 1.0f / fp8_max_of<FMT>();
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    float a = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a = fmaxf(a, fabsf(f[i][j]));
+    a = fmaxf(a, __shfl_xor(a, 1));
+    a = fmaxf(a, __shfl_xor(a, 2));
+    const u32 e = e8m0_roundup(a * rcp);
+    const float inv = e8m0_inv(e);
+    sbytes[i] = e;
+    lo[i] = mx_patch4(cvt4_fp8<FMT>(f[i][0] * inv, f[i][1] * inv, f[i][2] * inv, f[i][3] * inv), nanmask, 8 * i);
+    hi[i] = mx_patch4(cvt4_fp8<FMT>(f[i][4] * inv, f[i][5] * inv, f[i][6] * inv, f[i][7] * inv), nanmask, 8 * i + 4);
+  }
+}
+// column-wise blocks (32 rows = lanes l, l^8, l^16, l^24): the same bytes by row, and the scale byte of each of the 8 columns
+template <int FMT>
+__device__ __forceinline__ void mx_quant_cols(const float (&f)[8][8], unsigned long long nanmask, u32 (&lo)[8], u32 (&hi)[8],
+                                              u32 (&sbytes)[8]) {
+  const float rcp = 1.0f / fp8_max_of<FMT>();
+  float inv[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float a = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a = fmaxf(a, fabsf(f[i][j]));
+    a = fmaxf(a, __shfl_xor(a, 8));
+    a = fmaxf(a, __shfl_xor(a, 16));
+    const u32 e = e8m0_roundup(a * rcp);
+    sbytes[j] = e;
+    inv[j] = e8m0_inv(e);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    lo[i] = mx_patch4(cvt4_fp8<FMT>(f[i][0] * inv[0], f[i][1] * inv[1], f[i][2] * inv[2], f[i][3] * inv[3]), nanmask, 8 * i);
+    hi[i] = mx_patch4(cvt4_fp8<FMT>(f[i][4] * inv[4], f[i][5] * inv[5], f[i][6] * inv[6], f[i][7] * inv[7]), nanmask, 8 * i + 4);
+  }
+}
+// block-major scales: the scale bytes of a lane's 8 rows / 8 columns are 8 contiguous bytes
+__device__ __forceinline__ void store_scales8(uint8_t* p, const u32 (&s)[8]) {
+  st8<false>(p, s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24), s[4] | (s[5] << 8) | (s[6] << 16) | (s[7] << 24));
+}
 }  // namespace mi
+
+// The launch ladder of the kernels that emit y, yT or both, in E4M3 or E5M2: KERNEL<FMT, LEAD WRITE_Y, WRITE_T TRAIL>.  LEAD and
+// TRAIL are the parenthesised template arguments between FMT and the two flags (each FOLLOWED by its comma) and behind the flags
+// (each PRECEDED by its comma); "()" for none.  The rest is hipLaunchKernelGGL's argument list.  The callers have checked that
+// fmt is one of the two and that an output is present.
+#define MI_TARGS_(...) __VA_ARGS__
+#define MI_LAUNCH_YT_(FMTv, has_y, has_t, KERNEL, LEAD, TRAIL, ...)                                           \
+  do {                                                                                                        \
+    if ((has_y) && (has_t)) hipLaunchKernelGGL((KERNEL<FMTv, MI_TARGS_ LEAD true, true MI_TARGS_ TRAIL>), __VA_ARGS__); \
+    else if (has_y) hipLaunchKernelGGL((KERNEL<FMTv, MI_TARGS_ LEAD true, false MI_TARGS_ TRAIL>), __VA_ARGS__);        \
+    else hipLaunchKernelGGL((KERNEL<FMTv, MI_TARGS_ LEAD false, true MI_TARGS_ TRAIL>), __VA_ARGS__);                   \
+  } while (0)
+#define MI_LAUNCH_FMT_YT(fmt, ...)                                    \
+  do {                                                                \
+    if ((fmt) == MI_FMT_E4M3) MI_LAUNCH_YT_(MI_FMT_E4M3, __VA_ARGS__); \
+    else MI_LAUNCH_YT_(MI_FMT_E5M2, __VA_ARGS__);                      \
+  } while (0)
 #endif
 

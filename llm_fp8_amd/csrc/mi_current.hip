@@ -45,7 +45,6 @@ __global__ __launch_bounds__(256) void amax_kernel(const uint16_t* __restrict__ 
   constexpr int RPL = MODE <= 1 ? 8 : 4;
   constexpr int TR = 8 * RPL;
   constexpr int NIN = MODE == 3 ? 3 : (MODE == 2 ? 2 : 1);
-  __shared__ float s_amax[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntiles = ((rows + TR - 1) / TR) * tiles_c;
   const int stride = gridDim.x * 4;
@@ -151,24 +150,18 @@ __global__ __launch_bounds__(256) void amax_kernel(const uint16_t* __restrict__ 
     }
     t = tn;
   }
-  amax = wave_max(amax);
-  if (lane == 0) s_amax[wave] = amax;
-  __syncthreads();
-  if (tid == 0) partial[blockIdx.x] = fmaxf(fmaxf(s_amax[0], s_amax[1]), fmaxf(s_amax[2], s_amax[3]));
+  amax = block_max(amax);
+  if (tid == 0) partial[blockIdx.x] = amax;
 }
 
 // TE's compute_scale_from_amax on the maximum of the partials; out3 = {amax, scale, scale_inv}
 __global__ __launch_bounds__(256) void current_scale_kernel(const float* __restrict__ partial, int n, float fp8_max, float eps,
                                                             int pow2, float* __restrict__ out3) {
-  __shared__ float s_amax[4];
   const int tid = threadIdx.x;
   float m = 0.0f;
   for (int i = tid; i < n; i += 256) m = fmaxf(m, partial[i]);  // (the passes never write a NaN)
-  m = wave_max(m);
-  if ((tid & 63) == 0) s_amax[tid >> 6] = m;
-  __syncthreads();
+  const float amax = block_max(m);
   if (tid == 0) {
-    const float amax = fmaxf(fmaxf(s_amax[0], s_amax[1]), fmaxf(s_amax[2], s_amax[3]));
     const float a = amax < eps ? eps : amax;
     float scale = 1.0f;
     if (!(a == 0.0f) && !isinf(a)) {

@@ -79,6 +79,8 @@ __global__ __launch_bounds__(256) void rope_qkv_kernel(uint16_t* __restrict__ fu
 // yT [W, rows]) + amax and is never written in bf16.  Values are rounded to bf16 before the cast, so the bytes equal
 // mi_rope_qkv(backward) followed by mi_cast_amax bit for bit.  head_dim 128: a wave owns 64 rows x one whole q/k head
 // (the two 64-column halves x1 | x2 that rotate into each other) or 64 rows x 64 columns of the v part.
+// The block stores and the amax publish are written out here, not store_rows8 / store_cols8 / publish_amax (mi_common.h): at one
+// wave per SIMD (352-364 VGPRs) the helpers' register allocation cost 2.2-2.6 % of the kernel's time (profiles/cast_helpers_ab.txt).
 template <int FMT, bool WRITE_Y, bool WRITE_T>
 __global__ __launch_bounds__(256) void rope_bwd_cast_kernel(const uint16_t* __restrict__ dq, const uint16_t* __restrict__ dk,
                                                             const uint16_t* __restrict__ dv, const float* __restrict__ cosT,
@@ -176,8 +178,7 @@ __global__ __launch_bounds__(256) void rope_bwd_cast_kernel(const uint16_t* __re
     __syncthreads();
     if (tid == 0) {
       const float m = fmaxf(fmaxf(s_amax[0], s_amax[1]), fmaxf(s_amax[2], s_amax[3]));
-      // only a workgroup that would raise the value goes to the atomic unit: same-address atomics are served one at a time and a
-      // wave cannot retire before its atomic has returned (thousands of workgroups per launch)
+      // the guard of publish_amax (mi_common.h)
       if (m > 0.0f && m > __builtin_nontemporal_load(amax_out)) atomicMax(reinterpret_cast<unsigned int*>(amax_out), __float_as_uint(m));
     }
   }
@@ -202,7 +203,6 @@ __global__ __launch_bounds__(256) void swiglu_cast_kernel(const uint16_t* __rest
                                                           const float* __restrict__ scale_p, float* amax_out,
                                                           float* __restrict__ colsum, int rows, int F, int tiles_c,
                                                           const uint16_t* __restrict__ bias) {
-  __shared__ float s_amax[4];
   __shared__ float s_col[MODE == 1 ? 2 : 1][2][128];
   constexpr int NOUT = MODE == 0 ? 1 : 2;
   const int ocols = MODE == 0 ? F : 2 * F;
@@ -265,24 +265,8 @@ __global__ __launch_bounds__(256) void swiglu_cast_kernel(const uint16_t* __rest
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) {
       const int c0 = cg + o * F;
-      if (WRITE_Y) {
-        uint8_t* dst = y + (int64_t)r0 * ocols + c0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) mi::st8<MI_NT_Y>(dst + (int64_t)i * ocols, lo[o][i], hi[o][i]);
-      }
-      if (WRITE_T) {
-        u32 a[4], b[4], c[4], dd[4];
-        transpose4x4(lo[o][0], lo[o][1], lo[o][2], lo[o][3], a[0], a[1], a[2], a[3]);
-        transpose4x4(lo[o][4], lo[o][5], lo[o][6], lo[o][7], b[0], b[1], b[2], b[3]);
-        transpose4x4(hi[o][0], hi[o][1], hi[o][2], hi[o][3], c[0], c[1], c[2], c[3]);
-        transpose4x4(hi[o][4], hi[o][5], hi[o][6], hi[o][7], dd[0], dd[1], dd[2], dd[3]);
-        uint8_t* dst = yT + (int64_t)c0 * rows + r0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          mi::st8<MI_NT_YT>(dst + (int64_t)j * rows, a[j], b[j]);
-          mi::st8<MI_NT_YT>(dst + (int64_t)(j + 4) * rows, c[j], dd[j]);
-        }
-      }
+      if (WRITE_Y) store_rows8<MI_NT_Y>(y + (int64_t)r0 * ocols + c0, ocols, lo[o], hi[o]);
+      if (WRITE_T) store_cols8<MI_NT_YT>(yT + (int64_t)c0 * rows + r0, rows, lo[o], hi[o]);
     }
   }
   if (MODE == 1 && colsum != nullptr) {
@@ -302,34 +286,17 @@ __global__ __launch_bounds__(256) void swiglu_cast_kernel(const uint16_t* __rest
     const int c = tile_c * 128 + (tid & 127), o = tid >> 7;
     if (c < F) colsum[(int64_t)tile_r * ocols + o * F + c] = s_col[MODE == 1 ? o : 0][0][tid & 127] + s_col[MODE == 1 ? o : 0][1][tid & 127];
   }
-  if (amax_out != nullptr) {
-    amax = wave_max(amax);
-    if (lane == 0) s_amax[wave] = amax;
-    __syncthreads();
-    if (tid == 0) {
-      float m = fmaxf(fmaxf(s_amax[0], s_amax[1]), fmaxf(s_amax[2], s_amax[3]));
-      // only a workgroup that would raise the value goes to the atomic unit: same-address atomics are served one at a time and a
-      // wave cannot retire before its atomic has returned (thousands of workgroups per launch)
-      if (m > 0.0f && m > __builtin_nontemporal_load(amax_out)) atomicMax(reinterpret_cast<unsigned int*>(amax_out), __float_as_uint(m));
-    }
-  }
+  publish_amax(amax, amax_out);
 }
 
-template <int FMT, int MODE>
-static int launch_swiglu(const void* h, const void* d, void* y, void* yT, const float* scale, float* amax, float* colsum,
-                         int64_t rows, int64_t F, hipStream_t st, const void* bias = nullptr) {
-  const int64_t ocols = MODE == 0 ? F : 2 * F;
-  (void)ocols;
+template <int MODE>
+static int launch_swiglu(int fmt, const void* h, const void* d, void* y, void* yT, const float* scale, float* amax, float* colsum,
+                         int64_t rows, int64_t F, void* stream, const void* bias = nullptr) {
   const int tiles_r = (int)((rows + 127) / 128), tiles_c = (int)((F + 127) / 128);  // tiles of the [rows, F] gate space
   dim3 grid((unsigned)(tiles_r * tiles_c)), block(256);
-  const uint16_t *hp = (const uint16_t*)h, *dp = (const uint16_t*)d, *bp = (const uint16_t*)bias;
-  uint8_t *yp = (uint8_t*)y, *tp = (uint8_t*)yT;
-  if (y && yT)
-    hipLaunchKernelGGL((swiglu_cast_kernel<FMT, MODE, true, true>), grid, block, 0, st, hp, dp, yp, tp, scale, amax, colsum, (int)rows, (int)F, tiles_c, bp);
-  else if (y)
-    hipLaunchKernelGGL((swiglu_cast_kernel<FMT, MODE, true, false>), grid, block, 0, st, hp, dp, yp, tp, scale, amax, colsum, (int)rows, (int)F, tiles_c, bp);
-  else
-    hipLaunchKernelGGL((swiglu_cast_kernel<FMT, MODE, false, true>), grid, block, 0, st, hp, dp, yp, tp, scale, amax, colsum, (int)rows, (int)F, tiles_c, bp);
+  MI_LAUNCH_FMT_YT(fmt, y, yT, swiglu_cast_kernel, (MODE, ), (), grid, block, 0, (hipStream_t)stream, (const uint16_t*)h,
+                   (const uint16_t*)d, (uint8_t*)y, (uint8_t*)yT, scale, amax, colsum, (int)rows, (int)F, tiles_c,
+                   (const uint16_t*)bias);
   MI_CHECK_LAUNCH("mi_swiglu_cast launch");
   return MI_OK;
 }
@@ -368,7 +335,6 @@ __global__ __launch_bounds__(256) void norm_cast_kernel(const uint16_t* __restri
                                                         const uint16_t* __restrict__ gamma, uint8_t* __restrict__ y,
                                                         uint8_t* __restrict__ yT, const float* __restrict__ scale_p,
                                                         float* amax_out, int rows, int cols, int tiles_c) {
-  __shared__ float s_amax[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntiles = ((rows + 63) / 64) * tiles_c;  // tiles_c: 64-column tiles
   const int stride = gridDim.x * 4;
@@ -423,38 +389,12 @@ __global__ __launch_bounds__(256) void norm_cast_kernel(const uint16_t* __restri
         lo[i] = cvt4_fp8<FMT>(f[0] * scale, f[1] * scale, f[2] * scale, f[3] * scale);
         hi[i] = cvt4_fp8<FMT>(f[4] * scale, f[5] * scale, f[6] * scale, f[7] * scale);
       }
-      if (WRITE_Y) {
-        uint8_t* dst = y + (int64_t)r0 * cols + c0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) mi::st8<MI_NT_Y>(dst + (int64_t)i * cols, lo[i], hi[i]);
-      }
-      if (WRITE_T) {
-        u32 a[4], b[4], c[4], d[4];
-        transpose4x4(lo[0], lo[1], lo[2], lo[3], a[0], a[1], a[2], a[3]);
-        transpose4x4(lo[4], lo[5], lo[6], lo[7], b[0], b[1], b[2], b[3]);
-        transpose4x4(hi[0], hi[1], hi[2], hi[3], c[0], c[1], c[2], c[3]);
-        transpose4x4(hi[4], hi[5], hi[6], hi[7], d[0], d[1], d[2], d[3]);
-        uint8_t* dst = yT + (int64_t)c0 * rows + r0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          mi::st8<MI_NT_YT>(dst + (int64_t)j * rows, a[j], b[j]);
-          mi::st8<MI_NT_YT>(dst + (int64_t)(j + 4) * rows, c[j], d[j]);
-        }
-      }
+      if (WRITE_Y) store_rows8<MI_NT_Y>(y + (int64_t)r0 * cols + c0, cols, lo, hi);
+      if (WRITE_T) store_cols8<MI_NT_YT>(yT + (int64_t)c0 * rows + r0, rows, lo, hi);
     }
     t = tn;
   }
-  if (amax_out != nullptr) {
-    amax = wave_max(amax);
-    if (lane == 0) s_amax[wave] = amax;
-    __syncthreads();
-    if (tid == 0) {
-      float m = fmaxf(fmaxf(s_amax[0], s_amax[1]), fmaxf(s_amax[2], s_amax[3]));
-      // only a workgroup that would raise the value goes to the atomic unit: same-address atomics are served one at a time and a
-      // wave cannot retire before its atomic has returned
-      if (m > 0.0f && m > __builtin_nontemporal_load(amax_out)) atomicMax(reinterpret_cast<unsigned int*>(amax_out), __float_as_uint(m));
-    }
-  }
+  publish_amax(amax, amax_out);
 }
 
 // RMSNorm backward.  dy = grad w.r.t. the normalised output (the dgrad GEMM's bf16 result), xhat = x * rstd:
@@ -652,11 +592,10 @@ __global__ __launch_bounds__(256) void ce_bwd_cast_kernel(const uint16_t* __rest
                                                           uint8_t* __restrict__ y, uint8_t* __restrict__ yT,
                                                           const float* __restrict__ scale_p, float* amax_out, int rows, int cols,
                                                           int tiles_c) {
-  __shared__ float s_amax[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tile_r = blockIdx.x / tiles_c, tile_c = blockIdx.x % tiles_c;
   const int r0 = tile_r * 128 + (wave >> 1) * 64 + (lane >> 3) * 8;
-  const int c0 = tile_c * 128 + (wave & 1) * 64 + (lane & 7) * 8;
+  const int c0 =tile_c * 128 + (wave & 1) * 64 + (lane & 7) * 8;
   const float scale = *scale_p, g0 = *gscale;
   float amax = 0.0f;
   if ((r0 < rows) && (c0 < cols)) {
@@ -682,36 +621,10 @@ __global__ __launch_bounds__(256) void ce_bwd_cast_kernel(const uint16_t* __rest
       lo[i] = cvt4_fp8<FMT>(f[0] * scale, f[1] * scale, f[2] * scale, f[3] * scale);
       hi[i] = cvt4_fp8<FMT>(f[4] * scale, f[5] * scale, f[6] * scale, f[7] * scale);
     }
-    if (WRITE_Y) {
-      uint8_t* dst = y + (int64_t)r0 * cols + c0;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) mi::st8<MI_NT_Y>(dst + (int64_t)i * cols, lo[i], hi[i]);
-    }
-    if (WRITE_T) {
-      u32 a[4], b[4], c[4], d[4];
-      transpose4x4(lo[0], lo[1], lo[2], lo[3], a[0], a[1], a[2], a[3]);
-      transpose4x4(lo[4], lo[5], lo[6], lo[7], b[0], b[1], b[2], b[3]);
-      transpose4x4(hi[0], hi[1], hi[2], hi[3], c[0], c[1], c[2], c[3]);
-      transpose4x4(hi[4], hi[5], hi[6], hi[7], d[0], d[1], d[2], d[3]);
-      uint8_t* dst = yT + (int64_t)c0 * rows + r0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        mi::st8<MI_NT_YT>(dst + (int64_t)j * rows, a[j], b[j]);
-        mi::st8<MI_NT_YT>(dst + (int64_t)(j + 4) * rows, c[j], d[j]);
-      }
-    }
+    if (WRITE_Y) store_rows8<MI_NT_Y>(y + (int64_t)r0 * cols + c0, cols, lo, hi);
+    if (WRITE_T) store_cols8<MI_NT_YT>(yT + (int64_t)c0 * rows + r0, rows, lo, hi);
   }
-  if (amax_out != nullptr) {
-    amax = wave_max(amax);
-    if (lane == 0) s_amax[wave] = amax;
-    __syncthreads();
-    if (tid == 0) {
-      const float m = fmaxf(fmaxf(s_amax[0], s_amax[1]), fmaxf(s_amax[2], s_amax[3]));
-      // only a workgroup that would raise the value goes to the atomic unit: same-address atomics are served one at a time and a
-      // wave cannot retire before its atomic has returned (thousands of workgroups per launch)
-      if (m > 0.0f && m > __builtin_nontemporal_load(amax_out)) atomicMax(reinterpret_cast<unsigned int*>(amax_out), __float_as_uint(m));
-    }
-  }
+  publish_amax(amax, amax_out);
 }
 
 }  // namespace mi
@@ -757,22 +670,9 @@ extern "C" int mi_rope_qkv_bwd_cast(const void* dq_bf16, const void* dk_bf16, co
   if (rows == 0) return MI_OK;
   const int64_t units = ((rows + 63) / 64) * (int64_t)(n_q_heads + 3 * n_kv_heads);
   dim3 grid((unsigned)((units + 3) / 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define MI_RC(FMTv)                                                                                                          \
-  if (y_fp8 && yT_fp8)                                                                                                       \
-    hipLaunchKernelGGL((mi::rope_bwd_cast_kernel<FMTv, true, true>), grid, block, 0, st, (const uint16_t*)dq_bf16,           \
-                       (const uint16_t*)dk_bf16, (const uint16_t*)dv_bf16, cos_tab, sin_tab, (uint8_t*)y_fp8, (uint8_t*)yT_fp8, \
-                       scale, amax, (int)rows, (int)seq, n_q_heads, n_kv_heads);                                             \
-  else if (y_fp8)                                                                                                            \
-    hipLaunchKernelGGL((mi::rope_bwd_cast_kernel<FMTv, true, false>), grid, block, 0, st, (const uint16_t*)dq_bf16,          \
-                       (const uint16_t*)dk_bf16, (const uint16_t*)dv_bf16, cos_tab, sin_tab, (uint8_t*)y_fp8, (uint8_t*)yT_fp8, \
-                       scale, amax, (int)rows, (int)seq, n_q_heads, n_kv_heads);                                             \
-  else                                                                                                                       \
-    hipLaunchKernelGGL((mi::rope_bwd_cast_kernel<FMTv, false, true>), grid, block, 0, st, (const uint16_t*)dq_bf16,          \
-                       (const uint16_t*)dk_bf16, (const uint16_t*)dv_bf16, cos_tab, sin_tab, (uint8_t*)y_fp8, (uint8_t*)yT_fp8, \
-                       scale, amax, (int)rows, (int)seq, n_q_heads, n_kv_heads);
-  if (fmt == MI_FMT_E4M3) { MI_RC(MI_FMT_E4M3) } else { MI_RC(MI_FMT_E5M2) }
-#undef MI_RC
+  MI_LAUNCH_FMT_YT(fmt, y_fp8, yT_fp8, mi::rope_bwd_cast_kernel, (), (), grid, block, 0, (hipStream_t)stream, (const uint16_t*)dq_bf16,
+                   (const uint16_t*)dk_bf16, (const uint16_t*)dv_bf16, cos_tab, sin_tab, (uint8_t*)y_fp8, (uint8_t*)yT_fp8, scale, amax,
+                   (int)rows, (int)seq, n_q_heads, n_kv_heads);
   MI_CHECK_LAUNCH("mi_rope_qkv_bwd_cast launch");
   return MI_OK;
 }
@@ -793,9 +693,7 @@ extern "C" int mi_swiglu_cast(const void* h_bf16, void* y_fp8, void* yT_fp8, con
   int rc = swiglu_common_check("mi_swiglu_cast", h_bf16, y_fp8, yT_fp8, scale, rows, F, fmt);
   if (rc != MI_OK) return rc;
   if (rows == 0 || F == 0) return MI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (fmt == MI_FMT_E4M3) return mi::launch_swiglu<MI_FMT_E4M3, 0>(h_bf16, nullptr, y_fp8, yT_fp8, scale, amax, nullptr, rows, F, st);
-  return mi::launch_swiglu<MI_FMT_E5M2, 0>(h_bf16, nullptr, y_fp8, yT_fp8, scale, amax, nullptr, rows, F, st);
+  return mi::launch_swiglu<0>(fmt, h_bf16, nullptr, y_fp8, yT_fp8, scale, amax, nullptr, rows, F, stream);
 }
 
 extern "C" int mi_dswiglu_cast(const void* h_bf16, const void* dact_bf16, void* y_fp8, void* yT_fp8, const float* scale,
@@ -804,10 +702,7 @@ extern "C" int mi_dswiglu_cast(const void* h_bf16, const void* dact_bf16, void* 
   if (rc != MI_OK) return rc;
   MI_CHECK_ARG(dact_bf16 && ((uintptr_t)dact_bf16 % 16) == 0, "mi_dswiglu_cast: dact must be non-null and 16-byte aligned");
   if (rows == 0 || F == 0) return MI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (fmt == MI_FMT_E4M3)
-    return mi::launch_swiglu<MI_FMT_E4M3, 1>(h_bf16, dact_bf16, y_fp8, yT_fp8, scale, amax, colsum, rows, F, st);
-  return mi::launch_swiglu<MI_FMT_E5M2, 1>(h_bf16, dact_bf16, y_fp8, yT_fp8, scale, amax, colsum, rows, F, st);
+  return mi::launch_swiglu<1>(fmt, h_bf16, dact_bf16, y_fp8, yT_fp8, scale, amax, colsum, rows, F, stream);
 }
 
 // mi_swiglu_cast / mi_dswiglu_cast with the fc1 bias (bf16 [2F], 16-byte aligned) added to h inside the kernel: `h` is the fc1
@@ -818,9 +713,7 @@ extern "C" int mi_swiglu_cast_bias(const void* h_bf16, const void* bias_bf16, vo
   if (rc != MI_OK) return rc;
   MI_CHECK_ARG(bias_bf16 && ((uintptr_t)bias_bf16 % 16) == 0, "mi_swiglu_cast_bias: bias must be non-null and 16-byte aligned");
   if (rows == 0 || F == 0) return MI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (fmt == MI_FMT_E4M3) return mi::launch_swiglu<MI_FMT_E4M3, 0>(h_bf16, nullptr, y_fp8, yT_fp8, scale, amax, nullptr, rows, F, st, bias_bf16);
-  return mi::launch_swiglu<MI_FMT_E5M2, 0>(h_bf16, nullptr, y_fp8, yT_fp8, scale, amax, nullptr, rows, F, st, bias_bf16);
+  return mi::launch_swiglu<0>(fmt, h_bf16, nullptr, y_fp8, yT_fp8, scale, amax, nullptr, rows, F, stream, bias_bf16);
 }
 
 extern "C" int mi_dswiglu_cast_bias(const void* h_bf16, const void* bias_bf16, const void* dact_bf16, void* y_fp8, void* yT_fp8,
@@ -830,10 +723,7 @@ extern "C" int mi_dswiglu_cast_bias(const void* h_bf16, const void* bias_bf16, c
   MI_CHECK_ARG(dact_bf16 && ((uintptr_t)dact_bf16 % 16) == 0, "mi_dswiglu_cast_bias: dact must be non-null and 16-byte aligned");
   MI_CHECK_ARG(bias_bf16 && ((uintptr_t)bias_bf16 % 16) == 0, "mi_dswiglu_cast_bias: bias must be non-null and 16-byte aligned");
   if (rows == 0 || F == 0) return MI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (fmt == MI_FMT_E4M3)
-    return mi::launch_swiglu<MI_FMT_E4M3, 1>(h_bf16, dact_bf16, y_fp8, yT_fp8, scale, amax, colsum, rows, F, st, bias_bf16);
-  return mi::launch_swiglu<MI_FMT_E5M2, 1>(h_bf16, dact_bf16, y_fp8, yT_fp8, scale, amax, colsum, rows, F, st, bias_bf16);
+  return mi::launch_swiglu<1>(fmt, h_bf16, dact_bf16, y_fp8, yT_fp8, scale, amax, colsum, rows, F, stream, bias_bf16);
 }
 
 namespace mi {
@@ -930,18 +820,8 @@ extern "C" int mi_norm_cast(const void* x_bf16, const float* rstd, const void* g
   if (hipGetDevice(&devid) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess || ncu <= 0) ncu = 256;
   const int64_t cap = (int64_t)ncu * 2;  // two workgroups per CU, a whole multiple of the CU count (profiles/r03_cast_grid_sweep.txt)
   dim3 grid((unsigned)(wgs < cap ? wgs : cap)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const uint16_t *xp = (const uint16_t*)x_bf16, *gp = (const uint16_t*)gamma_bf16;
-  uint8_t *yp = (uint8_t*)y_fp8, *tp = (uint8_t*)yT_fp8;
-#define MI_NC(FMTv)                                                                                                        \
-  if (y_fp8 && yT_fp8)                                                                                                     \
-    hipLaunchKernelGGL((mi::norm_cast_kernel<FMTv, true, true>), grid, block, 0, st, xp, rstd, gp, yp, tp, scale, amax, (int)rows, (int)cols, tiles_c); \
-  else if (y_fp8)                                                                                                          \
-    hipLaunchKernelGGL((mi::norm_cast_kernel<FMTv, true, false>), grid, block, 0, st, xp, rstd, gp, yp, tp, scale, amax, (int)rows, (int)cols, tiles_c); \
-  else                                                                                                                     \
-    hipLaunchKernelGGL((mi::norm_cast_kernel<FMTv, false, true>), grid, block, 0, st, xp, rstd, gp, yp, tp, scale, amax, (int)rows, (int)cols, tiles_c);
-  if (fmt == MI_FMT_E4M3) { MI_NC(MI_FMT_E4M3) } else { MI_NC(MI_FMT_E5M2) }
-#undef MI_NC
+  MI_LAUNCH_FMT_YT(fmt, y_fp8, yT_fp8, mi::norm_cast_kernel, (), (), grid, block, 0, (hipStream_t)stream, (const uint16_t*)x_bf16, rstd,
+                   (const uint16_t*)gamma_bf16, (uint8_t*)y_fp8, (uint8_t*)yT_fp8, scale, amax, (int)rows, (int)cols, tiles_c);
   MI_CHECK_LAUNCH("mi_norm_cast launch");
   return MI_OK;
 }
@@ -1013,17 +893,8 @@ extern "C" int mi_ce_backward_cast(const void* logits_bf16, const int64_t* label
   const int tiles_r = (int)((rows + 127) / 128), tiles_c = (int)((cols + 127) / 128);
   MI_CHECK_ARG((int64_t)tiles_r * tiles_c < (1LL << 31), "mi_ce_backward_cast: shape too large");
   dim3 grid((unsigned)(tiles_r * tiles_c)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define MI_CC(FMTv, WY, WT)                                                                                              \
-  hipLaunchKernelGGL((mi::ce_bwd_cast_kernel<FMTv, WY, WT>), grid, block, 0, st, (const uint16_t*)logits_bf16, labels, lse, \
-                     gscale, (uint8_t*)y_fp8, (uint8_t*)yT_fp8, scale, amax, (int)rows, (int)cols, tiles_c)
-#define MI_CC_F(FMTv)                                    \
-  if (y_fp8 && yT_fp8) MI_CC(FMTv, true, true);          \
-  else if (y_fp8) MI_CC(FMTv, true, false);              \
-  else MI_CC(FMTv, false, true);
-  if (fmt == MI_FMT_E4M3) { MI_CC_F(MI_FMT_E4M3) } else { MI_CC_F(MI_FMT_E5M2) }
-#undef MI_CC_F
-#undef MI_CC
+  MI_LAUNCH_FMT_YT(fmt, y_fp8, yT_fp8, mi::ce_bwd_cast_kernel, (), (), grid, block, 0, (hipStream_t)stream, (const uint16_t*)logits_bf16,
+                   labels, lse, gscale, (uint8_t*)y_fp8, (uint8_t*)yT_fp8, scale, amax, (int)rows, (int)cols, tiles_c);
   MI_CHECK_LAUNCH("mi_ce_backward_cast launch");
   return MI_OK;
 }

@@ -36,10 +36,8 @@ __global__ __launch_bounds__(256) void mxfp8_quant_kernel(const uint16_t* __rest
   const int tile_r = blockIdx.x / tiles_c, tile_c = blockIdx.x % tiles_c;
   const int r0 = tile_r * 128 + (wave >> 1) * 64 + (lane >> 3) * 8;
   const int c0 = tile_c * 128 + (wave & 1) * 64 + (lane & 7) * 8;
-  const float rcp = 1.0f / fp8_max_of<FMT>();
   const bool active = (r0 < rows) && (c0 < cols);
-  float f[8][8];  // values as cast; a NaN is replaced by 0 here and recorded in `nanmask` (bit 8 i + j): the block amax then
-                  // needs no per-element test (fmaxf semantics: NaN ignored) and the byte is patched to 0x7F after the cast
+  float f[8][8];  // values as cast; a NaN is replaced by 0 and recorded in `nanmask` (mx_take_nans, mi_common.h)
   unsigned long long nanmask = 0;
   bool any_nan = false;
   if (PRE == 0) {
@@ -183,110 +181,38 @@ __global__ __launch_bounds__(256) void mxfp8_quant_kernel(const uint16_t* __rest
       if (c < cols) colsum[(int64_t)tile_r * cols + c] = s_col[0][tid] + s_col[1][tid];
     }
   }
-  if (__builtin_expect(any_nan, PRE != 0)) {  // PRE == 0: only threads whose packed screen saw a NaN come here
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (f[i][j] != f[i][j]) {
-          nanmask |= 1ull << (8 * i + j);
-          f[i][j] = 0.0f;
-        }
-  }
-  // bytes of a packed fp8 word (elements (i, j0..j0+3)) -> 0x7F where the mask says the source was a NaN (rare path)
-  auto patch4 = [&](u32 w, int bit0) -> u32 {
-    if (__builtin_expect(nanmask != 0, 0)) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if ((nanmask >> (bit0 + k)) & 1) w = (w & ~(0xFFu << (8 * k))) | (0x7Fu << (8 * k));
-    }
-    return w;
-  };
-  // NOTE: shuffles below are executed by every lane (inactive lanes carry zeros); rows/cols are
+  if (__builtin_expect(any_nan, PRE != 0)) nanmask = mx_take_nans(f);  // PRE == 0: only threads whose packed screen saw a NaN come here
+  // NOTE: the quantisers' shuffles are executed by every lane (inactive lanes carry zeros); rows/cols are
   // multiples of 32 so a 4-lane block group is all-active or all-inactive.
+  u32 lo[8], hi[8], sbytes[8];
   if (ROWWISE) {
-    u32 sbytes[8];
-    u32 lo[8], hi[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float a = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a = fmaxf(a, fabsf(f[i][j]));
-      a = fmaxf(a, __shfl_xor(a, 1));
-      a = fmaxf(a, __shfl_xor(a, 2));
-      u32 e = e8m0_roundup(a * rcp);
-      float inv = e8m0_inv(e);
-      sbytes[i] = e;
-      lo[i] = patch4(cvt4_fp8<FMT>(f[i][0] * inv, f[i][1] * inv, f[i][2] * inv, f[i][3] * inv), 8 * i);
-      hi[i] = patch4(cvt4_fp8<FMT>(f[i][4] * inv, f[i][5] * inv, f[i][6] * inv, f[i][7] * inv), 8 * i + 4);
-    }
+    mx_quant_rows<FMT>(f, nanmask, lo, hi, sbytes);
     if (active) {
-      uint8_t* dst = y_row + (int64_t)r0 * cols + c0;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) mi::st8<MI_NT_Y>(dst + (int64_t)i * cols, lo[i], hi[i]);
-      if ((lane & 3) == 0) {  // block-major scales [cols/32, rows]: this lane's 8 rows are 8 contiguous bytes
-        const u32 lo4 = sbytes[0] | (sbytes[1] << 8) | (sbytes[2] << 16) | (sbytes[3] << 24);
-        const u32 hi4 = sbytes[4] | (sbytes[5] << 8) | (sbytes[6] << 16) | (sbytes[7] << 24);
-        *reinterpret_cast<uint2*>(s_row + (int64_t)(c0 / 32) * ldr + r0) = make_uint2(lo4, hi4);
-      }
+      store_rows8<MI_NT_Y>(y_row + (int64_t)r0 * cols + c0, cols, lo, hi);
+      // block-major scales [cols/32, rows]: this lane's 8 rows are 8 contiguous bytes
+      if ((lane & 3) == 0) store_scales8(s_row + (int64_t)(c0 / 32) * ldr + r0, sbytes);
     }
   }
   if (COLWISE) {
-    u32 sbytes[8];
-    float inv[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float a = 0.0f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) a = fmaxf(a, fabsf(f[i][j]));
-      a = fmaxf(a, __shfl_xor(a, 8));
-      a = fmaxf(a, __shfl_xor(a, 16));
-      u32 e = e8m0_roundup(a * rcp);
-      sbytes[j] = e;
-      inv[j] = e8m0_inv(e);
-    }
-    u32 lo[8], hi[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      lo[i] = patch4(cvt4_fp8<FMT>(f[i][0] * inv[0], f[i][1] * inv[1], f[i][2] * inv[2], f[i][3] * inv[3]), 8 * i);
-      hi[i] = patch4(cvt4_fp8<FMT>(f[i][4] * inv[4], f[i][5] * inv[5], f[i][6] * inv[6], f[i][7] * inv[7]), 8 * i + 4);
-    }
+    mx_quant_cols<FMT>(f, nanmask, lo, hi, sbytes);
     if (active) {
-      u32 a[4], b[4], c[4], d[4];
-      transpose4x4(lo[0], lo[1], lo[2], lo[3], a[0], a[1], a[2], a[3]);
-      transpose4x4(lo[4], lo[5], lo[6], lo[7], b[0], b[1], b[2], b[3]);
-      transpose4x4(hi[0], hi[1], hi[2], hi[3], c[0], c[1], c[2], c[3]);
-      transpose4x4(hi[4], hi[5], hi[6], hi[7], d[0], d[1], d[2], d[3]);
-      uint8_t* dst = y_colT + (int64_t)c0 * ldr + r0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        mi::st8<MI_NT_YT>(dst + (int64_t)j * ldr, a[j], b[j]);
-        mi::st8<MI_NT_YT>(dst + (int64_t)(j + 4) * ldr, c[j], d[j]);
-      }
-      if (((lane >> 3) & 3) == 0) {  // block-major scales [rows/32, cols]: 8 contiguous bytes for this lane's 8 columns
-        const u32 lo4 = sbytes[0] | (sbytes[1] << 8) | (sbytes[2] << 16) | (sbytes[3] << 24);
-        const u32 hi4 = sbytes[4] | (sbytes[5] << 8) | (sbytes[6] << 16) | (sbytes[7] << 24);
-        *reinterpret_cast<uint2*>(s_colT + (int64_t)(r0 / 32) * cols + c0) = make_uint2(lo4, hi4);
-      }
+      store_cols8<MI_NT_YT>(y_colT + (int64_t)c0 * ldr + r0, ldr, lo, hi);
+      // block-major scales [rows/32, cols]: 8 contiguous bytes for this lane's 8 columns
+      if (((lane >> 3) & 3) == 0) store_scales8(s_colT + (int64_t)(r0 / 32) * cols + c0, sbytes);
     }
   }
 }
 
-template <int FMT, int PRE>
-static int launch_mx(const void* x, const void* aux16, const float* aux32, void* y_row, void* s_row, void* y_colT, void* s_colT,
-                     float* colsum, int64_t rows, int64_t cols, hipStream_t st, int64_t ld_rows = 0, const void* e0 = nullptr,
+template <int PRE>
+static int launch_mx(int fmt, const void* x, const void* aux16, const float* aux32, void* y_row, void* s_row, void* y_colT, void* s_colT,
+                     float* colsum, int64_t rows, int64_t cols, void* stream, int64_t ld_rows = 0, const void* e0 = nullptr,
                      const float* e1 = nullptr, int i0 = 0, int i1 = 0, int i2 = 0) {
   const int ldr = (int)(ld_rows > 0 ? ld_rows : rows);
   const int tiles_r = (int)((rows + 127) / 128), tiles_c = (int)((cols + 127) / 128);
   dim3 grid((unsigned)(tiles_r * tiles_c)), block(256);
-  const uint16_t *xp = (const uint16_t*)x, *ap = (const uint16_t*)aux16;
-  uint8_t *yr = (uint8_t*)y_row, *sr = (uint8_t*)s_row, *yc = (uint8_t*)y_colT, *sc = (uint8_t*)s_colT;
-  if (y_row && y_colT)
-    hipLaunchKernelGGL((mxfp8_quant_kernel<FMT, true, true, PRE>), grid, block, 0, st, xp, ap, aux32, yr, sr, yc, sc, colsum, (int)rows, (int)cols, tiles_c, ldr, (const uint16_t*)e0, e1, i0, i1, i2);
-  else if (y_row)
-    hipLaunchKernelGGL((mxfp8_quant_kernel<FMT, true, false, PRE>), grid, block, 0, st, xp, ap, aux32, yr, sr, yc, sc, colsum, (int)rows, (int)cols, tiles_c, ldr, (const uint16_t*)e0, e1, i0, i1, i2);
-  else
-    hipLaunchKernelGGL((mxfp8_quant_kernel<FMT, false, true, PRE>), grid, block, 0, st, xp, ap, aux32, yr, sr, yc, sc, colsum, (int)rows, (int)cols, tiles_c, ldr, (const uint16_t*)e0, e1, i0, i1, i2);
+  MI_LAUNCH_FMT_YT(fmt, y_row, y_colT, mxfp8_quant_kernel, (), (, PRE), grid, block, 0, (hipStream_t)stream, (const uint16_t*)x,
+                   (const uint16_t*)aux16, aux32, (uint8_t*)y_row, (uint8_t*)s_row, (uint8_t*)y_colT, (uint8_t*)s_colT, colsum, (int)rows,
+                   (int)cols, tiles_c, ldr, (const uint16_t*)e0, e1, i0, i1, i2);
   MI_CHECK_LAUNCH("mi_mxfp8_quantize launch");
   return MI_OK;
 }
@@ -307,9 +233,7 @@ static int mx_common_check(const char* who, const void* x, const void* y_row, co
   return MI_OK;
 }
 
-#define MI_MX_DISPATCH(PRE, x, a16, a32, cs, rows, cols)                                                                       \
-  (fmt == MI_FMT_E4M3 ? mi::launch_mx<MI_FMT_E4M3, PRE>(x, a16, a32, y_row, s_row, y_colT, s_colT, cs, rows, cols, (hipStream_t)stream) \
-                      : mi::launch_mx<MI_FMT_E5M2, PRE>(x, a16, a32, y_row, s_row, y_colT, s_colT, cs, rows, cols, (hipStream_t)stream))
+#define MI_MX_DISPATCH(PRE, x, a16, a32, cs, rows, cols) mi::launch_mx<PRE>(fmt, x, a16, a32, y_row, s_row, y_colT, s_colT, cs, rows, cols, stream)
 
 extern "C" int mi_mxfp8_quantize(const void* x_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT,
                                  int64_t rows, int64_t cols, int fmt, void* stream) {
@@ -326,9 +250,7 @@ extern "C" int mi_mxfp8_quantize_ex(const void* x_bf16, void* y_row, void* s_row
   MI_CHECK_ARG(ld_rows >= rows && ld_rows % 8 == 0 && ld_rows < (1LL << 31), "mi_mxfp8_quantize_ex: ld_rows (%lld) must be >= rows and a multiple of 8",
                (long long)ld_rows);
   if (rows == 0 || cols == 0) return MI_OK;
-  return (fmt == MI_FMT_E4M3
-              ? mi::launch_mx<MI_FMT_E4M3, 0>(x_bf16, nullptr, nullptr, y_row, s_row, y_colT, s_colT, colsum, rows, cols, (hipStream_t)stream, ld_rows)
-              : mi::launch_mx<MI_FMT_E5M2, 0>(x_bf16, nullptr, nullptr, y_row, s_row, y_colT, s_colT, colsum, rows, cols, (hipStream_t)stream, ld_rows));
+  return mi::launch_mx<0>(fmt, x_bf16, nullptr, nullptr, y_row, s_row, y_colT, s_colT, colsum, rows, cols, stream, ld_rows);
 }
 
 extern "C" int mi_mxfp8_norm_quantize(const void* x_bf16, const float* rstd, const void* gamma_bf16, void* y_row, void* s_row,
@@ -368,9 +290,6 @@ extern "C" int mi_mxfp8_rope_bwd_quantize(const void* dq_bf16, const void* dk_bf
   MI_CHECK_ARG(dk_bf16 && dv_bf16 && cos_tab && sin_tab && ((uintptr_t)dk_bf16 % 16) == 0 && ((uintptr_t)dv_bf16 % 16) == 0 &&
                    ((uintptr_t)cos_tab % 16) == 0 && ((uintptr_t)sin_tab % 16) == 0, "mi_mxfp8_rope_bwd_quantize: null or misaligned input");
   if (rows == 0) return MI_OK;
-  return (fmt == MI_FMT_E4M3
-              ? mi::launch_mx<MI_FMT_E4M3, 4>(dq_bf16, dk_bf16, cos_tab, y_row, s_row, y_colT, s_colT, nullptr, rows, W, (hipStream_t)stream,
-                                              0, dv_bf16, sin_tab, n_q_heads, n_kv_heads, (int)seq)
-              : mi::launch_mx<MI_FMT_E5M2, 4>(dq_bf16, dk_bf16, cos_tab, y_row, s_row, y_colT, s_colT, nullptr, rows, W, (hipStream_t)stream,
-                                              0, dv_bf16, sin_tab, n_q_heads, n_kv_heads, (int)seq));
+  return mi::launch_mx<4>(fmt, dq_bf16, dk_bf16, cos_tab, y_row, s_row, y_colT, s_colT, nullptr, rows, W, stream, 0, dv_bf16, sin_tab,
+                          n_q_heads, n_kv_heads, (int)seq);
 }

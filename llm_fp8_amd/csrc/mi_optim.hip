@@ -329,7 +329,6 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restr
 template <typename ST>
 __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
                                                                int chunk_elems, const float* __restrict__ grad_scale, AdamArgs a) {
-  __shared__ float s_amax[4];
   const ChunkRef cr = chunks[blockIdx.x];
   const AdamPtrs<ST> t(tab, T, cr.tensor);
   const int64_t n = tab[(int64_t)4 * T + cr.tensor];
@@ -364,49 +363,19 @@ __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __
       lo[i] = cvt4_fp8<MI_FMT_E4M3>(f[0] * scale, f[1] * scale, f[2] * scale, f[3] * scale);
       hi[i] = cvt4_fp8<MI_FMT_E4M3>(f[4] * scale, f[5] * scale, f[6] * scale, f[7] * scale);
     }
-    if (y != nullptr) {
-      uint8_t* dst = y + r0 * ld_y + c0;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        // nontemporal: the copies are read again only by the NEXT forward; as write-back lines the 64-byte row segments cost
-        // 4.0 ms per step on the 3B parameter set, streamed 1.3 ms (tools/bench_adamw.py)
-        typedef unsigned int v2u_ __attribute__((ext_vector_type(2)));
-        const v2u_ w = {lo[i], hi[i]};
-        __builtin_nontemporal_store(w, reinterpret_cast<v2u_*>(dst + (int64_t)i * ld_y));
-      }
-    }
-    if (yT != nullptr) {
-      u32 ta[4], tb[4], tc[4], td[4];
-      transpose4x4(lo[0], lo[1], lo[2], lo[3], ta[0], ta[1], ta[2], ta[3]);
-      transpose4x4(lo[4], lo[5], lo[6], lo[7], tb[0], tb[1], tb[2], tb[3]);
-      transpose4x4(hi[0], hi[1], hi[2], hi[3], tc[0], tc[1], tc[2], tc[3]);
-      transpose4x4(hi[4], hi[5], hi[6], hi[7], td[0], td[1], td[2], td[3]);
-      uint8_t* dst = yT + c0 * ld_yT + r0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        typedef unsigned int v2u_ __attribute__((ext_vector_type(2)));
-        const v2u_ w0 = {ta[j], tb[j]}, w1 = {tc[j], td[j]};
-        __builtin_nontemporal_store(w0, reinterpret_cast<v2u_*>(dst + (int64_t)j * ld_yT));
-        __builtin_nontemporal_store(w1, reinterpret_cast<v2u_*>(dst + (int64_t)(j + 4) * ld_yT));
-      }
-    }
+    // nontemporal: the copies are read again only by the NEXT forward; as write-back lines the 64-byte row segments cost
+    // 4.0 ms per step on the 3B parameter set, streamed 1.3 ms (tools/bench_adamw.py)
+    if (y != nullptr) store_rows8<true>(y + r0 * ld_y + c0, ld_y, lo, hi);
+    if (yT != nullptr) store_cols8<true>(yT + c0 * ld_yT + r0, ld_yT, lo, hi);
   }
-  if (amax_out != nullptr) {
-    amax = wave_max(amax);
-    if (lane == 0) s_amax[wave] = amax;
-    __syncthreads();
-    if (tid == 0) {
-      const float mx = fmaxf(fmaxf(s_amax[0], s_amax[1]), fmaxf(s_amax[2], s_amax[3]));
-      if (mx > 0.0f && mx > __builtin_nontemporal_load(amax_out)) atomicMax(reinterpret_cast<unsigned int*>(amax_out), __float_as_uint(mx));
-    }
-  }
+  publish_amax(amax, amax_out);
 }
 
 // AdamW + MXFP8 weight quantisation in one pass: the MXFP8 form of the weight-cast hand-off.  Block scaling has no state -- the
 // E8M0 scale of a 32-element block comes from the block itself -- so the copies the NEXT forward needs (row-wise blocks for
 // fprop, column-wise blocks, stored transposed, for dgrad) can be emitted as soon as the weight is updated.  Same tile walk as
 // adamw_cast_multi_kernel (128 x 128 tile per workgroup, 8 x 8 block per lane); the quantisation of the ROUNDED bf16 weight is
-// mxfp8_quant_kernel's, operation for operation (bitwise the bytes mi_mxfp8_quantize would produce from the updated weight).
+// mxfp8_quant_kernel's: both call mx_quant_rows / mx_quant_cols (mi_common.h).
 // Table rows (int64 each, T columns):
 //   0 p  1 g  2 exp_avg  3 exp_avg_sq  4 numel  5 cols (0 = no sink: flat path)  6 y_row  7 s_row  8 y_colT  9 s_colT
 //   10 ldr (rows of the whole operand the tensor is a row-block of)  11 unused  12 fp32 master weight (ST = float only)
@@ -437,9 +406,7 @@ __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* 
   const int64_t r0 = (int64_t)tile_r * 128 + (wave >> 1) * 64 + (lane >> 3) * 8;
   const int64_t c0 = (int64_t)tile_c * 128 + (wave & 1) * 64 + (lane & 7) * 8;
   const bool active = r0 < rows && c0 < cols;  // rows, cols multiples of 32: a 4-lane block group is all-active or all-inactive
-  const float rcp = 1.0f / fp8_max_of<MI_FMT_E4M3>();
   float f[8][8];
-  unsigned long long nanmask = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     if (active) {
@@ -449,91 +416,18 @@ __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* 
       for (int j = 0; j < 8; ++j) f[i][j] = 0.0f;
     }
   }
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (f[i][j] != f[i][j]) {  // as mxfp8_quant_kernel: a NaN does not enter the block amax and leaves as 0x7F
-        nanmask |= 1ull << (8 * i + j);
-        f[i][j] = 0.0f;
-      }
-  auto patch4 = [&](u32 w, int bit0) -> u32 {
-    if (__builtin_expect(nanmask != 0, 0)) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if ((nanmask >> (bit0 + k)) & 1) w = (w & ~(0xFFu << (8 * k))) | (0x7Fu << (8 * k));
-    }
-    return w;
-  };
-  typedef unsigned int v2u_ __attribute__((ext_vector_type(2)));
-  {  // row-wise blocks (32 columns = 4 lanes)
-    u32 sbytes[8], lo[8], hi[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float am = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) am = fmaxf(am, fabsf(f[i][j]));
-      am = fmaxf(am, __shfl_xor(am, 1));
-      am = fmaxf(am, __shfl_xor(am, 2));
-      const u32 e = e8m0_roundup(am * rcp);
-      const float inv = e8m0_inv(e);
-      sbytes[i] = e;
-      lo[i] = patch4(cvt4_fp8<MI_FMT_E4M3>(f[i][0] * inv, f[i][1] * inv, f[i][2] * inv, f[i][3] * inv), 8 * i);
-      hi[i] = patch4(cvt4_fp8<MI_FMT_E4M3>(f[i][4] * inv, f[i][5] * inv, f[i][6] * inv, f[i][7] * inv), 8 * i + 4);
-    }
-    if (active) {
-      uint8_t* dst = y_row + r0 * cols + c0;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const v2u_ w = {lo[i], hi[i]};
-        __builtin_nontemporal_store(w, reinterpret_cast<v2u_*>(dst + (int64_t)i * cols));
-      }
-      if ((lane & 3) == 0) {
-        const v2u_ w = {sbytes[0] | (sbytes[1] << 8) | (sbytes[2] << 16) | (sbytes[3] << 24),
-                        sbytes[4] | (sbytes[5] << 8) | (sbytes[6] << 16) | (sbytes[7] << 24)};
-        *reinterpret_cast<v2u_*>(s_row + (c0 / 32) * ldr + r0) = w;
-      }
-    }
+  const unsigned long long nanmask = mx_take_nans(f);
+  u32 lo[8], hi[8], sbytes[8];
+  // nontemporal stores, as in adamw_cast_multi_kernel
+  mx_quant_rows<MI_FMT_E4M3>(f, nanmask, lo, hi, sbytes);  // row-wise blocks (32 columns = 4 lanes)
+  if (active) {
+    store_rows8<true>(y_row + r0 * cols + c0, cols, lo, hi);
+    if ((lane & 3) == 0) store_scales8(s_row + (c0 / 32) * ldr + r0, sbytes);
   }
-  {  // column-wise blocks (32 rows = 4 lane rows), stored transposed
-    u32 sbytes[8];
-    float inv[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float am = 0.0f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) am = fmaxf(am, fabsf(f[i][j]));
-      am = fmaxf(am, __shfl_xor(am, 8));
-      am = fmaxf(am, __shfl_xor(am, 16));
-      const u32 e = e8m0_roundup(am * rcp);
-      sbytes[j] = e;
-      inv[j] = e8m0_inv(e);
-    }
-    u32 lo[8], hi[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      lo[i] = patch4(cvt4_fp8<MI_FMT_E4M3>(f[i][0] * inv[0], f[i][1] * inv[1], f[i][2] * inv[2], f[i][3] * inv[3]), 8 * i);
-      hi[i] = patch4(cvt4_fp8<MI_FMT_E4M3>(f[i][4] * inv[4], f[i][5] * inv[5], f[i][6] * inv[6], f[i][7] * inv[7]), 8 * i + 4);
-    }
-    if (active) {
-      u32 ta[4], tb[4], tc[4], td[4];
-      transpose4x4(lo[0], lo[1], lo[2], lo[3], ta[0], ta[1], ta[2], ta[3]);
-      transpose4x4(lo[4], lo[5], lo[6], lo[7], tb[0], tb[1], tb[2], tb[3]);
-      transpose4x4(hi[0], hi[1], hi[2], hi[3], tc[0], tc[1], tc[2], tc[3]);
-      transpose4x4(hi[4], hi[5], hi[6], hi[7], td[0], td[1], td[2], td[3]);
-      uint8_t* dst = y_colT + c0 * ldr + r0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const v2u_ w0 = {ta[j], tb[j]}, w1 = {tc[j], td[j]};
-        __builtin_nontemporal_store(w0, reinterpret_cast<v2u_*>(dst + (int64_t)j * ldr));
-        __builtin_nontemporal_store(w1, reinterpret_cast<v2u_*>(dst + (int64_t)(j + 4) * ldr));
-      }
-      if (((lane >> 3) & 3) == 0) {
-        const v2u_ w = {sbytes[0] | (sbytes[1] << 8) | (sbytes[2] << 16) | (sbytes[3] << 24),
-                        sbytes[4] | (sbytes[5] << 8) | (sbytes[6] << 16) | (sbytes[7] << 24)};
-        *reinterpret_cast<v2u_*>(s_colT + (r0 / 32) * cols + c0) = w;
-      }
-    }
+  mx_quant_cols<MI_FMT_E4M3>(f, nanmask, lo, hi, sbytes);  // column-wise blocks (32 rows = 4 lane rows), stored transposed
+  if (active) {
+    store_cols8<true>(y_colT + c0 * ldr + r0, ldr, lo, hi);
+    if (((lane >> 3) & 3) == 0) store_scales8(s_colT + (r0 / 32) * cols + c0, sbytes);
   }
 }
 

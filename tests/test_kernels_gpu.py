@@ -1170,3 +1170,107 @@ def test_adamw_mxcast_emits_the_bytes_of_the_quantiser(ops, dev, shape, parts):
         assert torch.equal(a.view(torch.int16), b.view(torch.int16))
     for got, want, what in zip((w8, sc, wt8, sct), q_ref, ("row data", "row scales", "column data", "column scales")):
         assert torch.equal(got, want), what
+
+
+# ------------------------------------------------------------------- y-only / yT-only builds of the fused cast kernels
+_SINGLE_OUT = {}  # (op, fmt) -> (run, result of the both-outputs call): inputs and reference are made once per op and format
+
+
+def _single_output_case(ops, dev, op, fmt):
+    """run(want_y, want_t) -> (y, yT, amax, colsum) of one fused cast op on fixed inputs, and the result of run(True, True).
+    Tiled ops: 136 x 200 (a ragged 128 x 128 tile both ways, two steps of the persistent walk per wave); RoPE: 72 rows = 3 sequences
+    of 24, 2 query heads, 1 KV head of dim 128.  Every input holds one NaN and one value whose scaled magnitude is above the
+    format's maximum (57344 covers both)."""
+    key = (op, fmt)
+    if key in _SINGLE_OUT:
+        return _SINGLE_OUT[key]
+    from llm_fp8_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(29)
+    R, F = 136, 200
+    bf = lambda t: t.to(torch.bfloat16).to(dev)
+    if op in ("swiglu", "swiglu_bias", "dswiglu"):
+        h = torch.randn(R, 2 * F, generator=g)
+        h[1, 5] = float("nan")
+        h[3, 7] = h[3, F + 7] = 200.0          # silu(200) * 200 = 40000, times the scale of 8
+        d = torch.randn(R, F, generator=g)
+        d[3, 7] = 100.0                          # backward: 100 * silu(200) = 20000, times the scale
+        h, d = bf(h), bf(d)
+        bias = bf(torch.randn(2 * F, generator=g) * 0.5) if op == "swiglu_bias" else None
+        scale = _f32(8.0, dev)
+
+        def call(a, wy, wt):
+            if op == "dswiglu":
+                return ops.dswiglu_cast(h, d, scale, a, fmt, want_y=wy, want_t=wt, want_colsum=True)
+            return ops.swiglu_cast(h, scale, a, fmt, want_y=wy, want_t=wt, bias=bias) + (None,)
+    elif op == "norm":
+        x = torch.randn(R, F, generator=g)
+        x[1, 5] = float("nan")
+        x[3, 7] = 100.0                          # ~14 after the normalisation, times gamma 64, times the scale of 128
+        gamma = torch.randn(F, generator=g)
+        gamma[7] = 64.0
+        x, gamma = bf(x), bf(gamma)
+        rstd = ops.rmsnorm_stats(x, 1e-5)
+        scale = _f32(128.0, dev)
+        call = lambda a, wy, wt: ops.norm_cast(x, rstd, gamma, scale, a, fmt, want_y=wy, want_t=wt) + (None,)
+    elif op == "rope":
+        T, S, nq, nkv, D = 72, 24, 2, 1, 128
+        dq, dk, dv = torch.randn(T, nq * D, generator=g), torch.randn(T, nkv * D, generator=g) * 3.0, torch.randn(T, nkv * D, generator=g)
+        dq[1, 5] = float("nan")
+        dv[3, 7] = 1e5
+        dq, dk, dv = bf(dq), bf(dk), bf(dv)
+        ang = torch.outer(torch.arange(S, dtype=torch.float32), 1.0 / (10000.0 ** (torch.arange(0, D, 2, dtype=torch.float32) / D)))
+        cos, sin = torch.cos(ang).contiguous().to(dev), torch.sin(ang).contiguous().to(dev)
+        scale = _f32(37.0, dev)
+        call = lambda a, wy, wt: ops.rope_qkv_backward_cast(dq, dk, dv, cos, sin, nq, nkv, D, S, scale, a, fmt, want_y=wy, want_t=wt) + (None,)
+    else:
+        assert op == "ce"
+        logits = torch.randn(R, F, generator=g) * 3
+        logits[1, 5] = float("nan")
+        logits = bf(logits)
+        labels = torch.randint(0, F, (R,), generator=g)
+        labels[9] = -100
+        labels = labels.to(dev)
+        st = torch.cuda.current_stream().cuda_stream
+        lse, loss = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
+        _lib.check(lib.mi_ce_forward(logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), loss.data_ptr(), R, F, st), "mi_ce_forward")
+        gscale, scale = _f32(0.37, dev), _f32(2e5, dev)  # (p - 1) * 0.37 * 2e5 at a label whose p is small: above 57344
+
+        def call(a, wy, wt):
+            y = torch.zeros((R, F), dtype=torch.uint8, device=dev) if wy else None
+            yt = torch.zeros((F, R), dtype=torch.uint8, device=dev) if wt else None
+            _lib.check(lib.mi_ce_backward_cast(logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), gscale.data_ptr(),
+                                               None if y is None else y.data_ptr(), None if yt is None else yt.data_ptr(),
+                                               scale.data_ptr(), a.data_ptr(), R, F, fmt, st), "mi_ce_backward_cast")
+            return y, yt, None
+
+    def run(want_y, want_t):
+        a = torch.zeros(1, device=dev)
+        y, yt, cs = call(a, want_y, want_t)
+        torch.cuda.synchronize()
+        return y, yt, a, cs
+
+    _SINGLE_OUT[key] = (run, run(True, True))
+    return _SINGLE_OUT[key]
+
+
+@pytest.mark.parametrize("which", ["y", "yT"])
+@pytest.mark.parametrize("fmt", [O.E4M3, O.E5M2])
+@pytest.mark.parametrize("op", ["swiglu", "swiglu_bias", "dswiglu", "norm", "rope", "ce"])
+def test_fused_casts_with_one_output_emit_the_bytes_of_the_both_outputs_call(ops, dev, op, fmt, which):
+    """The y-only and the yT-only instantiations of the fused cast kernels are kernels of their own: each writes, byte for byte, the
+    same output as the both-outputs call (which the tests above tie to the oracle), leaves the same amax and, for dSwiGLU, the same
+    column sums."""
+    run, (y2, t2, a2, cs2) = _single_output_case(ops, dev, op, fmt)
+    y, yt, a, cs = run(which == "y", which == "yT")
+    if which == "y":
+        assert yt is None and torch.equal(y, y2)
+    else:
+        assert y is None and torch.equal(yt, t2)
+    assert a2.item() > 0 and torch.equal(a, a2)
+    if op == "dswiglu":
+        assert torch.equal(cs.view(torch.int32), cs2.view(torch.int32))
+    # the inputs did what they are there for: a NaN byte, a saturated byte, and not only those
+    fmax = 0x7E if fmt == O.E4M3 else 0x7B
+    mag = y2 & 0x7F
+    assert int((mag == 0x7F).sum()) >= 1 and int((mag == fmax).sum()) >= 1 and int(((mag != 0) & (mag < fmax)).sum()) > y2.numel() // 2

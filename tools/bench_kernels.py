@@ -297,6 +297,75 @@ def main():
                     print(f"abbase {mname} {name:4s} {kind:5s} {m}x{n}x{k}: base {res['base']*1e6:7.1f} us {fl/res['base']/1e12:6.0f} TF   cur {res['cur']*1e6:7.1f} us "
                           f"{fl/res['cur']/1e12:6.0f} TF   {res['base']/res['cur']:.3f}x", flush=True)
             print(f"abbase {mname} decoder-layer GEMM time: base {tb*1e6:8.1f} us  cur {tc*1e6:8.1f} us  {tb/tc:.3f}x", flush=True)
+    if "castab" in args.which:  # the cast / quantise kernels of this build against a saved one (MI_BASE_LIB), and the noise of the day
+        # Three libraries in one process: `cur`, `base` and `base2`, a second copy of the base FILE (its own load of the same code).
+        # base2 / base is an A/A ratio: its spread over the rows of this run is what the machine does to two equal kernels, and a
+        # cur / base ratio inside that spread is no difference.  The ops go to the library that _lib.load() returns at the call.
+        import shutil
+        import tempfile
+        base_path = os.environ.get("MI_BASE_LIB")
+        if not base_path or not os.path.exists(base_path):
+            raise SystemExit("--which castab: set MI_BASE_LIB to the libmi_fp8.so of the build to compare against")
+        copy = shutil.copy(base_path, os.path.join(tempfile.mkdtemp(), "libmi_fp8_base2.so"))
+        libs = {"base": _mi_lib._bind(base_path, _mi_lib.SIGNATURES), "cur": _mi_lib._bind(_mi_lib.LIB_PATH, _mi_lib.SIGNATURES),
+                "base2": _mi_lib._bind(copy, _mi_lib.SIGNATURES)}
+        lab, rows_out = _mi_lib._lib, []
+
+        def ab(name, fn):
+            def mk(lib_):
+                def f():
+                    _mi_lib._lib = lib_
+                    fn()
+                return f
+            res = time_interleaved({k_: mk(l_) for k_, l_ in libs.items()}, rounds=int(os.environ.get("CASTAB_ROUNDS", "15")), inner=5)
+            _mi_lib._lib = lab
+            rows_out.append((name, res["base"], res["cur"] / res["base"], res["base2"] / res["base"]))
+            print(f"castab {name:34s} base {res['base']*1e6:8.1f} us  cur/base {rows_out[-1][2]:.4f}  base2/base {rows_out[-1][3]:.4f}", flush=True)
+
+        amax = torch.zeros(1, device=dev)
+        bf = lambda *shape: torch.randn(shape, device=dev, dtype=torch.float32, generator=g).to(torch.bfloat16)
+        for (R, C) in ((8192, 3072), (8192, 16384), (16384, 3072), (8192, 8192)):
+            x = bf(R, C)
+            y, yT = torch.empty((R, C), dtype=torch.uint8, device=dev), torch.empty((C, R), dtype=torch.uint8, device=dev)
+            ab(f"cast+T {R}x{C}", lambda: ops.cast_amax(x, one, amax, 0, y=y, yT=yT))
+            ab(f"cast   {R}x{C}", lambda: ops.cast_amax(x, one, amax, 0, y=y, want_t=False))
+            ab(f"castT  {R}x{C}", lambda: ops.cast_amax(x, one, amax, 0, yT=yT, want_y=False))
+        x, y8 = bf(8192, 3072), rand_fp8((8192, 3072), dev, g)
+        ab("cast+T+colsum 8192x3072", lambda: ops.cast_amax(x, one, amax, 1, want_colsum=True))
+        ab("transpose_u8 8192x3072", lambda: ops.transpose_u8(y8))
+        R, F = 8192, 8192
+        h, d = bf(R, 2 * F), bf(R, F)
+        ab(f"swiglu  fwd {R}x{F}", lambda: ops.swiglu_cast(h, one, amax, 0))
+        ab(f"dswiglu bwd {R}x{F}", lambda: ops.dswiglu_cast(h, d, one, amax, 0, want_colsum=True))
+        for (R, C) in ((8192, 3072), (8192, 16384)):
+            x = bf(R, C)
+            ab(f"mxquant {R}x{C}", lambda: ops.mxfp8_quantize(x))
+        x, gamma = bf(8192, 3072), bf(3072)
+        rstd = ops.rmsnorm_stats(x, 1e-5)
+        ab("norm_cast 8192x3072", lambda: ops.norm_cast(x, rstd, gamma, one, amax, 0))
+        T, S, nq, nkv, D = 8192, 8192, 24, 8, 128  # Llama-3.2-3B: d(qkv) of 8192 tokens
+        dq, dk, dv = bf(T, nq * D), bf(T, nkv * D), bf(T, nkv * D)
+        ang = torch.outer(torch.arange(S, dtype=torch.float32), 1.0 / (10000.0 ** (torch.arange(0, D, 2, dtype=torch.float32) / D)))
+        cos, sin = torch.cos(ang).contiguous().to(dev), torch.sin(ang).contiguous().to(dev)
+        ab(f"rope_bwd_cast {T}x{(nq + 2 * nkv) * D}", lambda: ops.rope_qkv_backward_cast(dq, dk, dv, cos, sin, nq, nkv, D, S, one, amax, 1))
+        T, V = 8192, 128256  # Llama-3.2-3B: d(logits) of 8192 tokens
+        logits, labels = bf(T, V), torch.randint(0, V, (T,), device=dev, generator=g)
+        lse, loss, gs = torch.empty(T, device=dev), torch.empty(T, device=dev), torch.full((1,), 1.0 / T, device=dev)
+        st = torch.cuda.current_stream().cuda_stream
+        _mi_lib.check(lab.mi_ce_forward(logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), loss.data_ptr(), T, V, st), "mi_ce_forward")
+        y, yT = torch.empty((T, V), dtype=torch.uint8, device=dev), torch.empty((V, T), dtype=torch.uint8, device=dev)
+        ab(f"ce_bwd_cast {T}x{V}", lambda: _mi_lib.check(_mi_lib.load().mi_ce_backward_cast(
+            logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), gs.data_ptr(), y.data_ptr(), yT.data_ptr(), one.data_ptr(), amax.data_ptr(),
+            T, V, 1, st), "mi_ce_backward_cast"))
+        part = ops.amax_partial(dev, ops.amax_grid(8192, 3072))
+        x = bf(8192, 3072)
+        ab("amax_bf16 8192x3072", lambda: ops.amax_bf16(x, part))
+        aa = [r[3] for r in rows_out]
+        lo, hi = min(aa), max(aa)
+        print(f"castab A/A spread (base2/base over {len(aa)} rows): {lo:.4f} .. {hi:.4f}", flush=True)
+        for name, _, ratio, _ in rows_out:
+            if not lo <= ratio <= hi:
+                print(f"castab OUTSIDE the A/A spread: {name} cur/base {ratio:.4f}", flush=True)
     if "grouped" in args.which:  # a Linear's dgrad + wgrad: two launches vs mi_gemm_fp8_grouped, interleaved A/B
         models = {"3b": (8192, {"qkv": (5120, 3072), "o": (3072, 3072), "fc1": (16384, 3072), "fc2": (3072, 8192), "lm_head": (128256, 3072)}),
                   "1b": (8192, {"qkv": (3072, 2048), "o": (2048, 2048), "fc1": (16384, 2048), "fc2": (2048, 8192)}),
@@ -430,7 +499,7 @@ def main():
                 print(f"gridsweep grid {grid:3d} {m}x{n}x{k}: {len(d)} workgroups, {int(d[0, 2])} K-steps each, cycles/K-tile-step median {float(cyc.median()):7.1f} "
                       f"(min {float(cyc.min()):.0f} max {float(cyc.max()):.0f}), clock {float(clk.median()):6.0f} MHz", flush=True)
         os.environ.pop("MI_GEMM_GRID", None)
-    if "cast" in args.which:
+    if "cast" in args.which.split(","):  # (a whole word: "castab" and "rotcast" are modes of their own)
         for (R, C) in ((8192, 3072), (8192, 16384), (16384, 3072), (8192, 8192)):
             x = torch.randn((R, C), device=dev, dtype=torch.float32, generator=g).to(torch.bfloat16)
             amax = torch.zeros(1, device=dev)
