@@ -241,6 +241,16 @@ def e8m0_to_f32(e: np.ndarray) -> np.ndarray:
     return np.where(e == 0xFF, np.float32(np.nan), v)
 
 
+def mx_block_amax(v: np.ndarray) -> np.ndarray:
+    """max |v| over each block of MX_BLOCK consecutive elements of the LAST axis, float32 [..., C / 32], with fmaxf semantics: a
+    NaN element is ignored (an all-NaN block gives 0), +-inf gives inf.  np.max would propagate the NaN; the device does not
+    (mx_take_nans, mi_common.h)."""
+    v = np.asarray(v, dtype=np.float32)
+    assert v.shape[-1] % MX_BLOCK == 0
+    ab = np.abs(v.reshape(*v.shape[:-1], v.shape[-1] // MX_BLOCK, MX_BLOCK))
+    return np.where(np.isnan(ab), np.float32(0), ab).max(axis=-1).astype(np.float32)
+
+
 def mxfp8_quantize_rowwise(x_bf16_bits: np.ndarray, fmt: int = E4M3):
     """K7: one E8M0 scale per 32 consecutive elements of the LAST axis.
 
@@ -250,9 +260,7 @@ def mxfp8_quantize_rowwise(x_bf16_bits: np.ndarray, fmt: int = E4M3):
     r, c = x.shape
     assert c % MX_BLOCK == 0
     xb = x.reshape(r, c // MX_BLOCK, MX_BLOCK)
-    ab = np.abs(xb)
-    ab = np.where(np.isnan(ab), np.float32(0), ab)  # fmaxf semantics
-    amax_b = ab.max(axis=2).astype(np.float32)
+    amax_b = mx_block_amax(x)
     e = float_to_e8m0_roundup((amax_b * _MAX_NORM_RCP[fmt]).astype(np.float32))
     with np.errstate(over="ignore", invalid="ignore"):
         inv = np.ldexp(np.float32(1.0), 127 - e.astype(np.int64)).astype(np.float32)  # 2^(127-e), exact
@@ -347,22 +355,26 @@ def mxfp8_linear_fwd_bwd(x_bits, w_bits, dy_bits, bias_bits=None, fmt=E4M3):
 # --------------------------------------------------------------------------- fused elementwise neighbours (K10, RoPE)
 def swiglu_f32(h_bits: np.ndarray) -> np.ndarray:
     """act = silu(gate) * up in float32 from bf16 h = [gate | up] (te_llama.py:62, SURVEY App. A "SwiGLU")."""
-    h = bf16_bits_to_f32(h_bits).astype(np.float64)
+    with np.errstate(invalid="ignore"):  # widening a signalling NaN raises the flag
+        h = bf16_bits_to_f32(h_bits).astype(np.float64)
     f = h.shape[1] // 2
     g, u = h[:, :f], h[:, f:]
-    with np.errstate(over="ignore"):
+    # over: exp(-g) for g <= -710 and the float32 cast of a product above FLT_MAX; invalid: -inf / inf and inf * 0 (a NaN result is
+    # the IEEE answer there, not an accident)
+    with np.errstate(over="ignore", invalid="ignore"):
         return (g / (1.0 + np.exp(-g)) * u).astype(np.float32)
 
 
 def dswiglu_f32(h_bits: np.ndarray, dact_bits: np.ndarray) -> np.ndarray:
     """dh = [dact * dsilu(g) * u | dact * silu(g)] in float32."""
-    h = bf16_bits_to_f32(h_bits).astype(np.float64)
-    d = bf16_bits_to_f32(dact_bits).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        h = bf16_bits_to_f32(h_bits).astype(np.float64)
+        d = bf16_bits_to_f32(dact_bits).astype(np.float64)
     f = h.shape[1] // 2
     g, u = h[:, :f], h[:, f:]
-    with np.errstate(over="ignore"):
+    with np.errstate(over="ignore", invalid="ignore"):  # as swiglu_f32
         s = 1.0 / (1.0 + np.exp(-g))
-    return np.concatenate([d * u * (s * (1.0 + g * (1.0 - s))), d * (g * s)], axis=1).astype(np.float32)
+        return np.concatenate([d * u * (s * (1.0 + g * (1.0 - s))), d * (g * s)], axis=1).astype(np.float32)
 
 
 # Device-order float32 restatements of the fused front ends (SURVEY.md 8f rows 1-2; the kernels' arithmetic is
@@ -377,13 +389,16 @@ def swiglu_f32_device_order(h_bits: np.ndarray, bias_bits: np.ndarray = None) ->
     `bias_bits` (bf16 [2F]): the fused-bias form -- one float32 add per element on the unpacked gate / up values first."""
     h = bf16_bits_to_f32(h_bits)
     if bias_bits is not None:
-        h = (h + bf16_bits_to_f32(bias_bits)[None, :]).astype(np.float32)
+        with np.errstate(invalid="ignore"):  # a signalling NaN operand
+            h = (h + bf16_bits_to_f32(bias_bits)[None, :]).astype(np.float32)
     f = h.shape[1] // 2
     g, u = h[:, :f], h[:, f:]
     one = np.float32(1.0)
-    with np.errstate(over="ignore"):
+    # over: exp(-g) = inf for g <= -89 (sigmoid exactly 0) and products above FLT_MAX; invalid: inf * 0 (g = -inf, or g = +inf with
+    # u = 0) is NaN on the device too
+    with np.errstate(over="ignore", invalid="ignore"):
         sg = one / (one + np.exp(-g, dtype=np.float32))
-    return ((g * sg) * u).astype(np.float32)
+        return ((g * sg) * u).astype(np.float32)
 
 
 def dswiglu_f32_device_order(h_bits: np.ndarray, dact_bits: np.ndarray, bias_bits: np.ndarray = None) -> np.ndarray:
@@ -391,16 +406,17 @@ def dswiglu_f32_device_order(h_bits: np.ndarray, dact_bits: np.ndarray, bias_bit
     `bias_bits`: as swiglu_f32_device_order."""
     h = bf16_bits_to_f32(h_bits)
     if bias_bits is not None:
-        h = (h + bf16_bits_to_f32(bias_bits)[None, :]).astype(np.float32)
+        with np.errstate(invalid="ignore"):
+            h = (h + bf16_bits_to_f32(bias_bits)[None, :]).astype(np.float32)
     d = bf16_bits_to_f32(dact_bits)
     f = h.shape[1] // 2
     g, u = h[:, :f], h[:, f:]
     one = np.float32(1.0)
-    with np.errstate(over="ignore"):
+    with np.errstate(over="ignore", invalid="ignore"):  # as swiglu_f32_device_order; g = +inf: inf * (1 - 1) is NaN inside dsilu
         sg = one / (one + np.exp(-g, dtype=np.float32))
-    left = (d * u) * (sg * (one + g * (one - sg)))
-    right = d * (g * sg)
-    return np.concatenate([left, right], axis=1).astype(np.float32)
+        left = (d * u) * (sg * (one + g * (one - sg)))
+        right = d * (g * sg)
+        return np.concatenate([left, right], axis=1).astype(np.float32)
 
 
 def rmsnorm_sumsq_device_order(x_bits: np.ndarray) -> np.ndarray:
@@ -440,12 +456,27 @@ def norm_apply_f32_device_order(x_bits: np.ndarray, rstd_f32: np.ndarray, gamma_
     return ((x * rstd_f32.astype(np.float32)[:, None]).astype(np.float32) * g[None, :]).astype(np.float32)
 
 
-def fp8_mismatches_near_boundary(got_bytes: np.ndarray, v_scaled_f32: np.ndarray, fmt: int, rel: float = 2.0 ** -17, abs_slack=None):
+def exp_arg_rel_band(g_f32: np.ndarray) -> np.ndarray:
+    """Relative width, per element, of the band around an FP8 rounding boundary inside which a value built on sigmoid(g) may land
+    on either side on the device: max(2^-17, 2 |g| log2(e) 2^-24).  2^-17 is the band of fp8_mismatches_near_boundary (a few
+    float32 ulps of v_exp_f32 / numpy's exp).  The second term: the device evaluates exp(-g) as v_exp_f32(-g * log2 e) with the
+    product ROUNDED to float32, an absolute error of up to |g| log2(e) 2^-24 in a base-2 exponent, i.e. up to
+    ln 2 * |g| log2(e) 2^-24 < |g| log2(e) 2^-24 relative in the exponential (and so in sigmoid(g) = 1 / (1 + exp(-g)) wherever exp(-g)
+    dominates the 1, g << 0); the factor 2 covers the rounding of the constant log2 e and numpy's own exp.  It exceeds 2^-17 only
+    for |g| > 44.4.  A non-finite g gets the plain band (such positions are held to identity, not to a band)."""
+    with np.errstate(invalid="ignore"):
+        g = np.abs(np.asarray(g_f32, dtype=np.float32)).astype(np.float64)
+    g = np.where(np.isfinite(g), g, 0.0)
+    return np.maximum(2.0 ** -17, 2.0 * g * np.log2(np.e) * 2.0 ** -24)
+
+
+def fp8_mismatches_near_boundary(got_bytes: np.ndarray, v_scaled_f32: np.ndarray, fmt: int, rel=2.0 ** -17, abs_slack=None):
     """For FP8 bytes produced from a float32 value that may differ from `v_scaled_f32` by a few ulps: returns
     (n_mismatch, n_unexplained) where a mismatch is EXPLAINED when the two codes are neighbours and `v_scaled_f32` lies within
     `rel` (relative) of the rounding boundary between them (the midpoint of the two FP8 values; the saturation edge counts).
     `abs_slack` (same shape as the value, optional): additional absolute distance allowed per element, for expressions with
-    a cancellation (dsilu has a zero near g = -1.2785: there the error is a few ulps of the TERMS, not of the tiny result)."""
+    a cancellation (dsilu has a zero near g = -1.2785: there the error is a few ulps of the TERMS, not of the tiny result).
+    `rel` may be an array of the value's shape (exp_arg_rel_band)."""
     want = fp8_encode_sat(v_scaled_f32.astype(np.float32), fmt)
     got = np.asarray(got_bytes)
     both_zero = ((got & 0x7F) == 0) & ((want & 0x7F) == 0)
@@ -459,7 +490,9 @@ def fp8_mismatches_near_boundary(got_bytes: np.ndarray, v_scaled_f32: np.ndarray
     same_sign = ((got[mism] ^ want[mism]) & 0x80) == 0
     mid = 0.5 * (gv + wv)
     slack = 0.0 if abs_slack is None else np.asarray(abs_slack, dtype=np.float64)[mism]
-    near = np.abs(v - mid) <= rel * np.maximum(np.abs(mid), 1e-30) + slack
+    rel = rel if np.ndim(rel) == 0 else np.broadcast_to(np.asarray(rel, dtype=np.float64), got.shape)[mism]
+    with np.errstate(invalid="ignore"):  # a non-finite value (inf - inf below) is never "near"
+        near = np.abs(v - mid) <= rel * np.maximum(np.abs(mid), 1e-30) + slack
     explained = neighbours & same_sign & near & np.isfinite(mid)
     return int(mism.sum()), int((~explained).sum())
 

@@ -228,3 +228,167 @@ def test_attention_oracle_against_torch_float64_autograd(B, S, H, G, D, causal):
     dk_shift = (ds_shift.transpose(-1, -2) @ qr.detach()).reshape(B, G, H // G, S, D).sum(2)
     close(dk2 - dk, dk_shift.transpose(1, 2).numpy(), "dk shift from the stored O")
     assert np.array_equal(dv2, dv)
+
+
+# ----------------------------------------------------------------------------------------- edge semantics of the fused casts
+# (the kernels are held to these on the GPU in tests/test_fused_cast_edges_gpu.py)
+_KAT_GATES = [np.nan, np.inf, -np.inf, 17, 30, 88, 89, 100, 3e38, -17, -30, -88, -88.5, -89, -100, -3e38, -0.0, 0.0]
+_KAT_UPS = [1, 0, -1, np.nan, np.inf, -np.inf, 3e38]
+
+
+def _kat_h():
+    """h bits [18, 14]: gate i in every column of row i, up j in column 7 + j; plus the gates and ups as bf16-rounded float32"""
+    g = O.round_to_bf16(np.array(_KAT_GATES, np.float32))
+    u = O.round_to_bf16(np.array(_KAT_UPS, np.float32))
+    h = np.concatenate([np.repeat(g[:, None], len(u), 1), np.repeat(u[None, :], len(g), 0)], axis=1)
+    return O.f32_to_bf16_bits(h), g, u
+
+
+def test_swiglu_restatements_known_answers_at_the_edges():
+    """What silu(g) * u is at the edges follows from the restatement ((g * (1 / (1 + exp(-g)))) * u, every operation float32) and
+    IEEE arithmetic alone; nothing here comes from a device.  Scale 16, both formats."""
+    import warnings
+    h_bits, g, u = _kat_h()
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        v = O.swiglu_f32_device_order(h_bits)
+        v64 = O.swiglu_f32(h_bits)
+    mx = {O.E4M3: 0x7E, O.E5M2: 0x7B}
+    with np.errstate(over="ignore", invalid="ignore"):
+        vs = (v * np.float32(16.0)).astype(np.float32)
+    G, Uu = np.meshgrid(g, u, indexing="ij")
+    with np.errstate(over="ignore", invalid="ignore"):
+        gu = (G * Uu).astype(np.float32)
+    fin_g = np.isfinite(G)
+    for fmt in (O.E4M3, O.E5M2):
+        b = O.fp8_encode_sat(vs, fmt)
+        row = lambda x: _KAT_GATES.index(x) if not np.isnan(x) else 0
+        col = lambda x: 3 if np.isnan(x) else _KAT_UPS.index(x)
+        assert (b[np.isnan(G) | np.isnan(Uu)] == 0x7F).all()                      # NaN in gate or up
+        assert b[row(np.inf), col(1)] == mx[fmt]                                  # +Inf * 1 (sigmoid 1)
+        assert b[row(np.inf), col(0)] == 0x7F                                     # Inf * 0
+        assert b[row(np.inf), col(-1)] == mx[fmt] | 0x80
+        assert (b[row(-np.inf)] == 0x7F).all()                                    # -Inf * sigmoid(-Inf) = -Inf * 0
+        # up = +-Inf under a finite gate that does not vanish in the product: +- max code, the sign of g * u
+        for gi in (17, 30, 88, 89, 100, 3e38, -17, -30, -88, -88.5):
+            sgn = 0x80 if gi < 0 else 0
+            assert b[row(gi), col(np.inf)] == mx[fmt] | sgn and b[row(gi), col(-np.inf)] == mx[fmt] | (sgn ^ 0x80)
+        assert b[row(3e38), col(1)] == mx[fmt]                                    # 3e38 * 16 overflows float32: + max code
+        assert b[row(3e38), col(3e38)] == mx[fmt]
+    # g >= 17: 1 + exp(-g) rounds to 1, the sigmoid is exactly 1 and silu(g) * u == g * u, bit for bit
+    big = fin_g & (G >= 17)
+    np.testing.assert_array_equal(v[big].view(np.uint32), gu[big].view(np.uint32))
+    # g <= -89: exp(-g) overflows float32, the sigmoid is exactly 0 and g * 0 = -0.0; times u > 0: -0.0 (byte 0x80)
+    for gi in (-89, -100, -3e38):
+        r = _KAT_GATES.index(gi)
+        assert v[r, 0] == 0 and np.signbit(v[r, 0]) and v[r, 6] == 0 and np.signbit(v[r, 6])      # u = 1, 3e38
+        assert v[r, 2] == 0 and not np.signbit(v[r, 2])                                           # u = -1: +0.0
+        assert np.isnan(v[r, 4]) and np.isnan(v[r, 5])                                            # -0.0 * +-Inf
+        assert O.fp8_encode_sat(vs[r, :1], O.E4M3)[0] == 0x80 and O.fp8_encode_sat(vs[r, :1], O.E5M2)[0] == 0x80
+    # -88.5: exp(88.5) is still finite, the sigmoid a float32 subnormal, the product a tiny negative number -- not flushed
+    r = _KAT_GATES.index(-88.5)
+    assert v[r, 0] < 0 and abs(v[r, 0] / v64[r, 0] - 1) < 1e-5
+    # signed zero gates: sigmoid 1/2, the zero keeps its sign through both products
+    rz, rp = _KAT_GATES.index(0.0), len(g) - 1
+    assert np.signbit(g[rz]) and not np.signbit(g[rp])
+    assert np.signbit(v[rz, 0]) and not np.signbit(v[rz, 2]) and not np.signbit(v[rp, 0]) and np.signbit(v[rp, 2])
+    assert (v[[rz, rp]][:, [0, 1, 2, 6]] == 0).all() and np.isnan(v[[rz, rp]][:, [3, 4, 5]]).all()
+    # the amax of such values: NaN ignored, Inf gives Inf
+    assert O.amax_f32(v) == np.inf
+    assert O.amax_f32(v[_KAT_GATES.index(30)][[0, 1, 2, 3]]) == np.float32(30.0)   # {30, 0, -30, NaN}
+    assert O.amax_f32(np.array([np.nan, -3.0, 2.0], np.float32)) == np.float32(3.0)
+    assert O.amax_f32(np.array([np.nan, np.nan], np.float32)) == 0
+    # the float64 form agrees wherever both are finite and non-zero
+    both = np.isfinite(v) & np.isfinite(v64) & (v != 0) & (v64 != 0)
+    np.testing.assert_allclose(v[both], v64[both], rtol=1e-5)
+
+
+def test_dswiglu_restatements_known_answers_at_the_edges():
+    import warnings
+    h_bits, g, u = _kat_h()
+    d = O.round_to_bf16(np.array([0.5, -2.0, 0.5, -2.0, 0.5, -2.0, 0.5], np.float32))
+    d_bits = O.f32_to_bf16_bits(np.repeat(d[None, :], len(g), 0))
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        v = O.dswiglu_f32_device_order(h_bits, d_bits)
+        v64 = O.dswiglu_f32(h_bits, d_bits)
+    F = len(u)
+    left, right = v[:, :F], v[:, F:]
+    G, Uu = np.meshgrid(g, u, indexing="ij")
+    D = np.repeat(d[None, :], len(g), 0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        du, dg = (D * Uu).astype(np.float32), (D * G).astype(np.float32)
+    big = np.isfinite(G) & (G >= 17)
+    # g >= 17: sigmoid exactly 1, dsilu = 1 * (1 + g * 0) = 1: the gate half is d * u, the up half d * g, bit for bit (NaN as NaN)
+    ok = big & ~np.isnan(du)
+    np.testing.assert_array_equal(left[ok].view(np.uint32), du[ok].view(np.uint32))
+    assert np.isnan(left[big & np.isnan(du)]).all()
+    np.testing.assert_array_equal(right[big].view(np.uint32), dg[big].view(np.uint32))
+    r = _KAT_GATES.index(np.inf)
+    assert np.isnan(left[r]).all()                        # g = +Inf: Inf * (1 - 1) inside dsilu
+    assert (right[r] == np.inf * d).all()                 # d * (Inf * 1)
+    r = _KAT_GATES.index(-np.inf)
+    assert np.isnan(v[r]).all()                           # 0 * -Inf on both sides
+    for gi in (-89, -100, -3e38):                         # sigmoid exactly 0: both halves are signed zeros (NaN under u = +-Inf / NaN)
+        r = _KAT_GATES.index(gi)
+        fin = np.isfinite(u)
+        assert (left[r, fin] == 0).all() and np.isnan(left[r, ~fin]).all() and (right[r] == 0).all()
+        assert (np.signbit(right[r]) == (d > 0)).all()    # d * (g * 0) = d * -0.0
+    both = np.isfinite(v) & np.isfinite(v64) & (v != 0) & (v64 != 0)
+    np.testing.assert_allclose(v[both], v64[both], rtol=2e-5)
+
+
+def test_mx_block_amax_ignores_nan_and_keeps_inf():
+    v = np.zeros((2, 64), np.float32)
+    v[0, :32] = [np.nan, -5.0] + [1.0] * 30
+    v[0, 32:] = np.nan
+    v[1, :32] = [np.nan, -np.inf] + [3.0] * 30
+    v[1, 40] = -0.25
+    np.testing.assert_array_equal(O.mx_block_amax(v), np.array([[5.0, 0.0], [np.inf, 0.25]], np.float32))
+    assert list(O.float_to_e8m0_roundup(O.mx_block_amax(v)[1] / np.float32(448.0))) == [0xFE, 117]   # 0.25 / 448 = 1.14 * 2^-11 -> 2^-10
+    # the quantiser uses it: a NaN keeps its 0x7F byte and does not touch the block's scale
+    x = O.f32_to_bf16_bits(np.array([[np.nan, 448.0] + [1.0] * 30], np.float32))
+    q, e = O.mxfp8_quantize_rowwise(x)
+    assert e[0, 0] == 127 and q[0, 0] == 0x7F and q[0, 1] == 0x7E and q[0, 2] == 0x38
+
+
+@pytest.mark.parametrize("backward", [False, True])
+def test_fused_cast_edge_sweeps_run_clean_and_stay_under_the_mismatch_cap(backward):
+    """The inputs of tests/test_fused_cast_edges_gpu.py, evaluated by the oracle alone:
+      * all four SwiGLU restatements run without a numpy warning on every bf16 pattern (warnings are errors here);
+      * the number of reference values that lie INSIDE their rounding-boundary band -- where the device may legitimately produce the
+        neighbouring code -- stays below the cap the GPU test puts on explained mismatches, max(2, 1e-3 size); the same for the
+        MX block scales against max(2, 1e-4 blocks).  Were it not so, the tables in tests/util.py would have to change, not the cap."""
+    import warnings
+    from tests import util as U
+    scale = U.DSWIGLU_SCALE if backward else U.SWIGLU_SCALE
+    worst = worst_mx = 0
+    for assign in (0, 1):
+        for bias_kind in ("none", "bias", "nan"):
+            for kind in U.SWEEP_KINDS:
+                h, d = U.gate_sweep(kind, assign)
+                b = U.sweep_bias(bias_kind, assign)
+                with warnings.catch_warnings():
+                    warnings.simplefilter("error")
+                    v32, fixed, rel, slack = U.swiglu_sweep_reference(h, d, b, backward, scale)
+                    if bias_kind == "none":
+                        v64 = O.dswiglu_f32(h, d) if backward else O.swiglu_f32(h)
+                with np.errstate(invalid="ignore"):
+                    both = np.isfinite(v32) & np.isfinite(v64) & (np.abs(v64) > 1e-30) if bias_kind == "none" else None
+                if both is not None:   # the two restatements are the same function on the whole sweep (dsilu: away from its zero)
+                    err = np.abs(v32[both].astype(np.float64) - v64[both]) / np.abs(v64[both])
+                    assert np.quantile(err, 0.999) < 1e-5
+                assert (O.amax_f32(v32) == np.inf) == (kind != "bounded")
+                with np.errstate(over="ignore", invalid="ignore"):
+                    vs = (v32 * scale).astype(np.float32)
+                for fmt in (O.E4M3, O.E5M2):
+                    n = int((U.fp8_in_boundary_band(vs, fmt, rel, slack) & ~fixed).sum())
+                    worst = max(worst, n)
+                    assert n <= max(2, 1e-3 * v32.size), f"{n} reference values inside their band ({assign}, {bias_kind}, {kind}, fmt {fmt})"
+                if bias_kind == "none" and kind != "finite":   # the MX twins take no bias and run the full and the bounded sweep
+                    v1, fixed1, rel1, _ = U.swiglu_sweep_reference(h, d, None, backward, np.float32(1.0))
+                    for fmt in (O.E4M3, O.E5M2):
+                        n = U.mx_scales_in_band(v1, fixed1, rel1, fmt)
+                        worst_mx = max(worst_mx, n)
+                        assert n <= 2, f"{n} MX block scales inside their band ({assign}, {kind}, fmt {fmt})"
+    print("most reference values inside a band:", worst, "block scales:", worst_mx)

@@ -36,6 +36,130 @@ def rand_fp8(shape, fmt, seed, spread=1.0):
     return O.fp8_encode_sat(v, fmt)
 
 
+# ---- inputs and criteria of the exhaustive edge sweeps of the fused FP8 casts (tests/test_fused_cast_edges_gpu.py runs the kernels
+# on them; tests/test_oracle.py counts, on the CPU, how many reference values lie inside their rounding-boundary band) ----
+# per-column tables, all bf16-exact: both signs, both zeros, a value near 1, small ones and a large one.  At the forward's scale 16
+# E4M3 saturates from |silu(g) u| = 28 (g = 28 under u = 1, g = 0.6 under u = 96), E5M2 from 3584 (g = 37.3 under u = 96).
+UP_TABLE = np.array([1.0, -0.0, -1.0078125, 0.01171875, 96.0, 0.0, -0.00244140625, 0.75], np.float32)
+# (dact: powers of two, so that d * u * dsilu(g) keeps u's short significand where dsilu(g) is EXACTLY 1/2 -- the ~26000 gates below
+# 2^-25 -- and does not sit exactly on an FP8 rounding boundary there: with -3 or 100 in this table thousands of reference values did)
+DACT_TABLE = np.array([0.125, -0.25, 1.0, 0.0, -2.0, 2.0 ** -10, 128.0, -0.0], np.float32)
+BIAS_TABLE = np.array([0.0, -1.5, 0.3125, 2.0], np.float32)   # a zero, a negative, a fractional entry
+SWEEP_KINDS = ("full", "finite", "bounded")
+SWIGLU_SCALE, DSWIGLU_SCALE = np.float32(16.0), np.float32(64.0)   # the scales of the benign-data tests
+
+
+def all_bf16_bits(kind: str = "full") -> np.ndarray:
+    """[256, 256] uint16: pattern r * 256 + c.  "finite": patterns with an all-ones exponent (Inf, NaN) replaced by 0.  "bounded":
+    also those of magnitude >= 2^64, so that no product with the tables above leaves float32 (under "finite" alone 3.4e38 * 96
+    overflows and the amax is Inf again)."""
+    bits = np.arange(65536, dtype=np.uint32).astype(np.uint16).reshape(256, 256)
+    exp = (bits >> 7) & 0xFF
+    if kind != "full":
+        bits = np.where(exp == 0xFF, 0, bits).astype(np.uint16)
+    if kind == "bounded":
+        bits = np.where(exp >= 127 + 64, 0, bits).astype(np.uint16)
+    return bits
+
+
+def gate_sweep(kind: str, assign: int):
+    """(h bits [256, 512], dact bits [256, 256]): every bf16 pattern as a gate, up and dact from the tables by column.  The two
+    assignments pair every gate value with different up / dact entries (0: up cycles inside a lane's 8 columns, dact changes every
+    8; 1: the other way round, shifted)."""
+    c = np.arange(256)
+    ui, di = ((c % 8, (c // 8) % 8), ((c // 8 + 3) % 8, (c + 5) % 8))[assign]
+    up = np.broadcast_to(O.f32_to_bf16_bits(UP_TABLE[ui])[None, :], (256, 256))
+    dact = np.ascontiguousarray(np.broadcast_to(O.f32_to_bf16_bits(DACT_TABLE[di])[None, :], (256, 256)))
+    return np.ascontiguousarray(np.concatenate([all_bf16_bits(kind), up], axis=1)), dact
+
+
+def sweep_bias(bias_kind: str, assign: int):
+    """fc1 bias bits [512] for the sweeps: None ("none"), the table by column ("bias"), or the table with ONE NaN entry ("nan":
+    in the gate half for assignment 0, in the up half for assignment 1)."""
+    if bias_kind == "none":
+        return None
+    c = np.arange(512)
+    b = BIAS_TABLE[(c + c // 4 + assign) % 4].copy()
+    if bias_kind == "nan":
+        b[37 + 256 * assign] = np.nan
+    return O.f32_to_bf16_bits(b)
+
+
+def swiglu_sweep_reference(h_bits, dact_bits, bias_bits, backward: bool, scale):
+    """The float32 restatement of a sweep and what the criteria need beside it: (v32, fixed, rel, abs_slack).
+    fixed: positions IEEE arithmetic decides -- the restatement is NaN, +-Inf or an exact zero, the sigmoid is exactly 1
+           (g >= 17: 1 + exp(-g) rounds to 1, the value is g * u, resp. d * u | d * g) or exactly 1/2 (|g| <= 2^-26: exp(-g) is
+           within an ulp of 1 whatever computes it, 1 + exp(-g) rounds to 2 -- ties go to even -- and the value is (g / 2) * u, resp.
+           (d * u) / 2 | d * (g / 2); a third of all bf16 patterns): identity is required there, sign of a zero included;
+    rel:   O.exp_arg_rel_band of the (biased) gate, per element;
+    abs_slack: the dsilu cancellation slack of test_dswiglu_cast_vs_oracle for the gate half of the backward, 2^-21 |d u| scale,
+           TIMES min(1, sigmoid(g) max(1, |g|)): never more than the existing slack, and equal to it around the zero of dsilu at
+           g = -1.2785 for which it was made.  dsilu = sg * t with t = 1 + g (1 - sg): the rounding errors of t's terms are a few
+           float32 ulps of max(1, |g|), and they reach the result multiplied by sg -- for g << 0 that is nothing, whereas the
+           unscaled slack there is thousands of times the value itself and puts every gate below -12 "inside a band" (more
+           reference values than the mismatch cap allows under E5M2, whatever the tables).  None for the forward."""
+    hf = O.bf16_bits_to_f32(h_bits)
+    if bias_bits is not None:
+        with np.errstate(invalid="ignore"):
+            hf = (hf + O.bf16_bits_to_f32(bias_bits)[None, :]).astype(np.float32)
+    F = hf.shape[1] // 2
+    g, u = hf[:, :F], hf[:, F:]
+    rel = O.exp_arg_rel_band(g)
+    with np.errstate(invalid="ignore"):
+        exact_sigmoid = (g >= np.float32(17.0)) | (np.abs(g) <= np.float32(2.0 ** -26))
+    if not backward:
+        v32, slack = O.swiglu_f32_device_order(h_bits, bias_bits), None
+    else:
+        v32 = O.dswiglu_f32_device_order(h_bits, dact_bits, bias_bits)
+        df = O.bf16_bits_to_f32(dact_bits)
+        with np.errstate(over="ignore", invalid="ignore"):
+            g64 = g.astype(np.float64)
+            sg = 1.0 / (1.0 + np.exp(-g64))
+            s = np.abs(df * u) * np.float32(scale) * np.float32(2.0 ** -21) * np.minimum(1.0, sg * np.maximum(1.0, np.abs(g64)))
+        slack = np.concatenate([np.where(np.isfinite(s), s, 0.0), np.zeros_like(df)], axis=1)
+        rel, exact_sigmoid = np.concatenate([rel, rel], axis=1), np.concatenate([exact_sigmoid, exact_sigmoid], axis=1)
+    fixed = ~np.isfinite(v32) | (v32 == 0) | exact_sigmoid
+    return v32, fixed, rel, slack
+
+
+def fp8_in_boundary_band(v_scaled_f32, fmt: int, rel, abs_slack=None) -> np.ndarray:
+    """Mask: the value lies within `rel` (relative, + abs_slack) of the midpoint between its own FP8 code and a neighbouring one,
+    i.e. an evaluation a few float32 ulps away may round to the other code (the saturation edge is no boundary: both sides clamp)."""
+    v = np.asarray(v_scaled_f32, dtype=np.float32)
+    code = O.fp8_encode_sat(v, fmt).astype(np.int16)
+    tab = O.fp8_decode_table(fmt).astype(np.float64)
+    top = int(O.fp8_encode_sat(np.array([np.inf], np.float32), fmt)[0])
+    mag = code & 0x7F
+    a = np.abs(v.astype(np.float64))
+    slack = 0.0 if abs_slack is None else np.asarray(abs_slack, dtype=np.float64)
+    out = np.zeros(v.shape, dtype=bool)
+    for step in (-1, 1):
+        nb = mag + step
+        ok = (nb >= 0) & (nb <= top) & (mag <= top)
+        mid = 0.5 * (tab[np.clip(mag, 0, top)] + tab[np.clip(nb, 0, top)])
+        with np.errstate(invalid="ignore"):
+            out |= ok & (np.abs(a - mid) <= rel * np.maximum(mid, 1e-30) + slack)
+    return out & np.isfinite(v)
+
+
+def mx_scales_in_band(v32, fixed, rel, fmt: int) -> int:
+    """How many MX blocks (row-wise and column-wise together) have amax / fp8_max within `rel` of a power of two, so that a device
+    value a few ulps away may round the E8M0 scale the other way; blocks whose amax element is `fixed` (IEEE-exact) do not count."""
+    n = 0
+    for mat, fx, rl in ((v32, fixed, rel), (np.ascontiguousarray(v32.T), np.ascontiguousarray(fixed.T), np.ascontiguousarray(rel.T))):
+        r, c = mat.shape
+        ab = np.abs(mat.reshape(r, c // 32, 32))
+        arg = np.where(np.isnan(ab), np.float32(-1), ab).argmax(-1)[..., None]
+        fx_b = np.take_along_axis(fx.reshape(r, c // 32, 32), arg, -1)[..., 0]
+        rl_b = np.take_along_axis(rl.reshape(r, c // 32, 32), arg, -1)[..., 0]
+        with np.errstate(over="ignore"):
+            v = (O.mx_block_amax(mat) * O._MAX_NORM_RCP[fmt]).astype(np.float64)
+        live = np.isfinite(v) & (v > 0) & ~fx_b
+        p2 = np.exp2(np.round(np.log2(np.where(live, v, 1.0))))
+        n += int((live & (np.abs(v / p2 - 1.0) <= rl_b)).sum())
+    return n
+
+
 def assert_mfma_close(got, ref, a8, b8, fa, fb, alpha):
     """fp32-output bound from the measured MFMA accumulation behaviour (tools/probe_mfma.hip): inside one
     128-deep instruction, products are added in groups of 8 aligned to the group's largest product and
