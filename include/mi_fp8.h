@@ -67,9 +67,11 @@ extern "C" {
  *   1  mi_adamw_f32_multi (fp32 master weights and moments in the fused AdamW + FP8 cast pass), mi_abi_revision
  *   2  mi_amax_bf16, mi_amax_norm, mi_amax_swiglu, mi_amax_dswiglu, mi_current_scale (Float8CurrentScaling: the amax of a tensor
  *      before its cast, and the scale from it)
+ *   3  mi_blockfp8_quantize_ex, mi_blockfp8_norm_quantize, mi_blockfp8_swiglu_quantize, mi_blockfp8_dswiglu_quantize
+ *      (Float8BlockScaling: 1 x 128 and 128 x 128 power-of-two block scales in the MX operand layout)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 2
+#define MI_ABI_REVISION 3
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -239,6 +241,33 @@ int mi_mxfp8_dswiglu_quantize(const void* h_bf16, const void* dact_bf16, void* y
 int mi_mxfp8_rope_bwd_quantize(const void* dq_bf16, const void* dk_bf16, const void* dv_bf16, const float* cos_tab,
                                const float* sin_tab, void* y_row, void* s_row, void* y_colT, void* s_colT, int64_t rows,
                                int64_t seq, int n_q_heads, int n_kv_heads, int head_dim, int fmt, void* stream);
+
+/*
+ * Float8BlockScaling quantise (revision 3): the K7 kernel with one POWER-OF-TWO scale per 1 x 128 block along the contraction
+ * axis (block_dim 1: 128 consecutive elements of a row for the row-wise copy, of a column for the column-wise one) or per
+ * 128 x 128 block (block_dim 2: both copies share the block's scale, so y_colT is the byte transpose of y_row).  Per block B of
+ * the fp32 values v the cast sees:
+ *     amax  = max |v|                        (fmaxf semantics: a NaN element is ignored, Inf gives Inf)
+ *     a     = max(amax, amax_epsilon)
+ *     scale = 1 if a is 0 or Inf, else fp8_max / a (IEEE fp32; Inf -> FLT_MAX) with the mantissa cleared   (mi_current_scale, pow2)
+ *     y     = sat_cast(v * scale)            (NaN -> the NaN byte, +-Inf and over-range -> +-max)
+ *     byte  = 254 - biased_exponent(scale)   (E8M0 of 1 / scale, exactly; 0..247)
+ * Outputs in the layout of mi_mxfp8_quantize(_ex), the block's byte stored at EVERY 32-group position the block covers, so that
+ * mi_gemm_mxfp8 / mi_gemm_mxfp8_grouped take these operands unchanged.  rows, cols multiples of 32; a trailing block shorter than
+ * 128 is a block over the elements that exist.  Blocks start at the tensor's first row and column: with block_dim 2 a row-block
+ * destination (ld_rows > rows) must start on a multiple of 128 rows of its operand (the operand's buffers 128-byte aligned).
+ * The argument lists are those of the mi_mxfp8_* counterparts plus (block_dim, amax_epsilon >= 0) in front of the stream.
+ */
+int mi_blockfp8_quantize_ex(const void* x_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT, float* colsum,
+                            int64_t rows, int64_t cols, int64_t ld_rows, int fmt, int block_dim, float amax_epsilon, void* stream);
+int mi_blockfp8_norm_quantize(const void* x_bf16, const float* rstd, const void* gamma_bf16, void* y_row, void* s_row,
+                              void* y_colT, void* s_colT, int64_t rows, int64_t cols, int fmt, int block_dim, float amax_epsilon,
+                              void* stream);
+int mi_blockfp8_swiglu_quantize(const void* h_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT, int64_t rows,
+                                int64_t F, int fmt, int block_dim, float amax_epsilon, void* stream);
+int mi_blockfp8_dswiglu_quantize(const void* h_bf16, const void* dact_bf16, void* y_row, void* s_row, void* y_colT,
+                                 void* s_colT, float* colsum, int64_t rows, int64_t F, int fmt, int block_dim, float amax_epsilon,
+                                 void* stream);
 
 /*
  * K8  block-scaled MXFP8 GEMM (v_mfma_scale_f32_16x16x128_f8f6f4 with per-32 E8M0 scales)

@@ -30,6 +30,9 @@ class Recipe:
     def current(self) -> bool:
         return isinstance(self, Float8CurrentScaling)
 
+    def block(self) -> bool:
+        return isinstance(self, Float8BlockScaling)
+
 
 @dataclass(frozen=True)
 class DelayedScaling(Recipe):
@@ -105,6 +108,46 @@ class Float8CurrentScaling(Recipe):
         for q in (self.fp8_quant_fwd_inp, self.fp8_quant_fwd_weight, self.fp8_quant_bwd_grad):
             if not (q.amax_epsilon >= 0.0):
                 raise ValueError("amax_epsilon must be non-negative")
+
+
+@dataclass(frozen=True)
+class Float8BlockScaling(Recipe):
+    """Block scaling with power-of-two scales, no history (the DeepSeek-V3 style recipe): one scale per 1 x 128 block along the
+    contraction axis for activations and gradients (scaling dim 1), one per 128 x 128 block for weights (scaling dim 2).
+    Field names and defaults are those of TE's Float8BlockScaling as far as its public definition is known here; TE itself is not
+    available to compare against, so parity with it is unpinned, as for the other recipes.
+    Only power-of-two scales: the gfx950 scaled MFMA applies E8M0 (power-of-two) scales, which a power-of-two scale inverse is
+    exactly; fp32 block scales would need a different GEMM main loop."""
+    fp8_format: Format = Format.E4M3
+    fp8_quant_fwd_inp: QParams = QParams(power_2_scale=True, amax_epsilon=0.0)
+    fp8_quant_fwd_weight: QParams = QParams(power_2_scale=True, amax_epsilon=0.0)
+    fp8_quant_bwd_grad: QParams = QParams(power_2_scale=True, amax_epsilon=0.0)
+    x_block_scaling_dim: int = 1
+    w_block_scaling_dim: int = 2
+    grad_block_scaling_dim: int = 1
+    fp8_gemm_fprop: MMParams = MMParams(use_split_accumulator=True)
+    fp8_gemm_dgrad: MMParams = MMParams(use_split_accumulator=True)
+    fp8_gemm_wgrad: MMParams = MMParams(use_split_accumulator=True)
+    fp8_dpa: bool = False
+    fp8_mha: bool = False
+
+    def __post_init__(self):
+        if self.fp8_format not in (Format.E4M3, Format.E5M2, Format.HYBRID):
+            raise ValueError("fp8_format must be Format.E4M3, Format.E5M2 or Format.HYBRID")
+        x, w, g = self.x_block_scaling_dim, self.w_block_scaling_dim, self.grad_block_scaling_dim
+        for name, d in (("x_block_scaling_dim", x), ("w_block_scaling_dim", w), ("grad_block_scaling_dim", g)):
+            if d not in (1, 2):
+                raise ValueError(f"{name} must be 1 (1x128 blocks) or 2 (128x128 blocks), got {d!r}")
+        if x == 2 and w == 2:
+            raise ValueError("2D by 2D block scaling is not supported: x_block_scaling_dim and w_block_scaling_dim cannot both be 2")
+        if w == 2 and g == 2:
+            raise ValueError("2D by 2D block scaling is not supported: w_block_scaling_dim and grad_block_scaling_dim cannot both be 2")
+        for q in (self.fp8_quant_fwd_inp, self.fp8_quant_fwd_weight, self.fp8_quant_bwd_grad):
+            if not (q.amax_epsilon >= 0.0):
+                raise ValueError("amax_epsilon must be non-negative")
+            if not q.power_2_scale:
+                raise ValueError("Float8BlockScaling needs power_2_scale=True: the gfx950 scaled MFMA applies E8M0 (power-of-two) "
+                                 "block scales; fp32 block scales would need a different GEMM main loop")
 
 
 def fmt_codes(fmt: Format) -> Tuple[int, int]:

@@ -9,6 +9,10 @@
 // 32-element block spans 4 neighbouring lanes, reduced with two DPP shuffles.
 // Replaces TE's MXFP8 quantise under MXFP8BlockScaling(fp8_format=E4M3)
 // (te_llama_mxfp8.py:28-29,86,93; SURVEY.md 2.3 K7, Appendix A "MXFP8").
+// The same kernel quantises for Float8BlockScaling (template parameter GRAN below): one power-of-two scale per 1 x 128 or 128 x 128
+// block, whose inverse is stored as an E8M0 byte at every 32-block position the block covers -- the layout above, so the MX GEMMs
+// read such operands unchanged (mi_blockfp8_* at the end of this file).
+#include <float.h>
 #include "mi_common.h"
 
 namespace mi {
@@ -22,14 +26,39 @@ namespace mi {
 //      colsum[tile_r, c] = per-128-row column sums (fc1 bias gradient, fixed order)
 __device__ __forceinline__ float mx_sigmoid(float g) { return 1.0f / (1.0f + __expf(-g)); }
 
-template <int FMT, bool ROWWISE, bool COLWISE, int PRE>
+// GRAN selects the scaling granularity of the quantise stage; the value block, the producers, the column sums and the NaN handling
+// above it are the same code for all three:
+//   0  MX: one E8M0 scale per 32 elements (mx_quant_rows / mx_quant_cols, mi_common.h)
+//   1  Float8BlockScaling, scaling dim 1: one power-of-two scale per 1 x 128 block along the contraction axis -- a row's 128 columns
+//      of the tile for the row-wise copy, a column's 128 rows for the column-wise one (two waves share either)
+//   2  Float8BlockScaling, scaling dim 2: one power-of-two scale for the whole 128 x 128 tile, shared by both copies
+// GRAN 1 / 2 store the scale-inverse as an E8M0 byte at every 32-group position the block covers, in the MX layout, so the MX GEMMs
+// read these operands unchanged.  A trailing block shorter than 128 is a block over the elements that exist (the lanes outside
+// the tensor carry zeros).
+
+// TE's compute_scale_from_amax with power-of-two forcing (current_scale_kernel, mi_current.hip, pow2 = 1) for one block
+template <int FMT>
+__device__ __forceinline__ float blk_scale(float amax, float eps) {
+  const float a = amax < eps ? eps : amax;
+  float scale = 1.0f;
+  if (!(a == 0.0f) && !isinf(a)) {
+    scale = fp8_max_of<FMT>() / a;  // IEEE fp32 division (no fast-math in this build)
+    if (isinf(scale)) scale = FLT_MAX;
+    if (scale != scale) scale = 1.0f;
+  }
+  return __uint_as_float(__float_as_uint(scale) & 0xFF800000u);  // mantissa cleared: rounded DOWN to a power of two
+}
+// the E8M0 byte of 1 / scale for a power-of-two scale: 2^(byte - 127) * scale == 1 (0..247, never 0xFF)
+__device__ __forceinline__ u32 blk_scale_byte(float scale) { return 254u - ((__float_as_uint(scale) >> 23) & 0xFFu); }
+
+template <int FMT, bool ROWWISE, bool COLWISE, int PRE, int GRAN>
 __global__ __launch_bounds__(256) void mxfp8_quant_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ aux16,
                                                           const float* __restrict__ aux32, uint8_t* __restrict__ y_row,
                                                           uint8_t* __restrict__ s_row, uint8_t* __restrict__ y_colT,
                                                           uint8_t* __restrict__ s_colT, float* __restrict__ colsum, int rows,
                                                           int cols, int tiles_c, int ldr, const uint16_t* __restrict__ e0 = nullptr,
                                                           const float* __restrict__ e1 = nullptr, int i0 = 0, int i1 = 0,
-                                                          int i2 = 0) {
+                                                          int i2 = 0, float eps = 0.0f) {
   // ldr: leading dimension of s_row / y_colT (= rows, or the row count of a larger operand this tensor is a row-block of)
   __shared__ float s_col[2][128];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -185,35 +214,127 @@ __global__ __launch_bounds__(256) void mxfp8_quant_kernel(const uint16_t* __rest
   // NOTE: the quantisers' shuffles are executed by every lane (inactive lanes carry zeros); rows/cols are
   // multiples of 32 so a 4-lane block group is all-active or all-inactive.
   u32 lo[8], hi[8], sbytes[8];
-  if (ROWWISE) {
-    mx_quant_rows<FMT>(f, nanmask, lo, hi, sbytes);
-    if (active) {
-      store_rows8<MI_NT_Y>(y_row + (int64_t)r0 * cols + c0, cols, lo, hi);
-      // block-major scales [cols/32, rows]: this lane's 8 rows are 8 contiguous bytes
-      if ((lane & 3) == 0) store_scales8(s_row + (int64_t)(c0 / 32) * ldr + r0, sbytes);
+  if (GRAN == 0) {
+    if (ROWWISE) {
+      mx_quant_rows<FMT>(f, nanmask, lo, hi, sbytes);
+      if (active) {
+        store_rows8<MI_NT_Y>(y_row + (int64_t)r0 * cols + c0, cols, lo, hi);
+        // block-major scales [cols/32, rows]: this lane's 8 rows are 8 contiguous bytes
+        if ((lane & 3) == 0) store_scales8(s_row + (int64_t)(c0 / 32) * ldr + r0, sbytes);
+      }
     }
-  }
-  if (COLWISE) {
-    mx_quant_cols<FMT>(f, nanmask, lo, hi, sbytes);
+    if (COLWISE) {
+      mx_quant_cols<FMT>(f, nanmask, lo, hi, sbytes);
+      if (active) {
+        store_cols8<MI_NT_YT>(y_colT + (int64_t)c0 * ldr + r0, ldr, lo, hi);
+        // block-major scales [rows/32, cols]: 8 contiguous bytes for this lane's 8 columns
+        if (((lane >> 3) & 3) == 0) store_scales8(s_colT + (int64_t)(r0 / 32) * cols + c0, sbytes);
+      }
+    }
+  } else if (GRAN == 1) {
+    // 1 x 128 blocks: a row of the tile spans 8 lanes of each of the two waves (wave & 1) that hold its 128 columns, a column the 8
+    // row groups of each of the two waves (wave >> 1) that hold its 128 rows.  The partial maxima meet in LDS (entries 0..127: the
+    // tile's rows, 128..255: its columns); then every thread turns ONE pair into its block's scale -- one IEEE division per thread
+    // instead of one per row and column of every lane -- and the lanes read the scales back.
+    __shared__ float s_blk[256][2];
+    const int lr = (wave >> 1) * 64 + (lane >> 3) * 8, lc = (wave & 1) * 64 + (lane & 7) * 8;
+    if (ROWWISE) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float a = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a = fmaxf(a, fabsf(f[i][j]));
+        a = fmaxf(a, __shfl_xor(a, 1));
+        a = fmaxf(a, __shfl_xor(a, 2));
+        a = fmaxf(a, __shfl_xor(a, 4));
+        if ((lane & 7) == 0) s_blk[lr + i][wave & 1] = a;
+      }
+    }
+    if (COLWISE) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float a = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a = fmaxf(a, fabsf(f[i][j]));
+        a = fmaxf(a, __shfl_xor(a, 8));
+        a = fmaxf(a, __shfl_xor(a, 16));
+        a = fmaxf(a, __shfl_xor(a, 32));
+        if ((lane >> 3) == 0) s_blk[128 + lc + j][wave >> 1] = a;
+      }
+    }
+    __syncthreads();
+    if (tid < 128 ? ROWWISE : COLWISE) s_blk[tid][0] = blk_scale<FMT>(fmaxf(s_blk[tid][0], s_blk[tid][1]), eps);  // (its own pair only)
+    __syncthreads();
+    if (ROWWISE) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float sc = s_blk[lr + i][0];
+        sbytes[i] = blk_scale_byte(sc);
+        lo[i] = mx_patch4(cvt4_fp8<FMT>(f[i][0] * sc, f[i][1] * sc, f[i][2] * sc, f[i][3] * sc), nanmask, 8 * i);
+        hi[i] = mx_patch4(cvt4_fp8<FMT>(f[i][4] * sc, f[i][5] * sc, f[i][6] * sc, f[i][7] * sc), nanmask, 8 * i + 4);
+      }
+      if (active) {
+        store_rows8<MI_NT_Y>(y_row + (int64_t)r0 * cols + c0, cols, lo, hi);
+        // the block's byte at each of its four 32-groups: one lane per group stores it for its 8 rows
+        if ((lane & 3) == 0) store_scales8(s_row + (int64_t)(c0 / 32) * ldr + r0, sbytes);
+      }
+    }
+    if (COLWISE) {
+      float sc[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        sc[j] = s_blk[128 + lc + j][0];
+        sbytes[j] = blk_scale_byte(sc[j]);
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        lo[i] = mx_patch4(cvt4_fp8<FMT>(f[i][0] * sc[0], f[i][1] * sc[1], f[i][2] * sc[2], f[i][3] * sc[3]), nanmask, 8 * i);
+        hi[i] = mx_patch4(cvt4_fp8<FMT>(f[i][4] * sc[4], f[i][5] * sc[5], f[i][6] * sc[6], f[i][7] * sc[7]), nanmask, 8 * i + 4);
+      }
+      if (active) {
+        store_cols8<MI_NT_YT>(y_colT + (int64_t)c0 * ldr + r0, ldr, lo, hi);
+        if (((lane >> 3) & 3) == 0) store_scales8(s_colT + (int64_t)(r0 / 32) * cols + c0, sbytes);
+      }
+    }
+  } else {
+    // 128 x 128 block = the tile: one maximum over the workgroup, one scale, one convert; the transposed store reuses its bytes
+    float a = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a = fmaxf(a, fabsf(f[i][j]));
+    const float sc = blk_scale<FMT>(block_max(a), eps);
+    const u32 sb = blk_scale_byte(sc);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      sbytes[i] = sb;
+      lo[i] = mx_patch4(cvt4_fp8<FMT>(f[i][0] * sc, f[i][1] * sc, f[i][2] * sc, f[i][3] * sc), nanmask, 8 * i);
+      hi[i] = mx_patch4(cvt4_fp8<FMT>(f[i][4] * sc, f[i][5] * sc, f[i][6] * sc, f[i][7] * sc), nanmask, 8 * i + 4);
+    }
     if (active) {
-      store_cols8<MI_NT_YT>(y_colT + (int64_t)c0 * ldr + r0, ldr, lo, hi);
-      // block-major scales [rows/32, cols]: 8 contiguous bytes for this lane's 8 columns
-      if (((lane >> 3) & 3) == 0) store_scales8(s_colT + (int64_t)(r0 / 32) * cols + c0, sbytes);
+      if (ROWWISE) {
+        store_rows8<MI_NT_Y>(y_row + (int64_t)r0 * cols + c0, cols, lo, hi);
+        if ((lane & 3) == 0) store_scales8(s_row + (int64_t)(c0 / 32) * ldr + r0, sbytes);
+      }
+      if (COLWISE) {
+        store_cols8<MI_NT_YT>(y_colT + (int64_t)c0 * ldr + r0, ldr, lo, hi);
+        if (((lane >> 3) & 3) == 0) store_scales8(s_colT + (int64_t)(r0 / 32) * cols + c0, sbytes);
+      }
     }
   }
 }
 
-template <int PRE>
+template <int PRE, int GRAN = 0>
 static int launch_mx(int fmt, const void* x, const void* aux16, const float* aux32, void* y_row, void* s_row, void* y_colT, void* s_colT,
                      float* colsum, int64_t rows, int64_t cols, void* stream, int64_t ld_rows = 0, const void* e0 = nullptr,
-                     const float* e1 = nullptr, int i0 = 0, int i1 = 0, int i2 = 0) {
+                     const float* e1 = nullptr, int i0 = 0, int i1 = 0, int i2 = 0, float eps = 0.0f) {
   const int ldr = (int)(ld_rows > 0 ? ld_rows : rows);
   const int tiles_r = (int)((rows + 127) / 128), tiles_c = (int)((cols + 127) / 128);
   dim3 grid((unsigned)(tiles_r * tiles_c)), block(256);
-  MI_LAUNCH_FMT_YT(fmt, y_row, y_colT, mxfp8_quant_kernel, (), (, PRE), grid, block, 0, (hipStream_t)stream, (const uint16_t*)x,
+  MI_LAUNCH_FMT_YT(fmt, y_row, y_colT, mxfp8_quant_kernel, (), (, PRE, GRAN), grid, block, 0, (hipStream_t)stream, (const uint16_t*)x,
                    (const uint16_t*)aux16, aux32, (uint8_t*)y_row, (uint8_t*)s_row, (uint8_t*)y_colT, (uint8_t*)s_colT, colsum, (int)rows,
-                   (int)cols, tiles_c, ldr, (const uint16_t*)e0, e1, i0, i1, i2);
-  MI_CHECK_LAUNCH("mi_mxfp8_quantize launch");
+                   (int)cols, tiles_c, ldr, (const uint16_t*)e0, e1, i0, i1, i2, eps);
+  MI_CHECK_LAUNCH(GRAN == 0 ? "mi_mxfp8_quantize launch" : "mi_blockfp8_quantize launch");
   return MI_OK;
 }
 
@@ -292,4 +413,65 @@ extern "C" int mi_mxfp8_rope_bwd_quantize(const void* dq_bf16, const void* dk_bf
   if (rows == 0) return MI_OK;
   return mi::launch_mx<4>(fmt, dq_bf16, dk_bf16, cos_tab, y_row, s_row, y_colT, s_colT, nullptr, rows, W, stream, 0, dv_bf16, sin_tab,
                           n_q_heads, n_kv_heads, (int)seq);
+}
+
+// ---- Float8BlockScaling: the same kernel with 1 x 128 (block_dim 1) or 128 x 128 (block_dim 2) power-of-two scales ----
+static int blk_common_check(const char* who, const void* x, const void* y_row, const void* s_row, const void* y_colT,
+                            const void* s_colT, int64_t rows, int64_t cols, int fmt, int block_dim, float amax_epsilon) {
+  int rc = mx_common_check(who, x, y_row, s_row, y_colT, s_colT, rows, cols, fmt);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(block_dim == 1 || block_dim == 2, "%s: block_dim %d must be 1 (1x128 blocks) or 2 (128x128 blocks)", who, block_dim);
+  MI_CHECK_ARG(amax_epsilon >= 0.0f, "%s: amax_epsilon must be non-negative", who);
+  return MI_OK;
+}
+
+#define MI_BLK_DISPATCH(PRE, x, a16, a32, cs, rows, cols, ld)                                                                       \
+  (block_dim == 1 ? mi::launch_mx<PRE, 1>(fmt, x, a16, a32, y_row, s_row, y_colT, s_colT, cs, rows, cols, stream, ld, nullptr, nullptr, 0, \
+                                          0, 0, amax_epsilon)                                                                       \
+                  : mi::launch_mx<PRE, 2>(fmt, x, a16, a32, y_row, s_row, y_colT, s_colT, cs, rows, cols, stream, ld, nullptr, nullptr, 0, \
+                                          0, 0, amax_epsilon))
+
+extern "C" int mi_blockfp8_quantize_ex(const void* x_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT, float* colsum,
+                                       int64_t rows, int64_t cols, int64_t ld_rows, int fmt, int block_dim, float amax_epsilon,
+                                       void* stream) {
+  int rc = blk_common_check("mi_blockfp8_quantize_ex", x_bf16, y_row, s_row, y_colT, s_colT, rows, cols, fmt, block_dim, amax_epsilon);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(ld_rows >= rows && ld_rows % 8 == 0 && ld_rows < (1LL << 31),
+               "mi_blockfp8_quantize_ex: ld_rows (%lld) must be >= rows and a multiple of 8", (long long)ld_rows);
+  // a 128 x 128 block is a tile of THIS call: as a row-block of a larger operand (ld_rows > rows) the tensor has to begin on one of the
+  // operand's block rows, or its blocks are not the operand's.  The operand's buffers are at least 128-byte aligned, so the row
+  // offset modulo 128 shows in the two pointers that advance by one byte per row.
+  MI_CHECK_ARG(block_dim != 2 || ld_rows == rows || (((uintptr_t)s_row % 128) == 0 && ((uintptr_t)y_colT % 128) == 0),
+               "mi_blockfp8_quantize_ex: with block_dim 2 a row-block destination must start on a multiple of 128 rows of its operand");
+  if (rows == 0 || cols == 0) return MI_OK;
+  return MI_BLK_DISPATCH(0, x_bf16, nullptr, nullptr, colsum, rows, cols, ld_rows);
+}
+
+extern "C" int mi_blockfp8_norm_quantize(const void* x_bf16, const float* rstd, const void* gamma_bf16, void* y_row, void* s_row,
+                                         void* y_colT, void* s_colT, int64_t rows, int64_t cols, int fmt, int block_dim,
+                                         float amax_epsilon, void* stream) {
+  int rc = blk_common_check("mi_blockfp8_norm_quantize", x_bf16, y_row, s_row, y_colT, s_colT, rows, cols, fmt, block_dim, amax_epsilon);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(rstd && gamma_bf16 && ((uintptr_t)gamma_bf16 % 16) == 0, "mi_blockfp8_norm_quantize: rstd / gamma missing or misaligned");
+  if (rows == 0 || cols == 0) return MI_OK;
+  return MI_BLK_DISPATCH(1, x_bf16, gamma_bf16, rstd, nullptr, rows, cols, 0);
+}
+
+extern "C" int mi_blockfp8_swiglu_quantize(const void* h_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT, int64_t rows,
+                                           int64_t F, int fmt, int block_dim, float amax_epsilon, void* stream) {
+  int rc = blk_common_check("mi_blockfp8_swiglu_quantize", h_bf16, y_row, s_row, y_colT, s_colT, rows, F, fmt, block_dim, amax_epsilon);
+  if (rc != MI_OK) return rc;
+  if (rows == 0 || F == 0) return MI_OK;
+  return MI_BLK_DISPATCH(2, h_bf16, nullptr, nullptr, nullptr, rows, F, 0);
+}
+
+extern "C" int mi_blockfp8_dswiglu_quantize(const void* h_bf16, const void* dact_bf16, void* y_row, void* s_row, void* y_colT,
+                                            void* s_colT, float* colsum, int64_t rows, int64_t F, int fmt, int block_dim,
+                                            float amax_epsilon, void* stream) {
+  int rc = blk_common_check("mi_blockfp8_dswiglu_quantize", h_bf16, y_row, s_row, y_colT, s_colT, rows, 2 * F, fmt, block_dim,
+                            amax_epsilon);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(dact_bf16 && ((uintptr_t)dact_bf16 % 16) == 0, "mi_blockfp8_dswiglu_quantize: dact missing or misaligned");
+  if (rows == 0 || F == 0) return MI_OK;
+  return MI_BLK_DISPATCH(3, h_bf16, dact_bf16, nullptr, colsum, rows, 2 * F, 0);
 }

@@ -308,11 +308,21 @@ def uses_current_scaling(model: torch.nn.Module) -> bool:
     """Does any part of `model` run under Float8CurrentScaling?  The recipes a model carries: the decoder layers' per-region ones
     (llama.TELlamaDecoderLayer.attn_recipe / mlp_recipe) and the outer one of llama.apply_fp8_autowrap."""
     from .common.recipe import Float8CurrentScaling
+    return _carries_recipe(model, Float8CurrentScaling)
+
+
+def uses_block_scaling(model: torch.nn.Module) -> bool:
+    """The same question for Float8BlockScaling (scenario `block`), which keeps no optimiser-filled FP8 weight copies either."""
+    from .common.recipe import Float8BlockScaling
+    return _carries_recipe(model, Float8BlockScaling)
+
+
+def _carries_recipe(model: torch.nn.Module, cls) -> bool:
     mods = [model] + list(model.modules())
     inner = getattr(model, "module", None)  # a data-parallel wrapper keeps the autowrapped model here
     if isinstance(inner, torch.nn.Module):
         mods.append(inner)
-    return any(isinstance(getattr(m, a, None), Float8CurrentScaling) for m in mods
+    return any(isinstance(getattr(m, a, None), cls) for m in mods
                for a in ("attn_recipe", "mlp_recipe", "_fp8_outer_recipe"))
 
 
@@ -356,6 +366,11 @@ class ShardedFP8DP(GradArenaDP):
                                "row shards are quantised by the optimiser into FP8 weight sinks, and a current-scaled weight needs the "
                                "amax of the whole updated weight before any row can be cast.  Use --sharding_mode replicated "
                                "(GradArenaDP), which works as is: ranks scale their own activations and the weights are identical")
+        if uses_block_scaling(module):
+            # (a recipe handed to fp8_autocast by hand is caught at the first forward instead: module._BlockQ.no_sink)
+            raise RuntimeError("ShardedFP8DP (--sharding_mode fsdp_fp8) cannot run Float8BlockScaling (--fp8_scenario block): its row "
+                               "shards are quantised by the optimiser into FP8 weight sinks, and the optimiser pass has no form that "
+                               "emits 128x128 block-scaled copies.  Use --sharding_mode replicated (GradArenaDP), which works as is")
         self._rs_bucket_bytes = int(bucket_mb * (1 << 20))
         super().__init__(module, process_group, bucket_mb, broadcast, sparse_embedding_grads)
         self._shard_now()

@@ -3,13 +3,14 @@
 accelerate steps train_fp8.py relies on (`convert_model`, `apply_fp8_autowrap`).
 
 The three reference files differ only in the recipe objects, so one
-file serves all three scenarios, and a fourth the reference does not have:
+file serves all three scenarios, and two more the reference does not have:
 
   scenario   attention region                         MLP region                               reference
   default    DelayedScaling(HYBRID, 16, "max")        DelayedScaling(E4M3, 16, "max")          te_llama.py:39-40
   hybrid     DelayedScaling(HYBRID, 16, "max")        same recipe object                       te_llama_hybrid.py:39
   mxfp8      MXFP8BlockScaling(E4M3)                  same recipe object                       te_llama_mxfp8.py:28-29
   current    Float8CurrentScaling(HYBRID)             same recipe object (the lm_head too)     -- (TE's third per-tensor recipe)
+  block      Float8BlockScaling(E4M3)                 same recipe object (the lm_head too)     -- (TE's 1x128 / 128x128 block recipe)
 
 No weights, tokenizer or dataset exist offline: configs are hard-coded from the public model cards
  and models are random-initialised.
@@ -24,7 +25,7 @@ from typing import Dict, Optional
 import torch
 
 from . import pytorch as te
-from .common.recipe import DelayedScaling, Float8CurrentScaling, Format, MXFP8BlockScaling
+from .common.recipe import DelayedScaling, Float8BlockScaling, Float8CurrentScaling, Format, MXFP8BlockScaling
 from .pytorch.fp8 import FP8GlobalStateManager
 from .pytorch.module import _can_fuse_norm, residual_add_stats
 
@@ -57,6 +58,10 @@ def llama_config(name: str, **overrides):
     return cfg
 
 
+# scenario `block`: ONE recipe object for both regions and the lm_head (1x128 activation / gradient blocks, 128x128 weight blocks)
+_BLOCK_RECIPE = Float8BlockScaling()
+
+
 def scenario_recipes(scenario: str):
     """(attention-region recipe, MLP-region recipe) for --fp8_scenario (train_fp8.py:103-116)."""
     if scenario == "default":
@@ -71,6 +76,8 @@ def scenario_recipes(scenario: str):
     if scenario == "current":
         r = Float8CurrentScaling()
         return r, r
+    if scenario == "block":
+        return _BLOCK_RECIPE, _BLOCK_RECIPE
     raise ValueError(f"unknown fp8 scenario {scenario!r}")
 
 
@@ -423,5 +430,7 @@ def outer_recipe_for_scenario(scenario: str):
         return DelayedScaling(fp8_format=Format.HYBRID, amax_history_len=1024, amax_compute_algo="most_recent")
     if scenario == "current":  # per-tensor scales from the live amax everywhere, the lm_head included
         return Float8CurrentScaling()
+    if scenario == "block":  # the regions' own recipe object: block scales everywhere, the lm_head included
+        return _BLOCK_RECIPE
     # scenarios mxfp8 / hybrid: E4M3, history 16, "max", margin 0 (never MXFP8 for the outer recipe: Appendix C.9)
     return DelayedScaling(fp8_format=Format.E4M3, amax_history_len=16, amax_compute_algo="max", margin=0)

@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from ..common.recipe import DelayedScaling, Float8CurrentScaling, Format, MXFP8BlockScaling, Recipe, fmt_codes
+from ..common.recipe import DelayedScaling, Float8BlockScaling, Float8CurrentScaling, Format, MXFP8BlockScaling, Recipe, fmt_codes
 from . import ops
 from .fp8 import FP8GlobalStateManager, ModuleMeta
 
@@ -114,6 +114,8 @@ class _GemmSpec:
             self.q = _MXQ(self.fmt_fwd, self.fmt_bwd)
         elif recipe.current():
             self.q = _CurrentQ(recipe, self.fmt_fwd, self.fmt_bwd)
+        elif recipe.block():
+            self.q = _BlockQ(recipe, self.fmt_fwd, self.fmt_bwd)
         else:
             self.q = _DelayedQ(meta_fwd, meta_bwd, self.fmt_fwd, self.fmt_bwd)
         self.trigger_bwd_update = trigger_bwd_update
@@ -232,7 +234,7 @@ def _weight_ok_for_sink(w, K: int) -> bool:
             and (w.is_contiguous() or getattr(w, "_mi_sharded", None) is not None))
 
 
-# What differs between the recipes at a GEMM site, behind the same few methods (`_GemmSpec.q` is one of the three classes below).  A quantised
+# What differs between the recipes at a GEMM site, behind the same few methods (`_GemmSpec.q` is one of the four classes below).  A quantised
 # operand has one shape under both: (row, col), the row-wise copy [R, C] and the column-wise one, stored transposed [C, R], each a
 # (data, scale) pair -- None data where the copy was not asked for.  `scale` is the one-element scale-inverse under delayed and
 # current scaling and the block-major E8M0 tensor under MXFP8.  A GEMM contracts the row-wise copies of its operands: the forward takes `row` of
@@ -406,6 +408,87 @@ class _MXQ:
 
     def sink_flat(self, sink, g: int):
         return sink.w8, sink.sc, sink.wt8, sink.sct
+
+
+class _BlockQ(_MXQ):
+    """Float8BlockScaling: no state; every quantisation finds one power-of-two scale per 1 x 128 block along the contraction axis
+    (scaling dim 1) or per 128 x 128 block (dim 2) and stores its inverse as the E8M0 byte of every 32-group the block covers, in
+    the MX operand layout.  An operand therefore IS an MXFP8 operand: `operands`, `gemm`, `unflat`, the grouped dgrad + wgrad
+    launch and its autotune key are _MXQ's.  With 128 x 128 weight blocks the column-wise weight copy is the byte transpose of the
+    row-wise one under the same scales, so the forward and dgrad GEMMs see one quantised weight."""
+    __slots__ = ("recipe",)
+    cache_key, sink_key = "blk", "blksink"
+    # the optimiser pass has no form that emits block-scaled copies (a 128 x 128 block's amax needs 128 updated rows before any of
+    # them can be cast): no sink, the forward quantises the weights (the is_first_microbatch cache still keeps them across a
+    # window) -- and distributed.ShardedFP8DP, which lives on optimiser-filled sinks, cannot run this recipe
+    no_sink = ("Float8BlockScaling keeps no optimiser-filled FP8 weight copies, which row-sharded weights (distributed.ShardedFP8DP, "
+               "--sharding_mode fsdp_fp8) depend on: use --sharding_mode replicated (GradArenaDP) with this recipe")
+
+    def __init__(self, recipe: Float8BlockScaling, fmt_f: int, fmt_b: int):
+        super().__init__(fmt_f, fmt_b)
+        self.recipe = recipe
+
+    def quantize(self, x2, g: int, want_t: bool, norm=None):
+        r = self.recipe
+        dim, eps = r.x_block_scaling_dim, r.fp8_quant_fwd_inp.amax_epsilon
+        if norm is None:
+            q = ops.blockfp8_quantize(x2, self.fmt_f, dim, rowwise=True, colwise=want_t, amax_epsilon=eps)
+        else:
+            q = ops.blockfp8_norm_quantize(x2, norm[0], norm[1], self.fmt_f, dim, rowwise=True, colwise=want_t, amax_epsilon=eps)
+        return q[:2], q[2:]
+
+    def swiglu(self, h, g: int, want_t: bool, bias):
+        assert bias is None
+        r = self.recipe
+        q = ops.blockfp8_swiglu_quantize(h, self.fmt_f, r.x_block_scaling_dim, rowwise=True, colwise=want_t,
+                                         amax_epsilon=r.fp8_quant_fwd_inp.amax_epsilon)
+        return q[:2], q[2:]
+
+    def quantize_grad(self, g2, g: int, want_y: bool, want_t: bool, colsum: bool = False):
+        r = self.recipe
+        q = ops.blockfp8_quantize(g2, self.fmt_b, r.grad_block_scaling_dim, rowwise=want_y, colwise=want_t, want_colsum=colsum,
+                                  amax_epsilon=r.fp8_quant_bwd_grad.amax_epsilon)
+        return q[:2], q[2:4], q[4] if colsum else None
+
+    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
+        assert bias is None
+        r = self.recipe
+        q = ops.blockfp8_dswiglu_quantize(h, dact, self.fmt_b, r.grad_block_scaling_dim, rowwise=want_y, colwise=want_t,
+                                          want_colsum=colsum, amax_epsilon=r.fp8_quant_bwd_grad.amax_epsilon)
+        return q[:2], q[2:4], q[4]
+
+    def offer(self, handoff: DyHandoff, g: int, want_y: bool, want_t: bool) -> None:
+        """Nothing: no DyHandoff producer has a block-scaled form.  RoPE backward and cross-entropy backward take their bf16 route
+        and the Linear quantises the gradient it receives."""
+
+    def taken(self, fp8, g: int):
+        raise RuntimeError("Float8BlockScaling offers no DyHandoff, so no producer can have put FP8 copies into one")
+
+    def quantize_weights(self, weights, ns, N: int, K: int, dev, g: int, want_t: bool):
+        """Every part is quantised straight into its row-block of the operand's buffers, no bf16 concatenation -- unless a part's
+        rows are no multiple of the block's rows (128 for 128 x 128 blocks; 32, the layout's unit, for 1 x 128).  One launch per
+        part emits both copies; with 128 x 128 blocks they hold the same bytes under the same scales."""
+        r = self.recipe
+        fmt, dim, eps = self.fmt_f, r.w_block_scaling_dim, r.fp8_quant_fwd_weight.amax_epsilon
+        ws_ = [(w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous() for w in weights]
+        if len(ws_) == 1:
+            return ops.blockfp8_quantize(ws_[0], fmt, dim, rowwise=True, colwise=want_t, amax_epsilon=eps)
+        if any(n % (128 if dim == 2 else 32) for n in ns):
+            return ops.blockfp8_quantize(torch.cat(ws_, 0), fmt, dim, rowwise=True, colwise=want_t, amax_epsilon=eps)
+        w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
+        sc = torch.empty((K // 32, N), dtype=torch.uint8, device=dev)
+        wt8 = torch.empty((K, N), dtype=torch.uint8, device=dev) if want_t else None
+        sct = torch.empty((N // 32, K), dtype=torch.uint8, device=dev) if want_t else None
+        o = 0
+        for w, n in zip(ws_, ns):
+            ops.blockfp8_quantize(w, fmt, dim, rowwise=True, colwise=want_t, amax_epsilon=eps,
+                                  out=(w8[o:o + n], sc[:, o:o + n], wt8[:, o:o + n] if want_t else None,
+                                       sct[o // 32:(o + n) // 32] if want_t else None))
+            o += n
+        return w8, sc, wt8, sct
+
+    def new_sink(self, weights, ns, N: int, K: int, dev, g: int):
+        return None
 
 
 class _CurrentQ:
@@ -833,7 +916,7 @@ class _FP8Module(torch.nn.Module):
             return None
         recipe = FP8GlobalStateManager.get_fp8_recipe()
         first = FP8GlobalStateManager.is_first_fp8_module()
-        if recipe.mxfp8() or recipe.current():  # no state: no meta windows, no arenas, an empty _extra_state
+        if recipe.mxfp8() or recipe.current() or recipe.block():  # no state: no meta windows, no arenas, an empty _extra_state
             return recipe, None, None, first
         key = (recipe.fp8_format, recipe.amax_history_len, recipe.amax_compute_algo, recipe.margin, str(device))
         if self._meta_key != key:
@@ -1039,7 +1122,7 @@ def _can_fuse_norm(mod, recipe, inp) -> bool:
     """K9 applies to RMSNorm (every recipe); the backward kernel keeps a whole row per wave (cols % 512, <= 8192)."""
     h = inp.shape[-1]
     return (getattr(mod, "fused_norm", True) and mod.normalization == "RMSNorm" and not mod.zero_centered_gamma
-            and (recipe.delayed() or recipe.mxfp8() or recipe.current()) and h % 512 == 0 and h // 512 in (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16))
+            and (recipe.delayed() or recipe.mxfp8() or recipe.current() or recipe.block()) and h % 512 == 0 and h // 512 in (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16))
 
 
 def _swiglu(a: torch.Tensor) -> torch.Tensor:
@@ -1109,7 +1192,7 @@ class LayerNormMLP(_FP8Module):
             return F.linear(self.act_fn(h), _master(self.fc2_weight).to(ln.dtype),
                             None if self.fc2_bias is None else self.fc2_bias.to(ln.dtype))
         recipe = st[0]
-        if self.activation == "swiglu" and self.fused_swiglu and (not recipe.mxfp8() or inp.numel() // inp.shape[-1] % 32 == 0):
+        if self.activation == "swiglu" and self.fused_swiglu and (not (recipe.mxfp8() or recipe.block()) or inp.numel() // inp.shape[-1] % 32 == 0):
             return _FP8SwiGLUMLPFn.apply(ln, self.fc1_weight, self.fc1_bias, self.fc2_weight, self.fc2_bias,
                                          self._spec(st, is_first_microbatch))
         h = _FP8LinearFn.apply(ln, self.fc1_bias, self._spec(st, is_first_microbatch), None, self.fc1_weight)

@@ -860,6 +860,98 @@ def mxfp8_dswiglu_quantize(h: torch.Tensor, dact: torch.Tensor, fmt: int = E4M3,
     return (*out, cs)
 
 
+# ---- Float8BlockScaling: the K7 kernel with 1 x 128 (dim 1) / 128 x 128 (dim 2) power-of-two scales.  Same tuples and the same
+# operand layout as the mxfp8_* functions above (the block's E8M0 byte at every 32-group it covers): gemm_mxfp8 reads them as is. ----
+def _blk_call(kind: str, name: str, args, R: int, C: int, in_bytes: float, rowwise: bool, colwise: bool):
+    fn = _lib.require(name, "Float8BlockScaling")
+    t = KernelTimer.active
+    if t is None:
+        rc = fn(*args)
+    else:
+        with t.span("blockfp8_quantize", f"{kind} {R}x{C}".strip(), float(R * C),
+                    in_bytes + R * C * (1 + 1 / 32) * (int(rowwise) + int(colwise))):
+            rc = fn(*args)
+    _lib.check(rc, name)
+
+
+def _blk_dim(dim: int) -> int:
+    if dim not in (1, 2):
+        raise ValueError(f"block scaling dim must be 1 (1x128 blocks) or 2 (128x128 blocks), got {dim!r}")
+    return int(dim)
+
+
+def blockfp8_quantize(x: torch.Tensor, fmt: int = E4M3, dim: int = 1, rowwise: bool = True, colwise: bool = True, out=None,
+                      want_colsum: bool = False, amax_epsilon: float = 0.0):
+    """mxfp8_quantize with one power-of-two scale per 1 x 128 block along the contraction axis (`dim` 1) or per 128 x 128 block
+    (`dim` 2: y_colT is the byte transpose of y_row).  Same returns, same `out` row-block form (with `dim` 2 the row-block must
+    start on a multiple of 128 rows of its operand), same `want_colsum`."""
+    _dev(x)
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
+    R, C = x.shape
+    ld = R
+    if out is not None:
+        y_row, s_row, y_colT, s_colT = out
+        _dev(y_row, s_row, y_colT, s_colT)
+        assert (y_row is not None) == rowwise and (y_colT is not None) == colwise
+        if rowwise:
+            assert y_row.shape == (R, C) and y_row.is_contiguous() and s_row.shape == (C // 32, R) and s_row.stride(1) == 1
+            ld = s_row.stride(0)
+        if colwise:
+            assert y_colT.shape == (C, R) and y_colT.stride(1) == 1 and s_colT.shape == (R // 32, C) and s_colT.is_contiguous()
+            assert not rowwise or y_colT.stride(0) == ld
+            ld = y_colT.stride(0)
+    else:
+        y_row, s_row, y_colT, s_colT = _mx_alloc(R, C, x.device, rowwise, colwise)
+    cs = torch.empty(((R + 127) // 128, C), dtype=torch.float32, device=x.device) if want_colsum else None
+    _blk_call("", "mi_blockfp8_quantize_ex",
+              (x.data_ptr(), _ptr(y_row), _ptr(s_row), _ptr(y_colT), _ptr(s_colT), _ptr(cs), R, C, ld, fmt, _blk_dim(dim),
+               float(amax_epsilon), _stream()), R, C, 2.0 * R * C, rowwise, colwise)
+    return (y_row, s_row, y_colT, s_colT, cs) if want_colsum else (y_row, s_row, y_colT, s_colT)
+
+
+def blockfp8_norm_quantize(x: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, fmt: int = E4M3, dim: int = 1,
+                           rowwise: bool = True, colwise: bool = True, amax_epsilon: float = 0.0):
+    """mxfp8_norm_quantize under block scaling: quantises (x * rstd[:, None]) * gamma without materialising it."""
+    _dev(x, rstd, gamma)
+    assert x.dtype == torch.bfloat16 and gamma.dtype == torch.bfloat16 and x.is_contiguous() and gamma.is_contiguous()
+    R, C = x.shape
+    out = _mx_alloc(R, C, x.device, rowwise, colwise)
+    _blk_call("norm", "mi_blockfp8_norm_quantize",
+              (x.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), *[_ptr(o) for o in out], R, C, fmt, _blk_dim(dim),
+               float(amax_epsilon), _stream()), R, C, 2.0 * R * C, rowwise, colwise)
+    return out
+
+
+def blockfp8_swiglu_quantize(h: torch.Tensor, fmt: int = E4M3, dim: int = 1, rowwise: bool = True, colwise: bool = True,
+                             amax_epsilon: float = 0.0):
+    """mxfp8_swiglu_quantize under block scaling: quantises silu(h[:, :F]) * h[:, F:] ([R, F])."""
+    _dev(h)
+    assert h.dtype == torch.bfloat16 and h.is_contiguous() and h.shape[1] % 2 == 0
+    R, F = h.shape[0], h.shape[1] // 2
+    out = _mx_alloc(R, F, h.device, rowwise, colwise)
+    _blk_call("swiglu", "mi_blockfp8_swiglu_quantize",
+              (h.data_ptr(), *[_ptr(o) for o in out], R, F, fmt, _blk_dim(dim), float(amax_epsilon), _stream()), R, F, 4.0 * R * F,
+              rowwise, colwise)
+    return out
+
+
+def blockfp8_dswiglu_quantize(h: torch.Tensor, dact: torch.Tensor, fmt: int = E4M3, dim: int = 1, rowwise: bool = True,
+                              colwise: bool = True, want_colsum: bool = False, amax_epsilon: float = 0.0):
+    """mxfp8_dswiglu_quantize under block scaling: quantises dh = [dact*dsilu(g)*u | dact*silu(g)] ([R, 2F]); returns
+    (..., colsum or None)."""
+    _dev(h, dact)
+    assert h.dtype == torch.bfloat16 and dact.dtype == torch.bfloat16 and h.is_contiguous() and dact.is_contiguous()
+    R, F2 = h.shape
+    F = F2 // 2
+    assert dact.shape == (R, F)
+    out = _mx_alloc(R, F2, h.device, rowwise, colwise)
+    cs = torch.empty(((R + 127) // 128, F2), dtype=torch.float32, device=h.device) if want_colsum else None
+    _blk_call("dswiglu", "mi_blockfp8_dswiglu_quantize",
+              (h.data_ptr(), dact.data_ptr(), *[_ptr(o) for o in out], _ptr(cs), R, F, fmt, _blk_dim(dim), float(amax_epsilon),
+               _stream()), R, F2, 6.0 * R * F, rowwise, colwise)
+    return (*out, cs)
+
+
 def _bshd_ok(t: torch.Tensor, D: int):
     assert t.dtype == torch.bfloat16 and t.dim() == 4 and t.shape[3] == D and t.stride(3) == 1 and t.stride(2) == D
     assert t.stride(0) == t.shape[1] * t.stride(1), "batch and sequence must collapse to one token stride"

@@ -32,7 +32,7 @@ class TrainingConfig:
     batch_size: int = 16
     max_seq_length: int = 512
     mixed_precision: str = "fp8"          # "bf16" | "fp8"
-    fp8_scenario: str = "default"         # "default" | "hybrid" | "mxfp8" | "current" (llama.scenario_recipes)
+    fp8_scenario: str = "default"         # "default" | "hybrid" | "mxfp8" | "current" | "block" (llama.scenario_recipes)
     use_te: bool = True
     learning_rate: float = 1.41e-5
     num_warmup_steps: int = 100
@@ -141,7 +141,8 @@ def resolve_sharding_mode(mode: str, model: torch.nn.Module, device, optimizer_s
     (`optimizer_state` "fp32" adds 8 bytes per trainable parameter to that state: +25.6 GB for 3B, +64 GB for 8B).  An explicit
     ddp / fsdp_full / replicated request is honoured even at world size 1 (rehearsal on a one-GPU box).
     A model that runs Float8CurrentScaling (scenario `current`) never resolves to `fsdp_fp8`: that mode lives on FP8 weight copies the
-    optimiser emits, which current scaling does not have; where the replicated state does not fit, `auto` is torch's `fsdp_full`."""
+    optimiser emits, which current scaling does not have; where the replicated state does not fit, `auto` is torch's `fsdp_full`.
+    The same holds for Float8BlockScaling (scenario `block`)."""
     import torch.distributed as dist
     if mode != "auto":
         return mode
@@ -150,10 +151,10 @@ def resolve_sharding_mode(mode: str, model: torch.nn.Module, device, optimizer_s
     from .distributed import fits_replicated
     # does not fit: the FULL_SHARD counterpart with FP8 all-gathers (distributed.ShardedFP8DP; masters, gradients and AdamW
     # moments of every GEMM weight at 1/world per rank), not torch FSDP (bf16 gathers in forward and backward, a cast after each)
-    from .distributed import uses_current_scaling
+    from .distributed import uses_block_scaling, uses_current_scaling
     if fits_replicated(model, device, optimizer_state=resolve_optimizer_state(optimizer_state)):
         return "replicated"
-    return "fsdp_full" if uses_current_scaling(model) else "fsdp_fp8"
+    return "fsdp_full" if (uses_current_scaling(model) or uses_block_scaling(model)) else "fsdp_fp8"
 
 
 def _single_process(model: torch.nn.Module, device) -> torch.nn.Module:
@@ -322,7 +323,7 @@ def build_arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch_size", type=int, default=16)
     ap.add_argument("--max_seq_length", type=int, default=512)
     ap.add_argument("--mixed_precision", choices=["bf16", "fp8"], default="fp8")
-    ap.add_argument("--fp8_scenario", choices=["default", "hybrid", "mxfp8", "current"], default="default")
+    ap.add_argument("--fp8_scenario", choices=["default", "hybrid", "mxfp8", "current", "block"], default="default")
     ap.add_argument("--use_te", action="store_true")
     ap.add_argument("--sharding_mode", choices=SHARDING_MODES, default="auto")
     ap.add_argument("--num_steps", type=int, default=10)
