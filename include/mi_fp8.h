@@ -69,9 +69,10 @@ extern "C" {
  *      before its cast, and the scale from it)
  *   3  mi_blockfp8_quantize_ex, mi_blockfp8_norm_quantize, mi_blockfp8_swiglu_quantize, mi_blockfp8_dswiglu_quantize
  *      (Float8BlockScaling: 1 x 128 and 128 x 128 power-of-two block scales in the MX operand layout)
+ *   4  mi_adamw_sr_bf16_multi (stochastic rounding of the bf16 weight and moments in the fused AdamW + FP8 cast pass)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 3
+#define MI_ABI_REVISION 4
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -492,6 +493,34 @@ int mi_adamw_mxcast_bf16_multi(const int64_t* table, int n_tensors, const int32_
 int mi_adamw_f32_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                        const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                        int64_t step, int sink_kind, void* stream);
+
+/*
+ * mi_adamw_cast_bf16_multi (sink_kind 0) / mi_adamw_mxcast_bf16_multi (sink_kind 1) with STOCHASTIC ROUNDING of every bf16 result
+ * (ABI 5 revision 4): the same bf16 state, walks and fp32 arithmetic; only the rounding of the updated weight, exp_avg and
+ * exp_avg_sq to bf16 differs.  An update below half a bf16 ulp then moves the weight with the matching probability instead of
+ * never, and exp_avg_sq decays (beta2 = 0.999 is a relative change below half an ulp: under RNE it does not).
+ * Rounding rule, for an fp32 result x with bits b: finite x -> bf16 bits (b + r) >> 16 with r = 16 uniform random bits, i.e. x goes
+ * to its upper neighbour (in magnitude) with probability (b & 0xFFFF) / 65536 and a bf16 value never moves; the largest finite
+ * magnitudes may become Inf, as under RNE.  NaN and Inf take the RNE conversion of the other calls and use no random bits.
+ * Generator: Philox4x32-10 (Salmon et al., SC'11; multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85), stateless.
+ *   key     = (seed & 0xFFFFFFFF, seed >> 32)
+ *   counter = (v & 0xFFFFFFFF, v >> 32, step & 0xFFFFFFFF, tensor_key << 2 | stream)
+ *   v = e >> 3 for the GLOBAL element index e = table row 12 + the element's index inside the tensor; stream 0 = weight,
+ *   1 = exp_avg, 2 = exp_avg_sq.  Element e takes r = bits [16 (j & 1), + 16) of output word j >> 1, j = e & 7: one call per
+ *   stream serves 8 consecutive elements.  The bits of an element depend on (seed, step, tensor key, stream, e) and on nothing
+ *   else: not on the walk (128 x 128 tile, 8-wide flat vector, element-wise tail), the chunking, the sink, or on whether the
+ *   tensor is a whole weight or a row shard of it (row 12 = first row x cols).
+ * table: int64 [14, n_tensors].  Rows 0-11 as for mi_adamw_cast_bf16_multi (sink_kind 0) or mi_adamw_mxcast_bf16_multi
+ * (sink_kind 1); 12 the global index of the tensor's first element (>= 0; the 8-wide walks need a multiple of 8, which the caller
+ * guarantees for tensors with cols > 0 -- a flat tensor with another base is walked element-wise); 13 the tensor key, < 2^30.
+ * The FP8 / MXFP8 copies are quantised from the stochastically rounded bf16 weight as stored: bitwise mi_cast_amax /
+ * mi_mxfp8_quantize of the updated p.  Alignment rules and refusals as for mi_adamw_f32_multi: MI_ERR_ARG before any launch for a
+ * null table / chunks, n_tensors < 1, chunk_elems not a positive multiple of 8, sink_kind outside {0, 1}, step < 1; n_chunks == 0
+ * is MI_OK.
+ */
+int mi_adamw_sr_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
+                           const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
+                           int64_t step, int sink_kind, uint64_t seed, void* stream);
 
 /*
  * Embedding weight gradient added in place: grad[id, :] += alpha * sum_{tokens t with ids[t] == id} dY[t, :]   (bf16, fp32

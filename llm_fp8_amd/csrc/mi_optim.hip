@@ -219,6 +219,66 @@ __device__ __forceinline__ float state_load(const float* b, int64_t k) { return 
 __device__ __forceinline__ void state_store(uint16_t* b, int64_t k, float f) { b[k] = (uint16_t)float_to_bf16_bits(f); }
 __device__ __forceinline__ void state_store(float* b, int64_t k, float f) { b[k] = f; }
 
+// ---- stochastic rounding of the bf16 results (SR = true instantiations of the bf16-state kernels; include/mi_fp8.h
+// mi_adamw_sr_bf16_multi states the rule and the generator).  Philox4x32-10, counter-based: the 16 random bits of an element are a
+// function of (seed, step, tensor key, stream, global element index) alone, whichever walk reaches the element.
+struct AdamSrArgs : AdamArgs {
+  u32 k0, k1, step;  // seed low / high word, step mod 2^32
+};
+template <bool SR> struct AdamKernelArgs { typedef AdamArgs T; };
+template <> struct AdamKernelArgs<true> { typedef AdamSrArgs T; };
+
+__device__ __forceinline__ void philox4x32_10(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1, u32 (&out)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const u32 h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const u32 h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// One tensor's generator inputs.  SR = false: empty, nothing is read or computed.
+template <bool SR>
+struct SrCtx {
+  __device__ __forceinline__ SrCtx(const AdamArgs&, const int64_t* __restrict__, int, int) {}
+};
+template <>
+struct SrCtx<true> {
+  u32 k0, k1, step, key4;
+  int64_t base;  // global index of the tensor's first element (table row 12)
+  __device__ __forceinline__ SrCtx(const AdamSrArgs& a, const int64_t* __restrict__ tab, int T, int t) {
+    k0 = a.k0; k1 = a.k1; step = a.step;
+    base = tab[(int64_t)12 * T + t];
+    key4 = (u32)tab[(int64_t)13 * T + t] << 2;
+  }
+  // the four words of `stream` for the 8 elements [8 v, 8 v + 8)
+  __device__ __forceinline__ void words(int64_t v, u32 stream, u32 (&w)[4]) const {
+    philox4x32_10((u32)v, (u32)((unsigned long long)v >> 32), step, key4 | stream, k0, k1, w);
+  }
+  // the 16 bits of global element e
+  __device__ __forceinline__ u32 bits16(int64_t e, u32 stream) const {
+    u32 w[4];
+    words(e >> 3, stream, w);
+    const int j = (int)(e & 7);
+    return (w[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+  }
+};
+// fp32 -> bf16 bits with the 16 random bits r: finite x moves to its upper neighbour with probability (low 16 bits) / 65536;
+// NaN and Inf convert as everywhere else
+__device__ __forceinline__ u32 sr_bf16_bits(float x, u32 r) {
+  const u32 b = __float_as_uint(x);
+  return ((b & 0x7F800000u) == 0x7F800000u) ? float_to_bf16_bits(x) : (b + r) >> 16;
+}
+__device__ __forceinline__ u32 sr_pack_bf16x2(float lo, float hi, u32 word) {
+  return sr_bf16_bits(lo, word & 0xFFFFu) | (sr_bf16_bits(hi, word >> 16) << 16);
+}
+
 // The tensor's addresses out of the table: `w` is what the update reads and writes at full state precision (p itself for bf16
 // state, the fp32 master of row 12 otherwise).
 template <typename ST>
@@ -243,11 +303,21 @@ struct AdamPtrs {
 };
 
 // AdamW on one lane's 8 consecutive elements (vector index i): load, update, store.  f = the 8 weights as stored in p -- the
-// ROUNDED bf16 values, which is what the FP8 sinks quantise.
-template <typename ST>
-__device__ __forceinline__ void adam_vec8(const AdamPtrs<ST>& t, int64_t i, float gs, const AdamArgs& a, float (&f)[8]) {
+// ROUNDED bf16 values, which is what the FP8 sinks quantise.  SR (bf16 state only): the three roundings are stochastic, one
+// generator call per stream for the lane's 8 elements (sr.base is a multiple of 8 on this path).
+template <typename ST, bool SR>
+__device__ __forceinline__ void adam_vec8(const AdamPtrs<ST>& t, int64_t i, float gs, const AdamArgs& a, const SrCtx<SR>& sr,
+                                          float (&f)[8]) {
+  static_assert(!SR || sizeof(ST) == 2, "stochastic rounding is for bf16 state");
   Vec8<ST> wv, mv, vv;
   u32 pw[4];
+  [[maybe_unused]] u32 rp[4], rm[4], rv[4];
+  if constexpr (SR) {
+    const int64_t v = (sr.base >> 3) + i;
+    sr.words(v, 0, rp);
+    sr.words(v, 1, rm);
+    sr.words(v, 2, rv);
+  }
   wv.load(t.w, i);
   const v4i gv = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(t.g) + i);
   mv.load(t.m, i);
@@ -265,11 +335,17 @@ __device__ __forceinline__ void adam_vec8(const AdamPtrs<ST>& t, int64_t i, floa
       wv.set(j, (float)pl, (float)ph);           // the master: the fp64 result rounded once to fp32 ...
       pw[j] = pack_bf16x2(wv.lo(j), wv.hi(j));   // ... and p = RNE_bf16 of that STORED value
     } else {
-      pw[j] = pack_bf16x2(pl, ph);
+      if constexpr (SR) pw[j] = sr_pack_bf16x2(pl, ph, rp[j]);
+      else pw[j] = pack_bf16x2(pl, ph);
       wv.x[j] = (int)pw[j];
     }
-    mv.set(j, (float)ml, (float)mh);
-    vv.set(j, (float)vl, (float)vh);
+    if constexpr (SR) {
+      mv.x[j] = (int)sr_pack_bf16x2(ml, mh, rm[j]);
+      vv.x[j] = (int)sr_pack_bf16x2(vl, vh, rv[j]);
+    } else {
+      mv.set(j, (float)ml, (float)mh);
+      vv.set(j, (float)vl, (float)vh);
+    }
     f[2 * j] = __uint_as_float(pw[j] << 16);
     f[2 * j + 1] = __uint_as_float(pw[j] & 0xFFFF0000u);
   }
@@ -283,17 +359,20 @@ __device__ __forceinline__ void adam_vec8(const AdamPtrs<ST>& t, int64_t i, floa
 }
 
 // Flat walk of one chunk: elements [chunk * chunk_elems, + chunk_elems) of the tensor, 8 per lane where every array is 16-byte
-// aligned, one per lane otherwise and on the tail.
-template <typename ST>
+// aligned, one per lane otherwise and on the tail.  SR: a tensor whose first element is not at a multiple of 8 of the global index
+// is walked element-wise too (a lane's 8 elements would straddle two generator calls).
+template <typename ST, bool SR>
 __device__ __forceinline__ void adam_flat_chunk(const AdamPtrs<ST>& t, int64_t n, int chunk, int chunk_elems, float gs,
-                                                const AdamArgs& a, int tid) {
+                                                const AdamArgs& a, const SrCtx<SR>& sr, int tid) {
   const int64_t lo = (int64_t)chunk * chunk_elems, hi = min(n, lo + chunk_elems);
   int64_t done = lo;
-  if (t.aligned16()) {
+  bool vec = t.aligned16();
+  if constexpr (SR) vec = vec && (sr.base & 7) == 0;
+  if (vec) {
     const int64_t v0 = lo >> 3, v1 = hi >> 3;
     for (int64_t i = v0 + tid; i < v1; i += 256) {
       float f[8];
-      adam_vec8(t, i, gs, a, f);
+      adam_vec8(t, i, gs, a, sr, f);
     }
     done = v1 << 3;
   }
@@ -301,10 +380,17 @@ __device__ __forceinline__ void adam_flat_chunk(const AdamPtrs<ST>& t, int64_t n
     typedef typename AdamMath<ST>::T T;
     T pf = state_load(t.w, k), mf = state_load(t.m, k), vf = state_load(t.v, k);
     adam_one(pf, T(gs) * T(bf16_bits_to_float(t.g[k])), mf, vf, a);
-    state_store(t.w, k, (float)pf);
-    if constexpr (sizeof(ST) == 4) t.p[k] = (uint16_t)float_to_bf16_bits((float)pf);
-    state_store(t.m, k, (float)mf);
-    state_store(t.v, k, (float)vf);
+    if constexpr (SR) {
+      const int64_t e = sr.base + k;
+      t.w[k] = (uint16_t)sr_bf16_bits(pf, sr.bits16(e, 0));
+      t.m[k] = (uint16_t)sr_bf16_bits(mf, sr.bits16(e, 1));
+      t.v[k] = (uint16_t)sr_bf16_bits(vf, sr.bits16(e, 2));
+    } else {
+      state_store(t.w, k, (float)pf);
+      if constexpr (sizeof(ST) == 4) t.p[k] = (uint16_t)float_to_bf16_bits((float)pf);
+      state_store(t.m, k, (float)mf);
+      state_store(t.v, k, (float)vf);
+    }
   }
 }
 
@@ -314,7 +400,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restr
   const AdamPtrs<uint16_t> t(tab, T, cr.tensor);
   const int64_t n = tab[(int64_t)4 * T + cr.tensor];
   const float gs = grad_scale ? *grad_scale : 1.0f;
-  adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, threadIdx.x);
+  adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, SrCtx<false>(a, tab, T, cr.tensor), threadIdx.x);
 }
 
 // AdamW + FP8 weight cast in one pass (the weight-cast hand-off): under delayed scaling the scale the NEXT
@@ -326,17 +412,20 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restr
 // Tensors without a sink (cols == 0) take the flat path of adamw_multi_kernel.  Table rows (int64 each, T columns):
 //   0 p  1 g  2 exp_avg  3 exp_avg_sq  4 numel  5 cols  6 y  7 yT  8 ld_y  9 ld_yT  10 scale ptr  11 amax ptr
 //   12 fp32 master weight (ST = float only: rows 2, 3 are then fp32 too and p is output only)
-template <typename ST>
+//   SR = true (bf16 state, stochastic rounding): 12 global index of the tensor's first element  13 tensor key
+template <typename ST, bool SR = false>
 __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
-                                                               int chunk_elems, const float* __restrict__ grad_scale, AdamArgs a) {
+                                                               int chunk_elems, const float* __restrict__ grad_scale,
+                                                               typename AdamKernelArgs<SR>::T a) {
   const ChunkRef cr = chunks[blockIdx.x];
   const AdamPtrs<ST> t(tab, T, cr.tensor);
+  const SrCtx<SR> sr(a, tab, T, cr.tensor);
   const int64_t n = tab[(int64_t)4 * T + cr.tensor];
   const int64_t cols = tab[(int64_t)5 * T + cr.tensor];
   const float gs = grad_scale ? *grad_scale : 1.0f;
   const int tid = threadIdx.x;
   if (cols == 0) {  // flat chunk (the walk of adamw_multi_kernel)
-    adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, tid);
+    adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);
     return;
   }
   // tile of a weight with an FP8 sink
@@ -357,7 +446,7 @@ __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       float f[8];  // the ROUNDED weight: what the next forward's cast would read
-      adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, f);
+      adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, sr, f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) amax = fmaxf(amax, (f[j] != f[j]) ? 0.0f : fabsf(f[j]));
       lo[i] = cvt4_fp8<MI_FMT_E4M3>(f[0] * scale, f[1] * scale, f[2] * scale, f[3] * scale);
@@ -381,17 +470,19 @@ __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __
 //   10 ldr (rows of the whole operand the tensor is a row-block of)  11 unused  12 fp32 master weight (ST = float only)
 // y_row / s_row / y_colT / s_colT point at the tensor's first row inside the operand's buffers: y_row [rows, cols],
 // s_row [cols/32, ldr], y_colT [cols, ldr], s_colT [rows/32, cols].
-template <typename ST>
+template <typename ST, bool SR = false>
 __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
-                                                                 int chunk_elems, const float* __restrict__ grad_scale, AdamArgs a) {
+                                                                 int chunk_elems, const float* __restrict__ grad_scale,
+                                                                 typename AdamKernelArgs<SR>::T a) {
   const ChunkRef cr = chunks[blockIdx.x];
   const AdamPtrs<ST> t(tab, T, cr.tensor);
+  const SrCtx<SR> sr(a, tab, T, cr.tensor);
   const int64_t n = tab[(int64_t)4 * T + cr.tensor];
   const int64_t cols = tab[(int64_t)5 * T + cr.tensor];
   const float gs = grad_scale ? *grad_scale : 1.0f;
   const int tid = threadIdx.x;
   if (cols == 0) {  // flat chunk (the walk of adamw_multi_kernel)
-    adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, tid);
+    adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);
     return;
   }
   uint8_t* y_row = reinterpret_cast<uint8_t*>(tab[(int64_t)6 * T + cr.tensor]);
@@ -410,7 +501,7 @@ __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* 
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     if (active) {
-      adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, f[i]);  // the ROUNDED weight: what the next forward's quantiser would read
+      adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, sr, f[i]);  // the ROUNDED weight: what the next forward's quantiser would read
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) f[i][j] = 0.0f;
@@ -539,6 +630,32 @@ extern "C" int mi_adamw_f32_multi(const int64_t* table, int n_tensors, const int
     hipLaunchKernelGGL(mi::adamw_mxcast_multi_kernel<float>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table,
                        n_tensors, (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, a);
   MI_CHECK_LAUNCH("mi_adamw_f32_multi launch");
+  return MI_OK;
+}
+
+// bf16 state with stochastic rounding: the SR instantiations of the same two kernels (table rows 12, 13: element base, tensor key)
+extern "C" int mi_adamw_sr_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
+                                      const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                      int64_t step, int sink_kind, uint64_t seed, void* stream) {
+  MI_CHECK_ARG(table && chunks, "mi_adamw_sr_bf16_multi: null pointer");
+  MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 0 && step >= 1, "mi_adamw_sr_bf16_multi: bad sizes");
+  MI_CHECK_ARG(chunk_elems >= 8 && chunk_elems % 8 == 0, "mi_adamw_sr_bf16_multi: chunk_elems must be a positive multiple of 8");
+  MI_CHECK_ARG(sink_kind == 0 || sink_kind == 1, "mi_adamw_sr_bf16_multi: sink_kind must be 0 (per-tensor FP8) or 1 (MXFP8)");
+  if (n_chunks == 0) return MI_OK;
+  mi::AdamSrArgs a;
+  static_cast<mi::AdamArgs&>(a) = make_adam_args(lr, beta1, beta2, eps, weight_decay, step);
+  a.k0 = (mi::u32)(seed & 0xFFFFFFFFull);
+  a.k1 = (mi::u32)(seed >> 32);
+  a.step = (mi::u32)((uint64_t)step & 0xFFFFFFFFull);
+  constexpr auto cast_sr = mi::adamw_cast_multi_kernel<uint16_t, true>;
+  constexpr auto mxcast_sr = mi::adamw_mxcast_multi_kernel<uint16_t, true>;
+  if (sink_kind == 0)
+    hipLaunchKernelGGL(cast_sr, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
+                       (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, a);
+  else
+    hipLaunchKernelGGL(mxcast_sr, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
+                       (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, a);
+  MI_CHECK_LAUNCH("mi_adamw_sr_bf16_multi launch");
   return MI_OK;
 }
 

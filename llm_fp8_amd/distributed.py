@@ -500,7 +500,14 @@ class ShardedFP8DP(GradArenaDP):
     # ------------------------------------------------------------------------------------------------ optimiser side
     def optimizer_param_groups(self):
         """Two groups for optim.ClippedAdamW: replicated parameters (every rank updates them identically) and the row shards
-        (`sharded=True`: their squared gradient norm is summed over the ranks of `dp_group` before the clip coefficient is formed)."""
+        (`sharded=True`: their squared gradient norm is summed over the ranks of `dp_group` before the clip coefficient is formed).
+        A shard whose full parameter carries `_mi_sr_key = (key, base)` (stochastic rounding, train.assign_sr_keys) gets the same
+        key and the global index of its first element, base + r0 x cols: it draws the random bits its rows draw in the whole weight."""
+        for sp in self._shards.values():
+            full, r0, _ = sp._mi_shard_of
+            k = getattr(full, "_mi_sr_key", None)
+            if k is not None:
+                sp._mi_sr_key = (k[0], k[1] + r0 * sp.shape[1])
         seen, rep_u = set(), []
         for p in self.module.parameters():
             if p.requires_grad and id(p) not in self._sharded and id(p) not in seen:
@@ -722,7 +729,7 @@ def replicated_state_bytes(module: torch.nn.Module, moment_bytes: int = 4, optim
     """Weights + gradients + two AdamW moments per trainable parameter (moments counted at fp32 to be safe).  `optimizer_state`
     "fp32" (optim.ClippedAdamW(state_dtype=torch.float32)) adds 8 bytes per trainable parameter on top of the bf16 layout: a
     4-byte master weight and two moments 2 bytes wider each (3B: +25.6 GB, 8B: +64 GB)."""
-    extra = 8 if optimizer_state == "fp32" else 0
+    extra = 8 if optimizer_state == "fp32" else 0  # "bf16_sr" (stochastic rounding) is the bf16 layout
     n = sum(p.numel() * (2 * p.element_size() + 2 * moment_bytes + extra) for p in module.parameters() if p.requires_grad)
     return n + sum(p.numel() * p.element_size() for p in module.parameters() if not p.requires_grad)
 

@@ -3,7 +3,8 @@
 AdamW update with the clip coefficient folded in (the gradients are never rescaled in place), each ONE multi-tensor launch
 per parameter group (device tables of tensor addresses + a chunk list).  bf16 parameters with bf16
 `exp_avg` / `exp_avg_sq`, fp32 math -- the state layout of torch's fused AdamW, so `state_dict()` is interchangeable.
-`state_dtype=torch.float32` keeps an fp32 master weight and fp32 moments behind the same passes instead (`ClippedAdamW`)."""
+`state_dtype=torch.float32` keeps an fp32 master weight and fp32 moments behind the same passes instead (`ClippedAdamW`);
+`stochastic_rounding=True` keeps the bf16 layout and rounds the weight and both moments stochastically."""
 from __future__ import annotations
 
 import os
@@ -29,13 +30,30 @@ class ClippedAdamW(torch.optim.Optimizer):
     `p._version`, and such a write DISCARDS the fp32 residue of that tensor -- the step starts from the value written.  A write
     that autograd's version counter does not see (`p.data.copy_(...)`, a raw kernel) is not detected, here as for the FP8 weight
     copies: the next step overwrites it from the master.  `load_state_dict` keeps the three tensors in fp32 and trusts a loaded
-    master (load the model's weights BEFORE the optimiser state, or the load counts as an external write)."""
+    master (load the model's weights BEFORE the optimiser state, or the load counts as an external write).
+
+    `stochastic_rounding=True` (bf16 state only; `mi_adamw_sr_bf16_multi`): the layout of the default mode, but the updated weight,
+    `exp_avg` and `exp_avg_sq` are rounded to bf16 stochastically -- fp32 bits b become `(b + r) >> 16` with 16 random bits r -- so
+    an update below half a bf16 ulp moves the weight with the matching probability and `exp_avg_sq` decays, at no extra memory.
+    The bits come from a counter-based generator (Philox4x32-10) keyed by `sr_seed` and counted by the parameter's `step`, a tensor
+    key and the element's index: a run is reproducible, a resumed run continues the same stream, and a row shard draws the bits
+    its rows would draw in the whole weight.  Key and first element index of a tensor are `p._mi_sr_key = (key, base)` when set,
+    else (position of the parameter over the param groups, 0).  With fp32 state the master carries the residue and
+    `p = RNE(master)` is right: the combination is refused.  `stochastic_rounding` and `sr_seed` are kept in the param groups
+    (and so in `state_dict()`) only in this mode."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm: Optional[float] = 1.0,
-                 state_dtype: torch.dtype = torch.bfloat16):
+                 state_dtype: torch.dtype = torch.bfloat16, stochastic_rounding: bool = False, sr_seed: int = 0):
         if state_dtype not in (torch.bfloat16, torch.float32):
             raise ValueError(f"ClippedAdamW: state_dtype must be torch.bfloat16 or torch.float32, not {state_dtype!r}")
+        if stochastic_rounding and state_dtype == torch.float32:
+            raise ValueError("ClippedAdamW: stochastic_rounding=True is for bf16 state; with state_dtype=torch.float32 the master "
+                             "weight carries the residue and p = RNE(master) is the right rounding")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._sr = bool(stochastic_rounding)
+        self.sr_seed = int(sr_seed) & 0xFFFFFFFFFFFFFFFF
+        if self._sr:
+            defaults.update(stochastic_rounding=True, sr_seed=self.sr_seed)
         super().__init__(params, defaults)
         self.max_grad_norm = max_grad_norm
         self.state_dtype = state_dtype
@@ -99,6 +117,19 @@ class ClippedAdamW(torch.optim.Optimizer):
             return None
         return s
 
+    def _sr_key(self, p):
+        """(tensor key, global index of the first element) of the stochastic-rounding generator for `p`."""
+        k = getattr(p, "_mi_sr_key", None)
+        if k is None:
+            index = getattr(self, "_sr_index", None)
+            if index is None or id(p) not in index:
+                index = self._sr_index = {id(q): i for i, q in enumerate(q for g in self.param_groups for q in g["params"])}
+            k = (index[id(p)], 0)
+        key, base = int(k[0]), int(k[1])
+        if not (0 <= key < 1 << 30 and base >= 0):
+            raise ValueError(f"ClippedAdamW: _mi_sr_key {k!r}: the tensor key must be in [0, 2^30) and the element base >= 0")
+        return key, base
+
     def _plan(self, group_items, dev, mx=False):
         """Device tables of one parameter group for the multi-tensor kernels.  The chunk lists only depend on the tensor sizes
         (and on which tensors have an FP8 sink) and are built once; the address table is re-uploaded when an address changed
@@ -121,8 +152,9 @@ class ClippedAdamW(torch.optim.Optimizer):
                     tr, tc = (p.shape[0] + self.TILE - 1) // self.TILE, (p.shape[1] + self.TILE - 1) // self.TILE
                     refs_cast.extend((t, c) for c in range(tr * tc))
             chunks = torch.tensor(refs, dtype=torch.int32).to(dev)
-            any_sink = self._f32 or any(s is not None for s in sinks)  # mi_adamw_f32_multi always walks the cast list
-            nrows = 13 if self._f32 else 12
+            # mi_adamw_f32_multi and mi_adamw_sr_bf16_multi always walk the cast list
+            any_sink = self._f32 or self._sr or any(s is not None for s in sinks)
+            nrows = 13 if self._f32 else 14 if self._sr else 12
             plan = {"sizes": sizes, "sink_sig": sink_sig, "chunks": chunks, "n_chunks": len(refs), "addr": None,
                     "chunks_cast": torch.tensor(refs_cast, dtype=torch.int32).to(dev) if any_sink else None, "n_chunks_cast": len(refs_cast),
                     "table": torch.empty((nrows, len(sizes)), dtype=torch.int64, device=dev),
@@ -133,6 +165,13 @@ class ClippedAdamW(torch.optim.Optimizer):
         rows = [[], [], [], [], list(sizes), [], [], [], [], [], [], []]
         if self._f32:
             rows.append([self.state[p]["master"].data_ptr() for _, p in group_items])  # 12: the fp32 master weight
+        if self._sr:
+            keys = [self._sr_key(p) for _, p in group_items]
+            for (_, p), s, (_, base) in zip(group_items, sinks, keys):
+                if s is not None and base % 8:
+                    raise ValueError(f"ClippedAdamW: element base {base} of a weight with an FP8 sink must be a multiple of 8")
+            rows.append([base for _, base in keys])  # 12: global index of the tensor's first element
+            rows.append([key for key, _ in keys])    # 13: tensor key
         for (_, p), s in zip(group_items, sinks):
             st = self.state[p]
             rows[0].append(p.data_ptr())
@@ -201,6 +240,13 @@ class ClippedAdamW(torch.optim.Optimizer):
         state is upcast and the master seeded from `p`); bf16 mode keeps torch's behaviour and drops the master of an fp32-mode
         state.  A loaded master is trusted: it is taken to go with the parameters as they are at this moment."""
         super().load_state_dict(state_dict)
+        for group in self.param_groups:  # the mode is this optimiser's; the seed of a saved stochastic-rounding run is kept
+            if self._sr:
+                group["stochastic_rounding"] = True
+                group.setdefault("sr_seed", self.sr_seed)
+            else:
+                group.pop("stochastic_rounding", None)
+                group.pop("sr_seed", None)
         if not self._f32:
             for st in self.state.values():
                 st.pop("master", None)
@@ -229,6 +275,7 @@ class ClippedAdamW(torch.optim.Optimizer):
             return None
         lib = _lib.load()
         f32_step = _lib.require("mi_adamw_f32_multi", "ClippedAdamW(state_dtype=torch.float32)") if self._f32 else None
+        sr_step = _lib.require("mi_adamw_sr_bf16_multi", "ClippedAdamW(stochastic_rounding=True)") if self._sr else None
         dev = items[0][1].device
         st = torch.cuda.current_stream().cuda_stream
         by_group = {}
@@ -301,6 +348,12 @@ class ClippedAdamW(torch.optim.Optimizer):
                               coef_ptr, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
                               int(self.state[gi[0][1]]["step"]), 1 if plan["mx"] else 0, st)
                 _lib.check(rc, "mi_adamw_f32_multi")
+            elif self._sr:  # bf16 state, stochastic rounding: the counter is the partition's step, the key the group's seed
+                rc = sr_step(plan["table"].data_ptr(), len(gi), plan["chunks_cast"].data_ptr(), plan["n_chunks_cast"], self.CHUNK,
+                             coef_ptr, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
+                             int(self.state[gi[0][1]]["step"]), 1 if plan["mx"] else 0,
+                             int(group.get("sr_seed", self.sr_seed)) & 0xFFFFFFFFFFFFFFFF, st)
+                _lib.check(rc, "mi_adamw_sr_bf16_multi")
             elif plan["chunks_cast"] is not None:  # some weights of this partition have FP8 sinks: update + cast in one pass
                 fn = lib.mi_adamw_mxcast_bf16_multi if plan["mx"] else lib.mi_adamw_cast_bf16_multi
                 rc = fn(plan["table"].data_ptr(), len(gi), plan["chunks_cast"].data_ptr(), plan["n_chunks_cast"],

@@ -45,7 +45,7 @@ class TrainingConfig:
     vocab_size: Optional[int] = None
     output_dir: Optional[str] = None      # ModelSaver.save_model (train_fp8.py:657-681)
     load_dir: Optional[str] = None        # local checkpoint directory (from_pretrained_local, te_llama.py:100-178)
-    optimizer_state: Optional[str] = None  # "bf16" | "fp32" (optim.ClippedAdamW state_dtype); None: resolve_optimizer_state
+    optimizer_state: Optional[str] = None  # "bf16" | "fp32" | "bf16_sr" (optim.ClippedAdamW); None: resolve_optimizer_state
 
 
 def create_model(cfg: TrainingConfig, device) -> torch.nn.Module:
@@ -112,13 +112,14 @@ def prepare_model(model: torch.nn.Module, cfg: TrainingConfig) -> torch.nn.Modul
     return model
 
 
-OPTIMIZER_STATES = ("bf16", "fp32")
+OPTIMIZER_STATES = ("bf16", "fp32", "bf16_sr")
 
 
 def resolve_optimizer_state(cfg_or_value=None) -> str:
     """Precision the optimiser state is kept in: `TrainingConfig.optimizer_state` / `--optimizer_state`, else the environment
     variable LLM_FP8_AMD_OPT_STATE (so a worker script can be driven in either mode unedited), else `bf16` (the reference's
-    layout: torch's fused AdamW on bf16 parameters).  `fp32` = fp32 master weights and moments (optim.ClippedAdamW)."""
+    layout: torch's fused AdamW on bf16 parameters).  `fp32` = fp32 master weights and moments (optim.ClippedAdamW); `bf16_sr` =
+    the bf16 layout with stochastic rounding of the weight and both moments (optim.ClippedAdamW(stochastic_rounding=True))."""
     v = getattr(cfg_or_value, "optimizer_state", cfg_or_value)
     if v is None:
         v = os.environ.get("LLM_FP8_AMD_OPT_STATE") or "bf16"
@@ -198,9 +199,23 @@ def wrap_distributed(model: torch.nn.Module, cfg: TrainingConfig, device) -> tor
     raise ValueError(f"unsupported sharding_mode {cfg.sharding_mode!r} (one of {SHARDING_MODES})")
 
 
+def assign_sr_keys(model) -> None:
+    """`p._mi_sr_key = (tensor key, first element index)` for optim.ClippedAdamW(stochastic_rounding=True): the key is the
+    parameter's position in the unwrapped module's `parameters()`, so it is the same under every wrapper and on every rank
+    (distributed.ShardedFP8DP.optimizer_param_groups hands a row shard its full parameter's key and its first row's index)."""
+    inner = model
+    while isinstance(getattr(inner, "module", None), torch.nn.Module):
+        inner = inner.module
+    for i, p in enumerate(inner.parameters()):
+        p._mi_sr_key = (i, 0)
+
+
 def create_optimizer(model, cfg: TrainingConfig):
     """AdamW(fused=True) + linear warmup/decay (train_fp8.py:200-210).  On the single-GPU path (bf16 parameters on the
     device, no FSDP/DDP wrapper) the clip + AdamW pair runs as `ClippedAdamW` (two HIP passes, same update rule)."""
+    opt_state = resolve_optimizer_state(cfg)
+    if opt_state == "bf16_sr":
+        assign_sr_keys(model)  # before the groups are formed: the row shards take their keys from the full parameters
     groups = model.optimizer_param_groups() if hasattr(model, "optimizer_param_groups") else None
     params = [p for g in groups for p in g["params"]] if groups is not None else [p for p in model.parameters() if p.requires_grad]
     fused = all(p.is_cuda for p in params)
@@ -210,19 +225,21 @@ def create_optimizer(model, cfg: TrainingConfig):
         # registered: the decoder weights' gradients would never enter the norm; and no FP8 copy would be kept current
         raise RuntimeError("LLM_FP8_AMD_TORCH_ADAMW=1 is not supported with --sharding_mode fsdp_fp8 (ShardedFP8DP): its row "
                            "shards need ClippedAdamW's clip over the ranks -- unset the variable or use another sharding mode")
-    opt_state = resolve_optimizer_state(cfg)
     if (fused and not wrapped and all(p.dtype == torch.bfloat16 for p in params)
             and os.environ.get("LLM_FP8_AMD_TORCH_ADAMW") != "1"):
         from .optim import ClippedAdamW
+        # sr_seed: the same on every rank (replicated ranks must stay identical; a row shard draws its rows' bits of the whole weight)
         opt = ClippedAdamW(groups if groups is not None else params, lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm,
-                           state_dtype=torch.float32 if opt_state == "fp32" else torch.bfloat16)
+                           state_dtype=torch.float32 if opt_state == "fp32" else torch.bfloat16,
+                           stochastic_rounding=opt_state == "bf16_sr", sr_seed=cfg.seed)
     else:
-        if opt_state == "fp32":  # torch's AdamW keeps its state in the parameters' dtype: no silent downgrade to bf16 state
+        if opt_state in ("fp32", "bf16_sr"):  # torch's AdamW keeps its state in the parameters' dtype and rounds to nearest: no silent downgrade
             why = ("the parameters are not all on the GPU" if not fused else
                    f"the model is wrapped in {type(model).__name__}" if wrapped else
                    "LLM_FP8_AMD_TORCH_ADAMW=1 selects torch's AdamW" if os.environ.get("LLM_FP8_AMD_TORCH_ADAMW") == "1" else
                    "the parameters are not all bf16")
-            raise RuntimeError(f"optimizer_state='fp32' needs ClippedAdamW (fp32 master weights and moments), but {why}: "
+            need = "fp32 master weights and moments" if opt_state == "fp32" else "stochastic rounding of the bf16 state"
+            raise RuntimeError(f"optimizer_state={opt_state!r} needs ClippedAdamW ({need}), but {why}: "
                                "torch.optim.AdamW would be built instead, with its state in the parameters' dtype")
         opt = torch.optim.AdamW(params, lr=cfg.learning_rate, fused=fused)
 
@@ -337,7 +354,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--save_layout", choices=["hf", "te"], default="hf")
     ap.add_argument("--repeat_batch", action="store_true", help="debug: train on one fixed synthetic batch")
     ap.add_argument("--optimizer_state", choices=OPTIMIZER_STATES, default=None,
-                    help="precision of the AdamW state: bf16 (default; or $LLM_FP8_AMD_OPT_STATE) | fp32 master weights + moments")
+                    help="precision of the AdamW state: bf16 (default; or $LLM_FP8_AMD_OPT_STATE) | fp32 master weights + moments | "
+                         "bf16_sr: bf16 with stochastic rounding of the weight and moments")
     return ap
 
 
