@@ -1,6 +1,7 @@
 // Shared device/host helpers for libmi_fp8 (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
@@ -130,6 +131,20 @@ __device__ __forceinline__ float e8m0_inv(u32 e) {
   if (e == 0xFFu) return __uint_as_float(0x7FC00000u);
   if (e == 0xFEu) return __uint_as_float(0x00400000u);
   return __uint_as_float((254u - e) << 23);
+}
+
+// TE's compute_scale_from_amax: fp8_max / max(amax, eps), 1 where that is no finite number; `pow2` rounds it DOWN to a power of
+// two.  The per-tensor scale of current scaling (mi_current.hip) and the block scales of Float8BlockScaling (mi_mxfp8.hip).
+__device__ __forceinline__ float scale_from_amax(float amax, float fp8_max, float eps, bool pow2) {
+  const float a = amax < eps ? eps : amax;
+  float scale = 1.0f;
+  if (!(a == 0.0f) && !isinf(a)) {
+    scale = fp8_max / a;  // IEEE fp32 division (no fast-math in this build)
+    if (isinf(scale)) scale = FLT_MAX;
+    if (scale != scale) scale = 1.0f;
+  }
+  if (pow2) scale = __uint_as_float(__float_as_uint(scale) & 0xFF800000u);  // mantissa cleared
+  return scale;
 }
 
 __device__ __forceinline__ float wave_max(float v) {

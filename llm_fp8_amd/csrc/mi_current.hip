@@ -18,7 +18,6 @@
 // MI_AMAX_NT (build-time): nontemporal (1) or plain (0, the product) loads in the amax pass.  The cast that follows re-reads the same
 // tensor, and behind plain loads it finds more of it on the die: 8192 x 3072 takes 10.0 us plain against 12.3 us nontemporal alone,
 // and the pair amax + mi_cast_amax 32.7 us against 37.2 us (the cast alone: 31.1 us; profiles/current_scaling.txt).
-#include <float.h>
 #include "mi_common.h"
 
 #ifndef MI_AMAX_NT
@@ -162,14 +161,7 @@ __global__ __launch_bounds__(256) void current_scale_kernel(const float* __restr
   for (int i = tid; i < n; i += 256) m = fmaxf(m, partial[i]);  // (the passes never write a NaN)
   const float amax = block_max(m);
   if (tid == 0) {
-    const float a = amax < eps ? eps : amax;
-    float scale = 1.0f;
-    if (!(a == 0.0f) && !isinf(a)) {
-      scale = fp8_max / a;  // IEEE fp32 division (no fast-math in this build)
-      if (isinf(scale)) scale = FLT_MAX;
-      if (scale != scale) scale = 1.0f;
-    }
-    if (pow2) scale = __uint_as_float(__float_as_uint(scale) & 0xFF800000u);  // mantissa cleared: rounded DOWN to a power of two
+    const float scale = scale_from_amax(amax, fp8_max, eps, pow2 != 0);
     out3[0] = amax;
     out3[1] = scale;
     out3[2] = 1.0f / scale;

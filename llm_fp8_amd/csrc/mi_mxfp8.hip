@@ -11,8 +11,9 @@
 // (te_llama_mxfp8.py:28-29,86,93; SURVEY.md 2.3 K7, Appendix A "MXFP8").
 // The same kernel quantises for Float8BlockScaling (template parameter GRAN below): one power-of-two scale per 1 x 128 or 128 x 128
 // block, whose inverse is stored as an E8M0 byte at every 32-block position the block covers -- the layout above, so the MX GEMMs
-// read such operands unchanged (mi_blockfp8_* at the end of this file).
-#include <float.h>
+// read such operands unchanged.
+// Host side: ONE argument check (quant_check), ONE launcher (launch_mx) and one body per producer (quant_plain / _norm / _swiglu /
+// _dswiglu / _rope_bwd) serve both families; the mi_mxfp8_* and mi_blockfp8_* entry points only say which granularity they mean.
 #include "mi_common.h"
 
 namespace mi {
@@ -24,7 +25,7 @@ namespace mi {
 //   2  silu(h[r,c]) * h[r,F+c]                (SwiGLU)      x = h: [rows, 2*cols]
 //   3  dSwiGLU: [d*dsilu(g)*u | d*silu(g)]                  x = h: [rows, cols] (cols = 2F), aux16 = d: [rows, F];
 //      colsum[tile_r, c] = per-128-row column sums (fc1 bias gradient, fixed order)
-__device__ __forceinline__ float mx_sigmoid(float g) { return 1.0f / (1.0f + __expf(-g)); }
+// The per-element values of 1 .. 3 are those of the delayed-scaling casts: norm_value2, swiglu_value2 and sigmoidf_ (mi_common.h).
 
 // GRAN selects the scaling granularity of the quantise stage; the value block, the producers, the column sums and the NaN handling
 // above it are the same code for all three:
@@ -36,18 +37,9 @@ __device__ __forceinline__ float mx_sigmoid(float g) { return 1.0f / (1.0f + __e
 // read these operands unchanged.  A trailing block shorter than 128 is a block over the elements that exist (the lanes outside
 // the tensor carry zeros).
 
-// TE's compute_scale_from_amax with power-of-two forcing (current_scale_kernel, mi_current.hip, pow2 = 1) for one block
+// one block's scale: TE's compute_scale_from_amax with power-of-two forcing
 template <int FMT>
-__device__ __forceinline__ float blk_scale(float amax, float eps) {
-  const float a = amax < eps ? eps : amax;
-  float scale = 1.0f;
-  if (!(a == 0.0f) && !isinf(a)) {
-    scale = fp8_max_of<FMT>() / a;  // IEEE fp32 division (no fast-math in this build)
-    if (isinf(scale)) scale = FLT_MAX;
-    if (scale != scale) scale = 1.0f;
-  }
-  return __uint_as_float(__float_as_uint(scale) & 0xFF800000u);  // mantissa cleared: rounded DOWN to a power of two
-}
+__device__ __forceinline__ float blk_scale(float amax, float eps) { return scale_from_amax(amax, fp8_max_of<FMT>(), eps, true); }
 // the E8M0 byte of 1 / scale for a power-of-two scale: 2^(byte - 127) * scale == 1 (0..247, never 0xFF)
 __device__ __forceinline__ u32 blk_scale_byte(float scale) { return 254u - ((__float_as_uint(scale) >> 23) & 0xFFu); }
 
@@ -103,11 +95,7 @@ __global__ __launch_bounds__(256) void mxfp8_quant_kernel(const uint16_t* __rest
         rs = aux32[r0 + i];
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        u32 w = (u32)raw[j];
-        f[i][2 * j] = (__uint_as_float(w << 16) * rs) * gm[2 * j];
-        f[i][2 * j + 1] = (__uint_as_float(w & 0xFFFF0000u) * rs) * gm[2 * j + 1];
-      }
+      for (int j = 0; j < 4; ++j) norm_value2((u32)raw[j], rs, gm[2 * j], gm[2 * j + 1], f[i][2 * j], f[i][2 * j + 1]);
     }
     any_nan = true;  // computed values: take the explicit NaN test below
   } else if (PRE == 4) {
@@ -172,17 +160,18 @@ __global__ __launch_bounds__(256) void mxfp8_quant_kernel(const uint16_t* __rest
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const u32 wg = (u32)gv[j], wu = (u32)uv[j], wd = (u32)dv[j];
+        if (PRE == 2) {
+          swiglu_value2<0>(wg, wu, wd, false, nullptr, nullptr, &f[i][2 * j], nullptr);
+          continue;
+        }
+        // a lane is in one half of dh: it takes that half's expression of swiglu_value2<1> alone
         const float g2[2] = {__uint_as_float(wg << 16), __uint_as_float(wg & 0xFFFF0000u)};
         const float u2[2] = {__uint_as_float(wu << 16), __uint_as_float(wu & 0xFFFF0000u)};
         const float d2[2] = {__uint_as_float(wd << 16), __uint_as_float(wd & 0xFFFF0000u)};
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          const float sg = mx_sigmoid(g2[e]);
-          float v;
-          if (PRE == 2) v = g2[e] * sg * u2[e];
-          else if (!up_half) v = d2[e] * u2[e] * (sg * (1.0f + g2[e] * (1.0f - sg)));
-          else v = d2[e] * (g2[e] * sg);
-          f[i][2 * j + e] = v;
+          const float sg = sigmoidf_(g2[e]);
+          f[i][2 * j + e] = !up_half ? d2[e] * u2[e] * (sg * (1.0f + g2[e] * (1.0f - sg))) : d2[e] * (g2[e] * sg);
         }
       }
     }
@@ -324,154 +313,166 @@ __global__ __launch_bounds__(256) void mxfp8_quant_kernel(const uint16_t* __rest
   }
 }
 
-template <int PRE, int GRAN = 0>
-static int launch_mx(int fmt, const void* x, const void* aux16, const float* aux32, void* y_row, void* s_row, void* y_colT, void* s_colT,
-                     float* colsum, int64_t rows, int64_t cols, void* stream, int64_t ld_rows = 0, const void* e0 = nullptr,
-                     const float* e1 = nullptr, int i0 = 0, int i1 = 0, int i2 = 0, float eps = 0.0f) {
+// What every entry point below hands on unchanged: its name, the scaling granularity (blk false: MX, gran 0; blk true:
+// Float8BlockScaling with gran = block_dim, 1 or 2, and eps = amax_epsilon), the four outputs, the format and the stream.
+// (`blk` beside `gran`: a mi_blockfp8_* caller's block_dim arrives unchecked, and its 0 has to be refused by name, not run as MX.)
+struct QuantCall {
+  const char* who;
+  bool blk;
+  int gran;
+  float eps;
+  void *y_row, *s_row, *y_colT, *s_colT;
+  int fmt;
+  void* stream;
+};
+
+// The launch of every producer; the ONE place where the run-time granularity becomes the GRAN template argument.
+template <int PRE>
+static int launch_mx(const QuantCall& c, const void* x, const void* aux16, const float* aux32, float* colsum, int64_t rows, int64_t cols,
+                     int64_t ld_rows = 0, const void* e0 = nullptr, const float* e1 = nullptr, int i0 = 0, int i1 = 0, int i2 = 0) {
+  if (rows == 0 || cols == 0) return MI_OK;
   const int ldr = (int)(ld_rows > 0 ? ld_rows : rows);
   const int tiles_r = (int)((rows + 127) / 128), tiles_c = (int)((cols + 127) / 128);
   dim3 grid((unsigned)(tiles_r * tiles_c)), block(256);
-  MI_LAUNCH_FMT_YT(fmt, y_row, y_colT, mxfp8_quant_kernel, (), (, PRE, GRAN), grid, block, 0, (hipStream_t)stream, (const uint16_t*)x,
-                   (const uint16_t*)aux16, aux32, (uint8_t*)y_row, (uint8_t*)s_row, (uint8_t*)y_colT, (uint8_t*)s_colT, colsum, (int)rows,
-                   (int)cols, tiles_c, ldr, (const uint16_t*)e0, e1, i0, i1, i2, eps);
-  MI_CHECK_LAUNCH(GRAN == 0 ? "mi_mxfp8_quantize launch" : "mi_blockfp8_quantize launch");
+#define MI_MX_LAUNCH_(GRAN)                                                                                                        \
+  MI_LAUNCH_FMT_YT(c.fmt, c.y_row, c.y_colT, mxfp8_quant_kernel, (), (, PRE, GRAN), grid, block, 0, (hipStream_t)c.stream,          \
+                   (const uint16_t*)x, (const uint16_t*)aux16, aux32, (uint8_t*)c.y_row, (uint8_t*)c.s_row, (uint8_t*)c.y_colT,     \
+                   (uint8_t*)c.s_colT, colsum, (int)rows, (int)cols, tiles_c, ldr, (const uint16_t*)e0, e1, i0, i1, i2, c.eps)
+  if constexpr (PRE == 4) {  // RoPE backward has no block-scaled form (quant_rope_bwd refuses one): MX is its only instantiation
+    MI_MX_LAUNCH_(0);
+  } else {
+    if (c.gran == 0) MI_MX_LAUNCH_(0);
+    else if (c.gran == 1) MI_MX_LAUNCH_(1);
+    else MI_MX_LAUNCH_(2);
+  }
+#undef MI_MX_LAUNCH_
+  MI_CHECK_LAUNCH(c.blk ? "mi_blockfp8_quantize launch" : "mi_mxfp8_quantize launch");
   return MI_OK;
+}
+
+// The argument check of every producer, on the [rows, cols] space that is quantised.
+static int quant_check(const QuantCall& c, const void* x, int64_t rows, int64_t cols) {
+  const char* who = c.who;
+  MI_CHECK_ARG(x, "%s: null input", who);
+  MI_CHECK_ARG((c.y_row && c.s_row) || (c.y_colT && c.s_colT), "%s: need (y_row,s_row) and/or (y_colT,s_colT)", who);
+  MI_CHECK_ARG((!c.y_row) == (!c.s_row) && (!c.y_colT) == (!c.s_colT), "%s: data and scale pointers must pair up", who);
+  MI_CHECK_ARG(rows >= 0 && cols >= 0 && rows % 32 == 0 && cols % 32 == 0,
+               "%s: rows (%lld) and cols (%lld) must be multiples of 32", who, (long long)rows, (long long)cols);
+  MI_CHECK_ARG(rows < (1LL << 31) && cols < (1LL << 31), "%s: shape too large", who);
+  MI_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)c.y_row % 8) == 0 && ((uintptr_t)c.y_colT % 8) == 0 &&
+                   ((uintptr_t)c.s_row % 8) == 0 && ((uintptr_t)c.s_colT % 8) == 0, "%s: misaligned pointer", who);
+  MI_CHECK_ARG(c.fmt == MI_FMT_E4M3 || c.fmt == MI_FMT_E5M2, "%s: bad fmt %d", who, c.fmt);
+  MI_CHECK_ARG(c.blk ? (c.gran == 1 || c.gran == 2) : c.gran == 0, "%s: block_dim %d must be 1 (1x128 blocks) or 2 (128x128 blocks)", who,
+               c.gran);
+  MI_CHECK_ARG(c.eps >= 0.0f, "%s: amax_epsilon must be non-negative", who);
+  return MI_OK;
+}
+
+// ---- one body per producer: its own checks and its launch ----
+static int quant_plain(const QuantCall& c, const void* x, float* colsum, int64_t rows, int64_t cols, int64_t ld_rows) {
+  int rc = quant_check(c, x, rows, cols);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(ld_rows >= rows && ld_rows % 8 == 0 && ld_rows < (1LL << 31), "%s: ld_rows (%lld) must be >= rows and a multiple of 8", c.who,
+               (long long)ld_rows);
+  // a 128 x 128 block is a tile of THIS call: as a row-block of a larger operand (ld_rows > rows) the tensor has to begin on one of the
+  // operand's block rows, or its blocks are not the operand's.  The operand's buffers are at least 128-byte aligned, so the row
+  // offset modulo 128 shows in the two pointers that advance by one byte per row.
+  MI_CHECK_ARG(c.gran != 2 || ld_rows == rows || (((uintptr_t)c.s_row % 128) == 0 && ((uintptr_t)c.y_colT % 128) == 0),
+               "%s: with block_dim 2 a row-block destination must start on a multiple of 128 rows of its operand", c.who);
+  return launch_mx<0>(c, x, nullptr, nullptr, colsum, rows, cols, ld_rows);
+}
+
+static int quant_norm(const QuantCall& c, const void* x, const float* rstd, const void* gamma, int64_t rows, int64_t cols) {
+  int rc = quant_check(c, x, rows, cols);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(rstd && gamma && ((uintptr_t)gamma % 16) == 0, "%s: rstd / gamma missing or misaligned", c.who);
+  return launch_mx<1>(c, x, gamma, rstd, nullptr, rows, cols);
+}
+
+static int quant_swiglu(const QuantCall& c, const void* h, int64_t rows, int64_t F) {
+  int rc = quant_check(c, h, rows, F);
+  if (rc != MI_OK) return rc;
+  return launch_mx<2>(c, h, nullptr, nullptr, nullptr, rows, F);
+}
+
+static int quant_dswiglu(const QuantCall& c, const void* h, const void* dact, float* colsum, int64_t rows, int64_t F) {
+  int rc = quant_check(c, h, rows, 2 * F);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(dact && ((uintptr_t)dact % 16) == 0, "%s: dact missing or misaligned", c.who);
+  return launch_mx<3>(c, h, dact, nullptr, colsum, rows, 2 * F);
+}
+
+static int quant_rope_bwd(const QuantCall& c, const void* dq, const void* dk, const void* dv, const float* cos_tab, const float* sin_tab,
+                          int64_t rows, int64_t seq, int n_q_heads, int n_kv_heads, int head_dim) {
+  MI_CHECK_ARG(!c.blk, "%s: RoPE backward has no block-scaled form", c.who);
+  MI_CHECK_ARG(head_dim == 128, "%s: head_dim %d not supported (128)", c.who, head_dim);
+  MI_CHECK_ARG(n_q_heads >= 1 && n_kv_heads >= 1 && seq >= 1, "%s: bad head counts / seq", c.who);
+  const int64_t W = (int64_t)(n_q_heads + 2 * n_kv_heads) * head_dim;
+  int rc = quant_check(c, dq, rows, W);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(dk && dv && cos_tab && sin_tab && ((uintptr_t)dk % 16) == 0 && ((uintptr_t)dv % 16) == 0 &&
+                   ((uintptr_t)cos_tab % 16) == 0 && ((uintptr_t)sin_tab % 16) == 0, "%s: null or misaligned input", c.who);
+  return launch_mx<4>(c, dq, dk, cos_tab, nullptr, rows, W, 0, dv, sin_tab, n_q_heads, n_kv_heads, (int)seq);
 }
 
 }  // namespace mi
 
-static int mx_common_check(const char* who, const void* x, const void* y_row, const void* s_row, const void* y_colT,
-                           const void* s_colT, int64_t rows, int64_t cols, int fmt) {
-  MI_CHECK_ARG(x, "%s: null input", who);
-  MI_CHECK_ARG((y_row && s_row) || (y_colT && s_colT), "%s: need (y_row,s_row) and/or (y_colT,s_colT)", who);
-  MI_CHECK_ARG((!y_row) == (!s_row) && (!y_colT) == (!s_colT), "%s: data and scale pointers must pair up", who);
-  MI_CHECK_ARG(rows >= 0 && cols >= 0 && rows % 32 == 0 && cols % 32 == 0,
-               "%s: rows (%lld) and cols (%lld) must be multiples of 32", who, (long long)rows, (long long)cols);
-  MI_CHECK_ARG(rows < (1LL << 31) && cols < (1LL << 31), "%s: shape too large", who);
-  MI_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)y_row % 8) == 0 && ((uintptr_t)y_colT % 8) == 0 &&
-                   ((uintptr_t)s_row % 8) == 0 && ((uintptr_t)s_colT % 8) == 0, "%s: misaligned pointer", who);
-  MI_CHECK_ARG(fmt == MI_FMT_E4M3 || fmt == MI_FMT_E5M2, "%s: bad fmt %d", who, fmt);
-  return MI_OK;
-}
-
-#define MI_MX_DISPATCH(PRE, x, a16, a32, cs, rows, cols) mi::launch_mx<PRE>(fmt, x, a16, a32, y_row, s_row, y_colT, s_colT, cs, rows, cols, stream)
+// ---- the C entry points (include/mi_fp8.h): mi_mxfp8_* with one E8M0 scale per 32 elements, mi_blockfp8_* the same producers with
+// 1 x 128 (block_dim 1) or 128 x 128 (block_dim 2) power-of-two scales ----
+#define MI_MX(name) {name, false, 0, 0.0f, y_row, s_row, y_colT, s_colT, fmt, stream}
+#define MI_BLK(name) {name, true, block_dim, amax_epsilon, y_row, s_row, y_colT, s_colT, fmt, stream}
 
 extern "C" int mi_mxfp8_quantize(const void* x_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT,
                                  int64_t rows, int64_t cols, int fmt, void* stream) {
-  int rc = mx_common_check("mi_mxfp8_quantize", x_bf16, y_row, s_row, y_colT, s_colT, rows, cols, fmt);
-  if (rc != MI_OK) return rc;
-  if (rows == 0 || cols == 0) return MI_OK;
-  return MI_MX_DISPATCH(0, x_bf16, nullptr, nullptr, nullptr, rows, cols);
+  return mi::quant_plain(MI_MX("mi_mxfp8_quantize"), x_bf16, nullptr, rows, cols, rows);
 }
 
 extern "C" int mi_mxfp8_quantize_ex(const void* x_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT, float* colsum,
                                     int64_t rows, int64_t cols, int64_t ld_rows, int fmt, void* stream) {
-  int rc = mx_common_check("mi_mxfp8_quantize_ex", x_bf16, y_row, s_row, y_colT, s_colT, rows, cols, fmt);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(ld_rows >= rows && ld_rows % 8 == 0 && ld_rows < (1LL << 31), "mi_mxfp8_quantize_ex: ld_rows (%lld) must be >= rows and a multiple of 8",
-               (long long)ld_rows);
-  if (rows == 0 || cols == 0) return MI_OK;
-  return mi::launch_mx<0>(fmt, x_bf16, nullptr, nullptr, y_row, s_row, y_colT, s_colT, colsum, rows, cols, stream, ld_rows);
+  return mi::quant_plain(MI_MX("mi_mxfp8_quantize_ex"), x_bf16, colsum, rows, cols, ld_rows);
 }
 
 extern "C" int mi_mxfp8_norm_quantize(const void* x_bf16, const float* rstd, const void* gamma_bf16, void* y_row, void* s_row,
                                       void* y_colT, void* s_colT, int64_t rows, int64_t cols, int fmt, void* stream) {
-  int rc = mx_common_check("mi_mxfp8_norm_quantize", x_bf16, y_row, s_row, y_colT, s_colT, rows, cols, fmt);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(rstd && gamma_bf16 && ((uintptr_t)gamma_bf16 % 16) == 0, "mi_mxfp8_norm_quantize: rstd / gamma missing or misaligned");
-  if (rows == 0 || cols == 0) return MI_OK;
-  return MI_MX_DISPATCH(1, x_bf16, gamma_bf16, rstd, nullptr, rows, cols);
+  return mi::quant_norm(MI_MX("mi_mxfp8_norm_quantize"), x_bf16, rstd, gamma_bf16, rows, cols);
 }
 
 extern "C" int mi_mxfp8_swiglu_quantize(const void* h_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT, int64_t rows,
                                         int64_t F, int fmt, void* stream) {
-  int rc = mx_common_check("mi_mxfp8_swiglu_quantize", h_bf16, y_row, s_row, y_colT, s_colT, rows, F, fmt);
-  if (rc != MI_OK) return rc;
-  if (rows == 0 || F == 0) return MI_OK;
-  return MI_MX_DISPATCH(2, h_bf16, nullptr, nullptr, nullptr, rows, F);
+  return mi::quant_swiglu(MI_MX("mi_mxfp8_swiglu_quantize"), h_bf16, rows, F);
 }
 
 extern "C" int mi_mxfp8_dswiglu_quantize(const void* h_bf16, const void* dact_bf16, void* y_row, void* s_row, void* y_colT,
                                          void* s_colT, float* colsum, int64_t rows, int64_t F, int fmt, void* stream) {
-  int rc = mx_common_check("mi_mxfp8_dswiglu_quantize", h_bf16, y_row, s_row, y_colT, s_colT, rows, 2 * F, fmt);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(dact_bf16 && ((uintptr_t)dact_bf16 % 16) == 0, "mi_mxfp8_dswiglu_quantize: dact missing or misaligned");
-  if (rows == 0 || F == 0) return MI_OK;
-  return MI_MX_DISPATCH(3, h_bf16, dact_bf16, nullptr, colsum, rows, 2 * F);
+  return mi::quant_dswiglu(MI_MX("mi_mxfp8_dswiglu_quantize"), h_bf16, dact_bf16, colsum, rows, F);
 }
 
 extern "C" int mi_mxfp8_rope_bwd_quantize(const void* dq_bf16, const void* dk_bf16, const void* dv_bf16, const float* cos_tab,
                                           const float* sin_tab, void* y_row, void* s_row, void* y_colT, void* s_colT, int64_t rows,
                                           int64_t seq, int n_q_heads, int n_kv_heads, int head_dim, int fmt, void* stream) {
-  MI_CHECK_ARG(head_dim == 128, "mi_mxfp8_rope_bwd_quantize: head_dim %d not supported (128)", head_dim);
-  MI_CHECK_ARG(n_q_heads >= 1 && n_kv_heads >= 1 && seq >= 1, "mi_mxfp8_rope_bwd_quantize: bad head counts / seq");
-  const int64_t W = (int64_t)(n_q_heads + 2 * n_kv_heads) * head_dim;
-  int rc = mx_common_check("mi_mxfp8_rope_bwd_quantize", dq_bf16, y_row, s_row, y_colT, s_colT, rows, W, fmt);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(dk_bf16 && dv_bf16 && cos_tab && sin_tab && ((uintptr_t)dk_bf16 % 16) == 0 && ((uintptr_t)dv_bf16 % 16) == 0 &&
-                   ((uintptr_t)cos_tab % 16) == 0 && ((uintptr_t)sin_tab % 16) == 0, "mi_mxfp8_rope_bwd_quantize: null or misaligned input");
-  if (rows == 0) return MI_OK;
-  return mi::launch_mx<4>(fmt, dq_bf16, dk_bf16, cos_tab, y_row, s_row, y_colT, s_colT, nullptr, rows, W, stream, 0, dv_bf16, sin_tab,
-                          n_q_heads, n_kv_heads, (int)seq);
+  return mi::quant_rope_bwd(MI_MX("mi_mxfp8_rope_bwd_quantize"), dq_bf16, dk_bf16, dv_bf16, cos_tab, sin_tab, rows, seq, n_q_heads,
+                            n_kv_heads, head_dim);
 }
-
-// ---- Float8BlockScaling: the same kernel with 1 x 128 (block_dim 1) or 128 x 128 (block_dim 2) power-of-two scales ----
-static int blk_common_check(const char* who, const void* x, const void* y_row, const void* s_row, const void* y_colT,
-                            const void* s_colT, int64_t rows, int64_t cols, int fmt, int block_dim, float amax_epsilon) {
-  int rc = mx_common_check(who, x, y_row, s_row, y_colT, s_colT, rows, cols, fmt);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(block_dim == 1 || block_dim == 2, "%s: block_dim %d must be 1 (1x128 blocks) or 2 (128x128 blocks)", who, block_dim);
-  MI_CHECK_ARG(amax_epsilon >= 0.0f, "%s: amax_epsilon must be non-negative", who);
-  return MI_OK;
-}
-
-#define MI_BLK_DISPATCH(PRE, x, a16, a32, cs, rows, cols, ld)                                                                       \
-  (block_dim == 1 ? mi::launch_mx<PRE, 1>(fmt, x, a16, a32, y_row, s_row, y_colT, s_colT, cs, rows, cols, stream, ld, nullptr, nullptr, 0, \
-                                          0, 0, amax_epsilon)                                                                       \
-                  : mi::launch_mx<PRE, 2>(fmt, x, a16, a32, y_row, s_row, y_colT, s_colT, cs, rows, cols, stream, ld, nullptr, nullptr, 0, \
-                                          0, 0, amax_epsilon))
 
 extern "C" int mi_blockfp8_quantize_ex(const void* x_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT, float* colsum,
                                        int64_t rows, int64_t cols, int64_t ld_rows, int fmt, int block_dim, float amax_epsilon,
                                        void* stream) {
-  int rc = blk_common_check("mi_blockfp8_quantize_ex", x_bf16, y_row, s_row, y_colT, s_colT, rows, cols, fmt, block_dim, amax_epsilon);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(ld_rows >= rows && ld_rows % 8 == 0 && ld_rows < (1LL << 31),
-               "mi_blockfp8_quantize_ex: ld_rows (%lld) must be >= rows and a multiple of 8", (long long)ld_rows);
-  // a 128 x 128 block is a tile of THIS call: as a row-block of a larger operand (ld_rows > rows) the tensor has to begin on one of the
-  // operand's block rows, or its blocks are not the operand's.  The operand's buffers are at least 128-byte aligned, so the row
-  // offset modulo 128 shows in the two pointers that advance by one byte per row.
-  MI_CHECK_ARG(block_dim != 2 || ld_rows == rows || (((uintptr_t)s_row % 128) == 0 && ((uintptr_t)y_colT % 128) == 0),
-               "mi_blockfp8_quantize_ex: with block_dim 2 a row-block destination must start on a multiple of 128 rows of its operand");
-  if (rows == 0 || cols == 0) return MI_OK;
-  return MI_BLK_DISPATCH(0, x_bf16, nullptr, nullptr, colsum, rows, cols, ld_rows);
+  return mi::quant_plain(MI_BLK("mi_blockfp8_quantize_ex"), x_bf16, colsum, rows, cols, ld_rows);
 }
 
 extern "C" int mi_blockfp8_norm_quantize(const void* x_bf16, const float* rstd, const void* gamma_bf16, void* y_row, void* s_row,
                                          void* y_colT, void* s_colT, int64_t rows, int64_t cols, int fmt, int block_dim,
                                          float amax_epsilon, void* stream) {
-  int rc = blk_common_check("mi_blockfp8_norm_quantize", x_bf16, y_row, s_row, y_colT, s_colT, rows, cols, fmt, block_dim, amax_epsilon);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(rstd && gamma_bf16 && ((uintptr_t)gamma_bf16 % 16) == 0, "mi_blockfp8_norm_quantize: rstd / gamma missing or misaligned");
-  if (rows == 0 || cols == 0) return MI_OK;
-  return MI_BLK_DISPATCH(1, x_bf16, gamma_bf16, rstd, nullptr, rows, cols, 0);
+  return mi::quant_norm(MI_BLK("mi_blockfp8_norm_quantize"), x_bf16, rstd, gamma_bf16, rows, cols);
 }
 
 extern "C" int mi_blockfp8_swiglu_quantize(const void* h_bf16, void* y_row, void* s_row, void* y_colT, void* s_colT, int64_t rows,
                                            int64_t F, int fmt, int block_dim, float amax_epsilon, void* stream) {
-  int rc = blk_common_check("mi_blockfp8_swiglu_quantize", h_bf16, y_row, s_row, y_colT, s_colT, rows, F, fmt, block_dim, amax_epsilon);
-  if (rc != MI_OK) return rc;
-  if (rows == 0 || F == 0) return MI_OK;
-  return MI_BLK_DISPATCH(2, h_bf16, nullptr, nullptr, nullptr, rows, F, 0);
+  return mi::quant_swiglu(MI_BLK("mi_blockfp8_swiglu_quantize"), h_bf16, rows, F);
 }
 
 extern "C" int mi_blockfp8_dswiglu_quantize(const void* h_bf16, const void* dact_bf16, void* y_row, void* s_row, void* y_colT,
                                             void* s_colT, float* colsum, int64_t rows, int64_t F, int fmt, int block_dim,
                                             float amax_epsilon, void* stream) {
-  int rc = blk_common_check("mi_blockfp8_dswiglu_quantize", h_bf16, y_row, s_row, y_colT, s_colT, rows, 2 * F, fmt, block_dim,
-                            amax_epsilon);
-  if (rc != MI_OK) return rc;
-  MI_CHECK_ARG(dact_bf16 && ((uintptr_t)dact_bf16 % 16) == 0, "mi_blockfp8_dswiglu_quantize: dact missing or misaligned");
-  if (rows == 0 || F == 0) return MI_OK;
-  return MI_BLK_DISPATCH(3, h_bf16, dact_bf16, nullptr, colsum, rows, 2 * F, 0);
+  return mi::quant_dswiglu(MI_BLK("mi_blockfp8_dswiglu_quantize"), h_bf16, dact_bf16, colsum, rows, F);
 }

@@ -342,25 +342,41 @@ class _MXQ:
     def __init__(self, fmt_f: int, fmt_b: int):
         self.fmt_f, self.fmt_b = fmt_f, fmt_b
 
+    # -- the two hooks of a subclass with another scaling granularity (_BlockQ) --
+    def _gran(self, role: str):
+        """(block dim, amax_epsilon) of `role` ("x": input, "w": weight, "grad": grad_output), or None: MX's 32-element blocks."""
+        return None
+
+    def _part_rows(self) -> int:
+        """The row multiple at which a weight part can be quantised into its row-block of the operand, without concatenation."""
+        return 32
+
+    def _plain(self, role: str, x, fmt: int, **kw):
+        """The plain quantiser at the granularity of `role`, through the public pair of ops."""
+        gran = self._gran(role)
+        if gran is None:
+            return ops.mxfp8_quantize(x, fmt, **kw)
+        return ops.blockfp8_quantize(x, fmt, gran[0], amax_epsilon=gran[1], **kw)
+
     def quantize(self, x2, g: int, want_t: bool, norm=None):
         if norm is None:
-            q = ops.mxfp8_quantize(x2, self.fmt_f, rowwise=True, colwise=want_t)
+            q = self._plain("x", x2, self.fmt_f, rowwise=True, colwise=want_t)
         else:
-            q = ops.mxfp8_norm_quantize(x2, norm[0], norm[1], self.fmt_f, rowwise=True, colwise=want_t)
+            q = ops._norm_quantize(x2, norm[0], norm[1], self.fmt_f, True, want_t, self._gran("x"))
         return q[:2], q[2:]
 
     def swiglu(self, h, g: int, want_t: bool, bias):
         assert bias is None
-        q = ops.mxfp8_swiglu_quantize(h, self.fmt_f, rowwise=True, colwise=want_t)
+        q = ops._swiglu_quantize(h, self.fmt_f, True, want_t, self._gran("x"))
         return q[:2], q[2:]
 
     def quantize_grad(self, g2, g: int, want_y: bool, want_t: bool, colsum: bool = False):
-        q = ops.mxfp8_quantize(g2, self.fmt_b, rowwise=want_y, colwise=want_t, want_colsum=colsum)
+        q = self._plain("grad", g2, self.fmt_b, rowwise=want_y, colwise=want_t, want_colsum=colsum)
         return q[:2], q[2:4], q[4] if colsum else None
 
     def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
         assert bias is None
-        q = ops.mxfp8_dswiglu_quantize(h, dact, self.fmt_b, rowwise=want_y, colwise=want_t, want_colsum=colsum)
+        q = ops._dswiglu_quantize(h, dact, self.fmt_b, want_y, want_t, colsum, self._gran("grad"))
         return q[:2], q[2:4], q[4]
 
     def offer(self, handoff: DyHandoff, g: int, want_y: bool, want_t: bool) -> None:
@@ -380,23 +396,22 @@ class _MXQ:
         return flat[:2], flat[2:]
 
     def quantize_weights(self, weights, ns, N: int, K: int, dev, g: int, want_t: bool):
-        """Every part is quantised straight into its row-block of the operand's buffers (mi_mxfp8_quantize_ex), no bf16
-        concatenation -- unless a part is not a multiple of 32 rows."""
+        """Every part is quantised straight into its row-block of the operand's buffers (mi_mxfp8_quantize_ex / mi_blockfp8_quantize_ex),
+        no bf16 concatenation -- unless a part's rows are no multiple of _part_rows().  One launch per part emits both copies."""
         fmt = self.fmt_f
         ws_ = [(w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous() for w in weights]
         if len(ws_) == 1:
-            return ops.mxfp8_quantize(ws_[0], fmt, rowwise=True, colwise=want_t)
-        if any(n % 32 for n in ns):
-            return ops.mxfp8_quantize(torch.cat(ws_, 0), fmt, rowwise=True, colwise=want_t)
+            return self._plain("w", ws_[0], fmt, rowwise=True, colwise=want_t)
+        if any(n % self._part_rows() for n in ns):
+            return self._plain("w", torch.cat(ws_, 0), fmt, rowwise=True, colwise=want_t)
         w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
         sc = torch.empty((K // 32, N), dtype=torch.uint8, device=dev)
         wt8 = torch.empty((K, N), dtype=torch.uint8, device=dev) if want_t else None
         sct = torch.empty((N // 32, K), dtype=torch.uint8, device=dev) if want_t else None
         r = 0
         for w, n in zip(ws_, ns):
-            ops.mxfp8_quantize(w, fmt, rowwise=True, colwise=want_t,
-                               out=(w8[r:r + n], sc[:, r:r + n], wt8[:, r:r + n] if want_t else None,
-                                    sct[r // 32:(r + n) // 32] if want_t else None))
+            self._plain("w", w, fmt, rowwise=True, colwise=want_t,
+                        out=(w8[r:r + n], sc[:, r:r + n], wt8[:, r:r + n] if want_t else None, sct[r // 32:(r + n) // 32] if want_t else None))
             r += n
         return w8, sc, wt8, sct
 
@@ -428,34 +443,16 @@ class _BlockQ(_MXQ):
         super().__init__(fmt_f, fmt_b)
         self.recipe = recipe
 
-    def quantize(self, x2, g: int, want_t: bool, norm=None):
+    def _gran(self, role: str):
         r = self.recipe
-        dim, eps = r.x_block_scaling_dim, r.fp8_quant_fwd_inp.amax_epsilon
-        if norm is None:
-            q = ops.blockfp8_quantize(x2, self.fmt_f, dim, rowwise=True, colwise=want_t, amax_epsilon=eps)
-        else:
-            q = ops.blockfp8_norm_quantize(x2, norm[0], norm[1], self.fmt_f, dim, rowwise=True, colwise=want_t, amax_epsilon=eps)
-        return q[:2], q[2:]
+        if role == "x":
+            return r.x_block_scaling_dim, r.fp8_quant_fwd_inp.amax_epsilon
+        if role == "w":
+            return r.w_block_scaling_dim, r.fp8_quant_fwd_weight.amax_epsilon
+        return r.grad_block_scaling_dim, r.fp8_quant_bwd_grad.amax_epsilon
 
-    def swiglu(self, h, g: int, want_t: bool, bias):
-        assert bias is None
-        r = self.recipe
-        q = ops.blockfp8_swiglu_quantize(h, self.fmt_f, r.x_block_scaling_dim, rowwise=True, colwise=want_t,
-                                         amax_epsilon=r.fp8_quant_fwd_inp.amax_epsilon)
-        return q[:2], q[2:]
-
-    def quantize_grad(self, g2, g: int, want_y: bool, want_t: bool, colsum: bool = False):
-        r = self.recipe
-        q = ops.blockfp8_quantize(g2, self.fmt_b, r.grad_block_scaling_dim, rowwise=want_y, colwise=want_t, want_colsum=colsum,
-                                  amax_epsilon=r.fp8_quant_bwd_grad.amax_epsilon)
-        return q[:2], q[2:4], q[4] if colsum else None
-
-    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
-        assert bias is None
-        r = self.recipe
-        q = ops.blockfp8_dswiglu_quantize(h, dact, self.fmt_b, r.grad_block_scaling_dim, rowwise=want_y, colwise=want_t,
-                                          want_colsum=colsum, amax_epsilon=r.fp8_quant_bwd_grad.amax_epsilon)
-        return q[:2], q[2:4], q[4]
+    def _part_rows(self) -> int:  # with 128 x 128 blocks a part has to fill whole block rows; 1 x 128 blocks only need the layout's unit
+        return 128 if self.recipe.w_block_scaling_dim == 2 else 32
 
     def offer(self, handoff: DyHandoff, g: int, want_y: bool, want_t: bool) -> None:
         """Nothing: no DyHandoff producer has a block-scaled form.  RoPE backward and cross-entropy backward take their bf16 route
@@ -463,29 +460,6 @@ class _BlockQ(_MXQ):
 
     def taken(self, fp8, g: int):
         raise RuntimeError("Float8BlockScaling offers no DyHandoff, so no producer can have put FP8 copies into one")
-
-    def quantize_weights(self, weights, ns, N: int, K: int, dev, g: int, want_t: bool):
-        """Every part is quantised straight into its row-block of the operand's buffers, no bf16 concatenation -- unless a part's
-        rows are no multiple of the block's rows (128 for 128 x 128 blocks; 32, the layout's unit, for 1 x 128).  One launch per
-        part emits both copies; with 128 x 128 blocks they hold the same bytes under the same scales."""
-        r = self.recipe
-        fmt, dim, eps = self.fmt_f, r.w_block_scaling_dim, r.fp8_quant_fwd_weight.amax_epsilon
-        ws_ = [(w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous() for w in weights]
-        if len(ws_) == 1:
-            return ops.blockfp8_quantize(ws_[0], fmt, dim, rowwise=True, colwise=want_t, amax_epsilon=eps)
-        if any(n % (128 if dim == 2 else 32) for n in ns):
-            return ops.blockfp8_quantize(torch.cat(ws_, 0), fmt, dim, rowwise=True, colwise=want_t, amax_epsilon=eps)
-        w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
-        sc = torch.empty((K // 32, N), dtype=torch.uint8, device=dev)
-        wt8 = torch.empty((K, N), dtype=torch.uint8, device=dev) if want_t else None
-        sct = torch.empty((N // 32, K), dtype=torch.uint8, device=dev) if want_t else None
-        o = 0
-        for w, n in zip(ws_, ns):
-            ops.blockfp8_quantize(w, fmt, dim, rowwise=True, colwise=want_t, amax_epsilon=eps,
-                                  out=(w8[o:o + n], sc[:, o:o + n], wt8[:, o:o + n] if want_t else None,
-                                       sct[o // 32:(o + n) // 32] if want_t else None))
-            o += n
-        return w8, sc, wt8, sct
 
     def new_sink(self, weights, ns, N: int, K: int, dev, g: int):
         return None

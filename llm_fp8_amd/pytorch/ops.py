@@ -297,44 +297,7 @@ def mxfp8_quantize(x: torch.Tensor, fmt: int = E4M3, rowwise: bool = True, colwi
     `out`: the same four tensors as row-block views of a larger operand's buffers (rows r.. of [N,C] / columns r.. of
     [C/32,N] and [C,N] / rows r/32.. of [N/32,C]) -- x is then quantised in place as part of that operand.
     `want_colsum`: also returns the fp32 partial column sums [ceil(R/128), C] of x (for colsum_finish)."""
-    _dev(x)
-    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
-    R, C = x.shape
-    y_row = s_row = y_colT = s_colT = None
-    ld = R
-    if out is not None:
-        y_row, s_row, y_colT, s_colT = out
-        _dev(y_row, s_row, y_colT, s_colT)
-        assert (y_row is not None) == rowwise and (y_colT is not None) == colwise
-        if rowwise:
-            assert y_row.shape == (R, C) and y_row.is_contiguous() and s_row.shape == (C // 32, R) and s_row.stride(1) == 1
-            ld = s_row.stride(0)
-        if colwise:
-            assert y_colT.shape == (C, R) and y_colT.stride(1) == 1 and s_colT.shape == (R // 32, C) and s_colT.is_contiguous()
-            assert not rowwise or y_colT.stride(0) == ld
-            ld = y_colT.stride(0)
-    else:
-        if rowwise:
-            y_row = torch.empty((R, C), dtype=torch.uint8, device=x.device)
-            s_row = torch.empty((C // 32, R), dtype=torch.uint8, device=x.device)
-        if colwise:
-            y_colT = torch.empty((C, R), dtype=torch.uint8, device=x.device)
-            s_colT = torch.empty((R // 32, C), dtype=torch.uint8, device=x.device)
-    cs = torch.empty(((R + 127) // 128, C), dtype=torch.float32, device=x.device) if want_colsum else None
-    if out is None and not want_colsum:
-        fn, args = _lib.load().mi_mxfp8_quantize, (x.data_ptr(), _ptr(y_row), _ptr(s_row), _ptr(y_colT), _ptr(s_colT), R, C, fmt, _stream())
-    else:
-        fn, args = _lib.load().mi_mxfp8_quantize_ex, (x.data_ptr(), _ptr(y_row), _ptr(s_row), _ptr(y_colT), _ptr(s_colT), _ptr(cs),
-                                                      R, C, ld, fmt, _stream())
-    t = KernelTimer.active
-    if t is None:
-        rc = fn(*args)
-    else:
-        nb = R * C * (2 + (1 + 1 / 32) * (int(rowwise) + int(colwise)))
-        with t.span("mxfp8_quantize", f"{R}x{C}", float(R * C), float(nb)):
-            rc = fn(*args)
-    _lib.check(rc, "mi_mxfp8_quantize")
-    return (y_row, s_row, y_colT, s_colT, cs) if want_colsum else (y_row, s_row, y_colT, s_colT)
+    return _quantize(x, fmt, rowwise, colwise, out, want_colsum, None)
 
 
 def gemm_mxfp8(a8, sa, b8, sb, fmt_a: int = E4M3, fmt_b: int = E4M3, bias=None, out=None,
@@ -397,23 +360,10 @@ def mxfp8_rope_bwd_quantize(dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor
     _dev(dq, dk, dv, cos, sin)
     dq, dk, dv = (t.contiguous() for t in (dq, dk, dv))
     T, W = dq.shape[0], (n_q + 2 * n_kv) * head_dim
-    y_row = s_row = y_colT = s_colT = None
-    if rowwise:
-        y_row = torch.empty((T, W), dtype=torch.uint8, device=dq.device)
-        s_row = torch.empty((W // 32, T), dtype=torch.uint8, device=dq.device)
-    if colwise:
-        y_colT = torch.empty((W, T), dtype=torch.uint8, device=dq.device)
-        s_colT = torch.empty((T // 32, W), dtype=torch.uint8, device=dq.device)
-    args = (dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), cos.data_ptr(), sin.data_ptr(), _ptr(y_row), _ptr(s_row), _ptr(y_colT),
-            _ptr(s_colT), T, seq, n_q, n_kv, head_dim, fmt, _stream())
-    t = KernelTimer.active
-    if t is None:
-        rc = _lib.load().mi_mxfp8_rope_bwd_quantize(*args)
-    else:
-        with t.span("mxfp8_quantize", f"rope {T}x{W}", float(T * W), float(T * W * (2 + (1 + 1 / 32) * (int(rowwise) + int(colwise))))):
-            rc = _lib.load().mi_mxfp8_rope_bwd_quantize(*args)
-    _lib.check(rc, "mi_mxfp8_rope_bwd_quantize")
-    return y_row, s_row, y_colT, s_colT
+    q, _ = _q_out(T, W, dq.device, rowwise, colwise)
+    _q_call("rope", "rope_bwd_quantize", (dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), cos.data_ptr(), sin.data_ptr(), *map(_ptr, q),
+                                          T, seq, n_q, n_kv, head_dim, fmt), None, T, W, 2.0 * T * W, rowwise, colwise)
+    return q
 
 
 def _group_shapes(problems, mx: bool):
@@ -799,7 +749,25 @@ def rmsnorm_bwd(dy: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, gamma: to
     return (dx, colsum_finish(part, dgamma_dtype)) if finish else (dx, part)
 
 
-def _mx_alloc(R: int, C: int, dev, rowwise: bool, colwise: bool):
+# ---- The block-scaled quantisers: K7 and its fused producers, once for both families.  `gran` is None for MXFP8 (one E8M0 scale per
+# 32 elements) or (dim, amax_epsilon) for Float8BlockScaling: one power-of-two scale per 1 x 128 (dim 1) / 128 x 128 (dim 2) block,
+# stored as the block's E8M0 byte at every 32-group it covers -- the same tuples and operand layout, so gemm_mxfp8 reads either. ----
+def _q_out(R: int, C: int, dev, rowwise: bool, colwise: bool, out=None):
+    """(y_row, s_row, y_colT, s_colT) (None where not asked) and their leading dimension: fresh tensors, or `out` checked as
+    row-block views of a larger operand's buffers."""
+    if out is not None:
+        y_row, s_row, y_colT, s_colT = out
+        _dev(y_row, s_row, y_colT, s_colT)
+        assert (y_row is not None) == rowwise and (y_colT is not None) == colwise
+        ld = R
+        if rowwise:
+            assert y_row.shape == (R, C) and y_row.is_contiguous() and s_row.shape == (C // 32, R) and s_row.stride(1) == 1
+            ld = s_row.stride(0)
+        if colwise:
+            assert y_colT.shape == (C, R) and y_colT.stride(1) == 1 and s_colT.shape == (R // 32, C) and s_colT.is_contiguous()
+            assert not rowwise or y_colT.stride(0) == ld
+            ld = y_colT.stride(0)
+        return (y_row, s_row, y_colT, s_colT), ld
     y_row = s_row = y_colT = s_colT = None
     if rowwise:
         y_row = torch.empty((R, C), dtype=torch.uint8, device=dev)
@@ -807,71 +775,11 @@ def _mx_alloc(R: int, C: int, dev, rowwise: bool, colwise: bool):
     if colwise:
         y_colT = torch.empty((C, R), dtype=torch.uint8, device=dev)
         s_colT = torch.empty((R // 32, C), dtype=torch.uint8, device=dev)
-    return y_row, s_row, y_colT, s_colT
+    return (y_row, s_row, y_colT, s_colT), R
 
 
-def _mx_call(kind: str, fn, args, R: int, C: int, in_bytes: float, rowwise: bool, colwise: bool):
-    t = KernelTimer.active
-    if t is None:
-        rc = fn(*args)
-    else:
-        with t.span("mxfp8_quantize", f"{kind} {R}x{C}", float(R * C), in_bytes + R * C * (1 + 1 / 32) * (int(rowwise) + int(colwise))):
-            rc = fn(*args)
-    _lib.check(rc, f"mi_mxfp8_{kind}_quantize")
-
-
-def mxfp8_norm_quantize(x: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, fmt: int = E4M3, rowwise: bool = True,
-                        colwise: bool = True):
-    """K9 for MXFP8: quantises (x * rstd[:, None]) * gamma without materialising it.  Same outputs as mxfp8_quantize."""
-    _dev(x, rstd, gamma)
-    assert x.dtype == torch.bfloat16 and gamma.dtype == torch.bfloat16 and x.is_contiguous() and gamma.is_contiguous()
-    R, C = x.shape
-    out = _mx_alloc(R, C, x.device, rowwise, colwise)
-    _mx_call("norm", _lib.load().mi_mxfp8_norm_quantize,
-             (x.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), *[_ptr(o) for o in out], R, C, fmt, _stream()), R, C, 2.0 * R * C,
-             rowwise, colwise)
-    return out
-
-
-def mxfp8_swiglu_quantize(h: torch.Tensor, fmt: int = E4M3, rowwise: bool = True, colwise: bool = True):
-    """K10 for MXFP8: quantises silu(h[:, :F]) * h[:, F:] ([R, F])."""
-    _dev(h)
-    assert h.dtype == torch.bfloat16 and h.is_contiguous() and h.shape[1] % 2 == 0
-    R, F = h.shape[0], h.shape[1] // 2
-    out = _mx_alloc(R, F, h.device, rowwise, colwise)
-    _mx_call("swiglu", _lib.load().mi_mxfp8_swiglu_quantize, (h.data_ptr(), *[_ptr(o) for o in out], R, F, fmt, _stream()), R, F,
-             4.0 * R * F, rowwise, colwise)
-    return out
-
-
-def mxfp8_dswiglu_quantize(h: torch.Tensor, dact: torch.Tensor, fmt: int = E4M3, rowwise: bool = True, colwise: bool = True,
-                           want_colsum: bool = False):
-    """K10 backward for MXFP8: quantises dh = [dact*dsilu(g)*u | dact*silu(g)] ([R, 2F]); returns (..., colsum or None)."""
-    _dev(h, dact)
-    assert h.dtype == torch.bfloat16 and dact.dtype == torch.bfloat16 and h.is_contiguous() and dact.is_contiguous()
-    R, F2 = h.shape
-    F = F2 // 2
-    assert dact.shape == (R, F)
-    out = _mx_alloc(R, F2, h.device, rowwise, colwise)
-    cs = torch.empty(((R + 127) // 128, F2), dtype=torch.float32, device=h.device) if want_colsum else None
-    _mx_call("dswiglu", _lib.load().mi_mxfp8_dswiglu_quantize,
-             (h.data_ptr(), dact.data_ptr(), *[_ptr(o) for o in out], _ptr(cs), R, F, fmt, _stream()), R, F2, 6.0 * R * F,
-             rowwise, colwise)
-    return (*out, cs)
-
-
-# ---- Float8BlockScaling: the K7 kernel with 1 x 128 (dim 1) / 128 x 128 (dim 2) power-of-two scales.  Same tuples and the same
-# operand layout as the mxfp8_* functions above (the block's E8M0 byte at every 32-group it covers): gemm_mxfp8 reads them as is. ----
-def _blk_call(kind: str, name: str, args, R: int, C: int, in_bytes: float, rowwise: bool, colwise: bool):
-    fn = _lib.require(name, "Float8BlockScaling")
-    t = KernelTimer.active
-    if t is None:
-        rc = fn(*args)
-    else:
-        with t.span("blockfp8_quantize", f"{kind} {R}x{C}".strip(), float(R * C),
-                    in_bytes + R * C * (1 + 1 / 32) * (int(rowwise) + int(colwise))):
-            rc = fn(*args)
-    _lib.check(rc, name)
+def _q_colsum(R: int, C: int, dev, want: bool):
+    return torch.empty(((R + 127) // 128, C), dtype=torch.float32, device=dev) if want else None
 
 
 def _blk_dim(dim: int) -> int:
@@ -880,76 +788,112 @@ def _blk_dim(dim: int) -> int:
     return int(dim)
 
 
+def _q_call(kind: str, entry: str, args, gran, R: int, C: int, in_bytes: float, rowwise: bool, colwise: bool):
+    """mi_mxfp8_<entry>(*args, stream) or, under `gran`, mi_blockfp8_<entry>(*args, dim, amax_epsilon, stream), inside its timer span."""
+    if gran is None:
+        span, name = "mxfp8_quantize", "mi_mxfp8_" + entry
+        fn, args = getattr(_lib.load(), name), (*args, _stream())
+    else:
+        span, name = "blockfp8_quantize", "mi_blockfp8_" + entry
+        args = (*args, _blk_dim(gran[0]), float(gran[1]), _stream())
+        fn = _lib.require(name, "Float8BlockScaling")
+    t = KernelTimer.active
+    if t is None:
+        rc = fn(*args)
+    else:
+        with t.span(span, f"{kind} {R}x{C}".strip(), float(R * C), in_bytes + R * C * (1 + 1 / 32) * (int(rowwise) + int(colwise))):
+            rc = fn(*args)
+    _lib.check(rc, "mi_mxfp8_quantize" if name == "mi_mxfp8_quantize_ex" else name)  # (the plain MX form reports one name)
+
+
+def _quantize(x, fmt, rowwise, colwise, out, want_colsum, gran):
+    _dev(x)
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
+    R, C = x.shape
+    q, ld = _q_out(R, C, x.device, rowwise, colwise, out)
+    cs = _q_colsum(R, C, x.device, want_colsum)
+    if gran is None and out is None and not want_colsum:
+        entry, args = "quantize", (x.data_ptr(), *map(_ptr, q), R, C, fmt)
+    else:
+        entry, args = "quantize_ex", (x.data_ptr(), *map(_ptr, q), _ptr(cs), R, C, ld, fmt)
+    _q_call("", entry, args, gran, R, C, 2.0 * R * C, rowwise, colwise)
+    return (*q, cs) if want_colsum else q
+
+
+def _norm_quantize(x, rstd, gamma, fmt, rowwise, colwise, gran):
+    _dev(x, rstd, gamma)
+    assert x.dtype == torch.bfloat16 and gamma.dtype == torch.bfloat16 and x.is_contiguous() and gamma.is_contiguous()
+    R, C = x.shape
+    q, _ = _q_out(R, C, x.device, rowwise, colwise)
+    _q_call("norm", "norm_quantize", (x.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), *map(_ptr, q), R, C, fmt), gran, R, C,
+            2.0 * R * C, rowwise, colwise)
+    return q
+
+
+def _swiglu_quantize(h, fmt, rowwise, colwise, gran):
+    _dev(h)
+    assert h.dtype == torch.bfloat16 and h.is_contiguous() and h.shape[1] % 2 == 0
+    R, F = h.shape[0], h.shape[1] // 2
+    q, _ = _q_out(R, F, h.device, rowwise, colwise)
+    _q_call("swiglu", "swiglu_quantize", (h.data_ptr(), *map(_ptr, q), R, F, fmt), gran, R, F, 4.0 * R * F, rowwise, colwise)
+    return q
+
+
+def _dswiglu_quantize(h, dact, fmt, rowwise, colwise, want_colsum, gran):
+    _dev(h, dact)
+    assert h.dtype == torch.bfloat16 and dact.dtype == torch.bfloat16 and h.is_contiguous() and dact.is_contiguous()
+    R, F2 = h.shape
+    F = F2 // 2
+    assert dact.shape == (R, F)
+    q, _ = _q_out(R, F2, h.device, rowwise, colwise)
+    cs = _q_colsum(R, F2, h.device, want_colsum)
+    _q_call("dswiglu", "dswiglu_quantize", (h.data_ptr(), dact.data_ptr(), *map(_ptr, q), _ptr(cs), R, F, fmt), gran, R, F2,
+            6.0 * R * F, rowwise, colwise)
+    return (*q, cs)
+
+
+def mxfp8_norm_quantize(x: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, fmt: int = E4M3, rowwise: bool = True,
+                        colwise: bool = True):
+    """K9 for MXFP8: quantises (x * rstd[:, None]) * gamma without materialising it.  Same outputs as mxfp8_quantize."""
+    return _norm_quantize(x, rstd, gamma, fmt, rowwise, colwise, None)
+
+
+def mxfp8_swiglu_quantize(h: torch.Tensor, fmt: int = E4M3, rowwise: bool = True, colwise: bool = True):
+    """K10 for MXFP8: quantises silu(h[:, :F]) * h[:, F:] ([R, F])."""
+    return _swiglu_quantize(h, fmt, rowwise, colwise, None)
+
+
+def mxfp8_dswiglu_quantize(h: torch.Tensor, dact: torch.Tensor, fmt: int = E4M3, rowwise: bool = True, colwise: bool = True,
+                           want_colsum: bool = False):
+    """K10 backward for MXFP8: quantises dh = [dact*dsilu(g)*u | dact*silu(g)] ([R, 2F]); returns (..., colsum or None)."""
+    return _dswiglu_quantize(h, dact, fmt, rowwise, colwise, want_colsum, None)
+
+
 def blockfp8_quantize(x: torch.Tensor, fmt: int = E4M3, dim: int = 1, rowwise: bool = True, colwise: bool = True, out=None,
                       want_colsum: bool = False, amax_epsilon: float = 0.0):
     """mxfp8_quantize with one power-of-two scale per 1 x 128 block along the contraction axis (`dim` 1) or per 128 x 128 block
     (`dim` 2: y_colT is the byte transpose of y_row).  Same returns, same `out` row-block form (with `dim` 2 the row-block must
     start on a multiple of 128 rows of its operand), same `want_colsum`."""
-    _dev(x)
-    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
-    R, C = x.shape
-    ld = R
-    if out is not None:
-        y_row, s_row, y_colT, s_colT = out
-        _dev(y_row, s_row, y_colT, s_colT)
-        assert (y_row is not None) == rowwise and (y_colT is not None) == colwise
-        if rowwise:
-            assert y_row.shape == (R, C) and y_row.is_contiguous() and s_row.shape == (C // 32, R) and s_row.stride(1) == 1
-            ld = s_row.stride(0)
-        if colwise:
-            assert y_colT.shape == (C, R) and y_colT.stride(1) == 1 and s_colT.shape == (R // 32, C) and s_colT.is_contiguous()
-            assert not rowwise or y_colT.stride(0) == ld
-            ld = y_colT.stride(0)
-    else:
-        y_row, s_row, y_colT, s_colT = _mx_alloc(R, C, x.device, rowwise, colwise)
-    cs = torch.empty(((R + 127) // 128, C), dtype=torch.float32, device=x.device) if want_colsum else None
-    _blk_call("", "mi_blockfp8_quantize_ex",
-              (x.data_ptr(), _ptr(y_row), _ptr(s_row), _ptr(y_colT), _ptr(s_colT), _ptr(cs), R, C, ld, fmt, _blk_dim(dim),
-               float(amax_epsilon), _stream()), R, C, 2.0 * R * C, rowwise, colwise)
-    return (y_row, s_row, y_colT, s_colT, cs) if want_colsum else (y_row, s_row, y_colT, s_colT)
+    return _quantize(x, fmt, rowwise, colwise, out, want_colsum, (dim, amax_epsilon))
 
 
 def blockfp8_norm_quantize(x: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, fmt: int = E4M3, dim: int = 1,
                            rowwise: bool = True, colwise: bool = True, amax_epsilon: float = 0.0):
     """mxfp8_norm_quantize under block scaling: quantises (x * rstd[:, None]) * gamma without materialising it."""
-    _dev(x, rstd, gamma)
-    assert x.dtype == torch.bfloat16 and gamma.dtype == torch.bfloat16 and x.is_contiguous() and gamma.is_contiguous()
-    R, C = x.shape
-    out = _mx_alloc(R, C, x.device, rowwise, colwise)
-    _blk_call("norm", "mi_blockfp8_norm_quantize",
-              (x.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), *[_ptr(o) for o in out], R, C, fmt, _blk_dim(dim),
-               float(amax_epsilon), _stream()), R, C, 2.0 * R * C, rowwise, colwise)
-    return out
+    return _norm_quantize(x, rstd, gamma, fmt, rowwise, colwise, (dim, amax_epsilon))
 
 
 def blockfp8_swiglu_quantize(h: torch.Tensor, fmt: int = E4M3, dim: int = 1, rowwise: bool = True, colwise: bool = True,
                              amax_epsilon: float = 0.0):
     """mxfp8_swiglu_quantize under block scaling: quantises silu(h[:, :F]) * h[:, F:] ([R, F])."""
-    _dev(h)
-    assert h.dtype == torch.bfloat16 and h.is_contiguous() and h.shape[1] % 2 == 0
-    R, F = h.shape[0], h.shape[1] // 2
-    out = _mx_alloc(R, F, h.device, rowwise, colwise)
-    _blk_call("swiglu", "mi_blockfp8_swiglu_quantize",
-              (h.data_ptr(), *[_ptr(o) for o in out], R, F, fmt, _blk_dim(dim), float(amax_epsilon), _stream()), R, F, 4.0 * R * F,
-              rowwise, colwise)
-    return out
+    return _swiglu_quantize(h, fmt, rowwise, colwise, (dim, amax_epsilon))
 
 
 def blockfp8_dswiglu_quantize(h: torch.Tensor, dact: torch.Tensor, fmt: int = E4M3, dim: int = 1, rowwise: bool = True,
                               colwise: bool = True, want_colsum: bool = False, amax_epsilon: float = 0.0):
     """mxfp8_dswiglu_quantize under block scaling: quantises dh = [dact*dsilu(g)*u | dact*silu(g)] ([R, 2F]); returns
     (..., colsum or None)."""
-    _dev(h, dact)
-    assert h.dtype == torch.bfloat16 and dact.dtype == torch.bfloat16 and h.is_contiguous() and dact.is_contiguous()
-    R, F2 = h.shape
-    F = F2 // 2
-    assert dact.shape == (R, F)
-    out = _mx_alloc(R, F2, h.device, rowwise, colwise)
-    cs = torch.empty(((R + 127) // 128, F2), dtype=torch.float32, device=h.device) if want_colsum else None
-    _blk_call("dswiglu", "mi_blockfp8_dswiglu_quantize",
-              (h.data_ptr(), dact.data_ptr(), *[_ptr(o) for o in out], _ptr(cs), R, F, fmt, _blk_dim(dim), float(amax_epsilon),
-               _stream()), R, F2, 6.0 * R * F, rowwise, colwise)
-    return (*out, cs)
+    return _dswiglu_quantize(h, dact, fmt, rowwise, colwise, want_colsum, (dim, amax_epsilon))
 
 
 def _bshd_ok(t: torch.Tensor, D: int):
