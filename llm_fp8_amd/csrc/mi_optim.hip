@@ -4,6 +4,7 @@
 //   mi_sumsq_bf16   partial[b] = sum over block b's elements of g^2 (fp32), b < n_partials
 //   mi_adamw_bf16   torch.optim.AdamW semantics for bf16 parameters with bf16 exp_avg / exp_avg_sq, fp32 math
 #include "mi_common.h"
+#include <string>
 
 namespace mi {
 
@@ -119,13 +120,30 @@ __global__ __launch_bounds__(256) void adamw_kernel(uint16_t* __restrict__ p, co
   }
 }
 
-// ---- multi-tensor forms: ONE launch over every tensor of a parameter group.  `tab` [5, T] int64 on the device: rows of
-// p / g / exp_avg / exp_avg_sq addresses and element counts; `chunks` [nchunks] = (tensor index, chunk index inside it); a
-// workgroup owns one chunk of `chunk_elems` elements.  (A 3B model has ~280 parameter tensors: 2 x 280 launches per step,
-// most of them a few microseconds long, become 2.)
+// ---- multi-tensor forms: ONE launch over every tensor of a parameter group.  `chunks` [nchunks] = (tensor index, chunk index
+// inside it); a workgroup owns one chunk.  (A 3B model has ~280 parameter tensors: 2 x 280 launches per step, most of them a few
+// microseconds long, become 2.)
+// THE TABLE.  `tab` [rows, T] int64 on the device, one column per tensor; built by optim.py (`table_rows`, the same row numbers as
+// ROW_*), stated for callers in include/mi_fp8.h.  Every kernel below reads it through tab_at().
+//   0 p  1 g  2 exp_avg  3 exp_avg_sq  4 numel                                      -- all a kernel without sinks reads
+//   5 cols: 0 = no sink, the tensor's chunks are flat runs of chunk_elems elements (the walk of adamw_multi_kernel);
+//           > 0 = a [numel / cols, cols] weight with a sink, its chunks are 128 x 128 tiles, row-major over the tiles
+//   6..11, per-tensor sink (adamw_cast_multi_kernel):  6 y [rows, ld_y] or 0  7 yT [cols, ld_yT] or 0  8 ld_y  9 ld_yT
+//           10 const float* scale  11 float* amax
+//   6..11, MXFP8 sink (adamw_mxcast_multi_kernel):     6 y_row [rows, cols]  7 s_row [cols/32, ldr]  8 y_colT [cols, ldr]
+//           9 s_colT [rows/32, cols]  10 ldr = rows of the whole operand the tensor is a row-block of  11 unused;
+//           rows 6..9 point at the tensor's first row inside the operand's buffers
+//   12 ST = float: the fp32 master weight (rows 2, 3 are then fp32 too and p is output only)
+//   12, 13 SR = true (bf16 state, stochastic rounding): global index of the tensor's first element, tensor key
 struct ChunkRef {
   int tensor, chunk;
 };
+enum TabRow {
+  ROW_P, ROW_G, ROW_EXP_AVG, ROW_EXP_AVG_SQ, ROW_NUMEL, ROW_COLS,
+  ROW_Y, ROW_YT, ROW_LD_Y, ROW_LD_YT, ROW_SCALE, ROW_AMAX, ROW_MASTER, ROW_SR_KEY,
+  ROW_Y_ROW = ROW_Y, ROW_S_ROW, ROW_Y_COLT, ROW_S_COLT, ROW_LDR, ROW_SR_BASE = ROW_MASTER
+};
+__device__ __forceinline__ int64_t tab_at(const int64_t* __restrict__ tab, int T, TabRow row, int t) { return tab[(int64_t)row * T + t]; }
 
 __global__ __launch_bounds__(256) void sumsq_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
                                                           int chunk_elems, double* __restrict__ partial) {
@@ -135,8 +153,8 @@ __global__ __launch_bounds__(256) void sumsq_multi_kernel(const int64_t* __restr
   // (in fp32 the chunking moved the last bit of the norm in a few percent of the steps).  The kernel stays HBM-bound.
   __shared__ double s_red[4];
   const ChunkRef cr = chunks[blockIdx.x];
-  const uint16_t* g = reinterpret_cast<const uint16_t*>(tab[(int64_t)1 * T + cr.tensor]);
-  const int64_t n = tab[(int64_t)4 * T + cr.tensor];
+  const uint16_t* g = reinterpret_cast<const uint16_t*>(tab_at(tab, T, ROW_G, cr.tensor));
+  const int64_t n = tab_at(tab, T, ROW_NUMEL, cr.tensor);
   const int64_t lo = (int64_t)cr.chunk * chunk_elems, hi = min(n, lo + chunk_elems);
   const int tid = threadIdx.x;
   double acc0 = 0.0, acc1 = 0.0;
@@ -183,7 +201,7 @@ __global__ __launch_bounds__(256) void sumsq_multi_kernel(const int64_t* __restr
 }
 
 // ---- state type of the multi-tensor AdamW kernels.  ST = uint16_t: bf16 parameter, exp_avg and exp_avg_sq (torch's fused AdamW
-// layout; the weight is read from and written to p).  ST = float: fp32 exp_avg / exp_avg_sq and an fp32 MASTER weight (table row 12)
+// layout; the weight is read from and written to p).  ST = float: fp32 exp_avg / exp_avg_sq and an fp32 MASTER weight (ROW_MASTER)
 // that carries the update unrounded; p is then output only, p = RNE_bf16(master).  Vec8<ST> = one lane's 8 consecutive values.
 template <typename ST>
 struct Vec8;
@@ -251,11 +269,11 @@ struct SrCtx {
 template <>
 struct SrCtx<true> {
   u32 k0, k1, step, key4;
-  int64_t base;  // global index of the tensor's first element (table row 12)
+  int64_t base;  // global index of the tensor's first element
   __device__ __forceinline__ SrCtx(const AdamSrArgs& a, const int64_t* __restrict__ tab, int T, int t) {
     k0 = a.k0; k1 = a.k1; step = a.step;
-    base = tab[(int64_t)12 * T + t];
-    key4 = (u32)tab[(int64_t)13 * T + t] << 2;
+    base = tab_at(tab, T, ROW_SR_BASE, t);
+    key4 = (u32)tab_at(tab, T, ROW_SR_KEY, t) << 2;
   }
   // the four words of `stream` for the 8 elements [8 v, 8 v + 8)
   __device__ __forceinline__ void words(int64_t v, u32 stream, u32 (&w)[4]) const {
@@ -280,18 +298,18 @@ __device__ __forceinline__ u32 sr_pack_bf16x2(float lo, float hi, u32 word) {
 }
 
 // The tensor's addresses out of the table: `w` is what the update reads and writes at full state precision (p itself for bf16
-// state, the fp32 master of row 12 otherwise).
+// state, the fp32 master otherwise).
 template <typename ST>
 struct AdamPtrs {
   uint16_t* p;
   const uint16_t* g;
   ST *w, *m, *v;
   __device__ __forceinline__ AdamPtrs(const int64_t* __restrict__ tab, int T, int t) {
-    p = reinterpret_cast<uint16_t*>(tab[t]);
-    g = reinterpret_cast<const uint16_t*>(tab[(int64_t)1 * T + t]);
-    m = reinterpret_cast<ST*>(tab[(int64_t)2 * T + t]);
-    v = reinterpret_cast<ST*>(tab[(int64_t)3 * T + t]);
-    if constexpr (sizeof(ST) == 4) w = reinterpret_cast<ST*>(tab[(int64_t)12 * T + t]);
+    p = reinterpret_cast<uint16_t*>(tab_at(tab, T, ROW_P, t));
+    g = reinterpret_cast<const uint16_t*>(tab_at(tab, T, ROW_G, t));
+    m = reinterpret_cast<ST*>(tab_at(tab, T, ROW_EXP_AVG, t));
+    v = reinterpret_cast<ST*>(tab_at(tab, T, ROW_EXP_AVG_SQ, t));
+    if constexpr (sizeof(ST) == 4) w = reinterpret_cast<ST*>(tab_at(tab, T, ROW_MASTER, t));
     else w = p;
   }
   __device__ __forceinline__ bool aligned16() const {
@@ -398,10 +416,24 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restr
                                                           int chunk_elems, const float* __restrict__ grad_scale, AdamArgs a) {
   const ChunkRef cr = chunks[blockIdx.x];
   const AdamPtrs<uint16_t> t(tab, T, cr.tensor);
-  const int64_t n = tab[(int64_t)4 * T + cr.tensor];
+  const int64_t n = tab_at(tab, T, ROW_NUMEL, cr.tensor);
   const float gs = grad_scale ? *grad_scale : 1.0f;
   adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, SrCtx<false>(a, tab, T, cr.tensor), threadIdx.x);
 }
+
+// A lane's 8 x 8 block inside the chunk's 128 x 128 tile: wave w owns the 64 x 64 quadrant (w >> 1, w & 1), lane l its block
+// (l >> 3, l & 7).  (r0, c0) = the block's first element in the [rows, cols] weight; it may lie outside (ragged tiles).
+struct TileBlock {
+  int64_t rows, r0, c0;
+  __device__ __forceinline__ TileBlock(int64_t n, int64_t cols, int chunk, int tid) {
+    rows = n / cols;
+    const int tiles_c = (int)((cols + 127) >> 7);
+    const int lane = tid & 63, wave = tid >> 6;
+    const int tile_r = chunk / tiles_c, tile_c = chunk % tiles_c;
+    r0 = (int64_t)tile_r * 128 + (wave >> 1) * 64 + (lane >> 3) * 8;
+    c0 = (int64_t)tile_c * 128 + (wave & 1) * 64 + (lane & 7) * 8;
+  }
+};
 
 // AdamW + FP8 weight cast in one pass (the weight-cast hand-off): under delayed scaling the scale the NEXT
 // forward quantises a weight with is already final when the optimiser runs (the forward arena was updated at the end of this
@@ -409,10 +441,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restr
 // tile of the [rows, cols] weight (the tiling of cast_amax_kernel: 8 x 8 block per lane, in-register byte transpose): each
 // element is updated, rounded to bf16, stored -- and that ROUNDED value is quantised exactly as mi_cast_amax would
 // (y = sat(float(bf16) * scale), amax = max |bf16|), into y [rows, ld_y] and the transposed copy yT [cols, ld_yT].
-// Tensors without a sink (cols == 0) take the flat path of adamw_multi_kernel.  Table rows (int64 each, T columns):
-//   0 p  1 g  2 exp_avg  3 exp_avg_sq  4 numel  5 cols  6 y  7 yT  8 ld_y  9 ld_yT  10 scale ptr  11 amax ptr
-//   12 fp32 master weight (ST = float only: rows 2, 3 are then fp32 too and p is output only)
-//   SR = true (bf16 state, stochastic rounding): 12 global index of the tensor's first element  13 tensor key
+// Tensors without a sink (cols == 0) take the flat path of adamw_multi_kernel.  Table: the per-tensor rows of THE TABLE above.
 template <typename ST, bool SR = false>
 __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
                                                                int chunk_elems, const float* __restrict__ grad_scale,
@@ -420,28 +449,21 @@ __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __
   const ChunkRef cr = chunks[blockIdx.x];
   const AdamPtrs<ST> t(tab, T, cr.tensor);
   const SrCtx<SR> sr(a, tab, T, cr.tensor);
-  const int64_t n = tab[(int64_t)4 * T + cr.tensor];
-  const int64_t cols = tab[(int64_t)5 * T + cr.tensor];
+  const int64_t n = tab_at(tab, T, ROW_NUMEL, cr.tensor);
+  const int64_t cols = tab_at(tab, T, ROW_COLS, cr.tensor);
   const float gs = grad_scale ? *grad_scale : 1.0f;
-  const int tid = threadIdx.x;
-  if (cols == 0) {  // flat chunk (the walk of adamw_multi_kernel)
-    adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);
-    return;
-  }
+  const int tid = threadIdx.x, tensor = cr.tensor;
+  if (cols == 0) return adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);  // the walk of adamw_multi_kernel
   // tile of a weight with an FP8 sink
-  uint8_t* y = reinterpret_cast<uint8_t*>(tab[(int64_t)6 * T + cr.tensor]);
-  uint8_t* yT = reinterpret_cast<uint8_t*>(tab[(int64_t)7 * T + cr.tensor]);
-  const int64_t ld_y = tab[(int64_t)8 * T + cr.tensor], ld_yT = tab[(int64_t)9 * T + cr.tensor];
-  const float scale = *reinterpret_cast<const float*>(tab[(int64_t)10 * T + cr.tensor]);
-  float* amax_out = reinterpret_cast<float*>(tab[(int64_t)11 * T + cr.tensor]);
-  const int64_t rows = n / cols;
-  const int tiles_c = (int)((cols + 127) >> 7);
-  const int lane = tid & 63, wave = tid >> 6;
-  const int tile_r = cr.chunk / tiles_c, tile_c = cr.chunk % tiles_c;
-  const int64_t r0 = (int64_t)tile_r * 128 + (wave >> 1) * 64 + (lane >> 3) * 8;
-  const int64_t c0 = (int64_t)tile_c * 128 + (wave & 1) * 64 + (lane & 7) * 8;
+  uint8_t* y = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_Y, tensor));
+  uint8_t* yT = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_YT, tensor));
+  const int64_t ld_y = tab_at(tab, T, ROW_LD_Y, tensor), ld_yT = tab_at(tab, T, ROW_LD_YT, tensor);
+  const float scale = *reinterpret_cast<const float*>(tab_at(tab, T, ROW_SCALE, tensor));
+  float* amax_out = reinterpret_cast<float*>(tab_at(tab, T, ROW_AMAX, tensor));
+  const TileBlock b(n, cols, cr.chunk, tid);
+  const int64_t r0 = b.r0, c0 = b.c0;
   float amax = 0.0f;
-  if (r0 < rows && c0 < cols) {
+  if (r0 < b.rows && c0 < cols) {
     u32 lo[8], hi[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -464,12 +486,7 @@ __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __
 // E8M0 scale of a 32-element block comes from the block itself -- so the copies the NEXT forward needs (row-wise blocks for
 // fprop, column-wise blocks, stored transposed, for dgrad) can be emitted as soon as the weight is updated.  Same tile walk as
 // adamw_cast_multi_kernel (128 x 128 tile per workgroup, 8 x 8 block per lane); the quantisation of the ROUNDED bf16 weight is
-// mxfp8_quant_kernel's: both call mx_quant_rows / mx_quant_cols (mi_common.h).
-// Table rows (int64 each, T columns):
-//   0 p  1 g  2 exp_avg  3 exp_avg_sq  4 numel  5 cols (0 = no sink: flat path)  6 y_row  7 s_row  8 y_colT  9 s_colT
-//   10 ldr (rows of the whole operand the tensor is a row-block of)  11 unused  12 fp32 master weight (ST = float only)
-// y_row / s_row / y_colT / s_colT point at the tensor's first row inside the operand's buffers: y_row [rows, cols],
-// s_row [cols/32, ldr], y_colT [cols, ldr], s_colT [rows/32, cols].
+// mxfp8_quant_kernel's: both call mx_quant_rows / mx_quant_cols (mi_common.h).  Table: the MXFP8 rows of THE TABLE above.
 template <typename ST, bool SR = false>
 __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
                                                                  int chunk_elems, const float* __restrict__ grad_scale,
@@ -477,26 +494,19 @@ __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* 
   const ChunkRef cr = chunks[blockIdx.x];
   const AdamPtrs<ST> t(tab, T, cr.tensor);
   const SrCtx<SR> sr(a, tab, T, cr.tensor);
-  const int64_t n = tab[(int64_t)4 * T + cr.tensor];
-  const int64_t cols = tab[(int64_t)5 * T + cr.tensor];
+  const int64_t n = tab_at(tab, T, ROW_NUMEL, cr.tensor);
+  const int64_t cols = tab_at(tab, T, ROW_COLS, cr.tensor);
   const float gs = grad_scale ? *grad_scale : 1.0f;
-  const int tid = threadIdx.x;
-  if (cols == 0) {  // flat chunk (the walk of adamw_multi_kernel)
-    adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);
-    return;
-  }
-  uint8_t* y_row = reinterpret_cast<uint8_t*>(tab[(int64_t)6 * T + cr.tensor]);
-  uint8_t* s_row = reinterpret_cast<uint8_t*>(tab[(int64_t)7 * T + cr.tensor]);
-  uint8_t* y_colT = reinterpret_cast<uint8_t*>(tab[(int64_t)8 * T + cr.tensor]);
-  uint8_t* s_colT = reinterpret_cast<uint8_t*>(tab[(int64_t)9 * T + cr.tensor]);
-  const int64_t ldr = tab[(int64_t)10 * T + cr.tensor];
-  const int64_t rows = n / cols;
-  const int tiles_c = (int)((cols + 127) >> 7);
-  const int lane = tid & 63, wave = tid >> 6;
-  const int tile_r = cr.chunk / tiles_c, tile_c = cr.chunk % tiles_c;
-  const int64_t r0 = (int64_t)tile_r * 128 + (wave >> 1) * 64 + (lane >> 3) * 8;
-  const int64_t c0 = (int64_t)tile_c * 128 + (wave & 1) * 64 + (lane & 7) * 8;
-  const bool active = r0 < rows && c0 < cols;  // rows, cols multiples of 32: a 4-lane block group is all-active or all-inactive
+  const int tid = threadIdx.x, lane = tid & 63, tensor = cr.tensor;
+  if (cols == 0) return adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);  // the walk of adamw_multi_kernel
+  uint8_t* y_row = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_Y_ROW, tensor));
+  uint8_t* s_row = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_S_ROW, tensor));
+  uint8_t* y_colT = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_Y_COLT, tensor));
+  uint8_t* s_colT = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_S_COLT, tensor));
+  const int64_t ldr = tab_at(tab, T, ROW_LDR, tensor);
+  const TileBlock b(n, cols, cr.chunk, tid);
+  const int64_t r0 = b.r0, c0 = b.c0;
+  const bool active = r0 < b.rows && c0 < cols;  // rows, cols multiples of 32: a 4-lane block group is all-active or all-inactive
   float f[8][8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -569,94 +579,83 @@ static mi::AdamArgs make_adam_args(float lr, float beta1, float beta2, float eps
   return a;
 }
 
+// The argument check of the six multi-tensor entry points, before any launch.  `who` = the entry point (its __func__), for the
+// message.  The calls with a sink_kind (fp32 state, stochastic rounding: `empty_ok`) accept an empty chunk list and name chunk_elems
+// and sink_kind in messages of their own; the others have one message for every size.
+static int check_multi(const char* who, bool empty_ok, bool pointers, int n_tensors, int n_chunks, int chunk_elems, int64_t step,
+                       int sink_kind = 0) {
+  const bool chunk_ok = chunk_elems >= 8 && chunk_elems % 8 == 0;
+  MI_CHECK_ARG(pointers, "%s: null pointer", who);
+  MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= (empty_ok ? 0 : 1) && (empty_ok || chunk_ok) && step >= 1, "%s: bad sizes", who);
+  MI_CHECK_ARG(chunk_ok, "%s: chunk_elems must be a positive multiple of 8", who);
+  MI_CHECK_ARG(sink_kind == 0 || sink_kind == 1, "%s: sink_kind must be 0 (per-tensor FP8) or 1 (MXFP8)", who);
+  return MI_OK;
+}
+
+// One workgroup of 256 lanes per chunk; `tail` = the kernel's arguments after chunk_elems.  An empty chunk list (where the check
+// lets one through) is nothing to do.
+template <typename Kernel, typename... Tail>
+static int launch_multi(const char* who, Kernel kernel, const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks,
+                        int chunk_elems, void* stream, Tail... tail) {
+  if (n_chunks == 0) return MI_OK;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors, (const mi::ChunkRef*)chunks,
+                     chunk_elems, tail...);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MI_OK : mi::hip_fail(e, (std::string(who) + " launch").c_str());
+}
+
 extern "C" int mi_sumsq_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                                    double* partial, void* stream) {
-  MI_CHECK_ARG(table && chunks && partial, "mi_sumsq_bf16_multi: null pointer");
-  MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 1 && chunk_elems >= 8 && chunk_elems % 8 == 0, "mi_sumsq_bf16_multi: bad sizes");
-  hipLaunchKernelGGL(mi::sumsq_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
-                     (const mi::ChunkRef*)chunks, chunk_elems, partial);
-  MI_CHECK_LAUNCH("mi_sumsq_bf16_multi launch");
-  return MI_OK;
+  if (int rc = check_multi(__func__, false, table && chunks && partial, n_tensors, n_chunks, chunk_elems, 1)) return rc;
+  return launch_multi(__func__, mi::sumsq_multi_kernel, table, n_tensors, chunks, n_chunks, chunk_elems, stream, partial);
 }
 
 extern "C" int mi_adamw_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                                    const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                                    int64_t step, void* stream) {
-  MI_CHECK_ARG(table && chunks, "mi_adamw_bf16_multi: null pointer");
-  MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 1 && chunk_elems >= 8 && chunk_elems % 8 == 0 && step >= 1, "mi_adamw_bf16_multi: bad sizes");
-  hipLaunchKernelGGL(mi::adamw_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
-                     (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, make_adam_args(lr, beta1, beta2, eps, weight_decay, step));
-  MI_CHECK_LAUNCH("mi_adamw_bf16_multi launch");
-  return MI_OK;
+  if (int rc = check_multi(__func__, false, table && chunks, n_tensors, n_chunks, chunk_elems, step)) return rc;
+  return launch_multi(__func__, mi::adamw_multi_kernel, table, n_tensors, chunks, n_chunks, chunk_elems, stream, grad_scale,
+                      make_adam_args(lr, beta1, beta2, eps, weight_decay, step));
 }
 
 extern "C" int mi_adamw_cast_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                                         const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                                         int64_t step, void* stream) {
-  MI_CHECK_ARG(table && chunks, "mi_adamw_cast_bf16_multi: null pointer");
-  MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 1 && chunk_elems >= 8 && chunk_elems % 8 == 0 && step >= 1, "mi_adamw_cast_bf16_multi: bad sizes");
-  hipLaunchKernelGGL(mi::adamw_cast_multi_kernel<uint16_t>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
-                     (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, make_adam_args(lr, beta1, beta2, eps, weight_decay, step));
-  MI_CHECK_LAUNCH("mi_adamw_cast_bf16_multi launch");
-  return MI_OK;
+  if (int rc = check_multi(__func__, false, table && chunks, n_tensors, n_chunks, chunk_elems, step)) return rc;
+  return launch_multi(__func__, mi::adamw_cast_multi_kernel<uint16_t>, table, n_tensors, chunks, n_chunks, chunk_elems, stream, grad_scale,
+                      make_adam_args(lr, beta1, beta2, eps, weight_decay, step));
 }
 
 extern "C" int mi_adamw_mxcast_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                                           const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                                           int64_t step, void* stream) {
-  MI_CHECK_ARG(table && chunks, "mi_adamw_mxcast_bf16_multi: null pointer");
-  MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 1 && chunk_elems >= 8 && chunk_elems % 8 == 0 && step >= 1, "mi_adamw_mxcast_bf16_multi: bad sizes");
-  hipLaunchKernelGGL(mi::adamw_mxcast_multi_kernel<uint16_t>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
-                     (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, make_adam_args(lr, beta1, beta2, eps, weight_decay, step));
-  MI_CHECK_LAUNCH("mi_adamw_mxcast_bf16_multi launch");
-  return MI_OK;
+  if (int rc = check_multi(__func__, false, table && chunks, n_tensors, n_chunks, chunk_elems, step)) return rc;
+  return launch_multi(__func__, mi::adamw_mxcast_multi_kernel<uint16_t>, table, n_tensors, chunks, n_chunks, chunk_elems, stream, grad_scale,
+                      make_adam_args(lr, beta1, beta2, eps, weight_decay, step));
 }
 
 // fp32 optimiser state: the walks, the arithmetic and the FP8 emitters of the two kernels above, instantiated for an fp32 master
-// weight (table row 12) and fp32 moments.  sink_kind 0 = the per-tensor table layout, 1 = the MXFP8 one.
+// weight and fp32 moments.  sink_kind 0 = the per-tensor table layout, 1 = the MXFP8 one.
 extern "C" int mi_adamw_f32_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                                   const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                                   int64_t step, int sink_kind, void* stream) {
-  MI_CHECK_ARG(table && chunks, "mi_adamw_f32_multi: null pointer");
-  MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 0 && step >= 1, "mi_adamw_f32_multi: bad sizes");
-  MI_CHECK_ARG(chunk_elems >= 8 && chunk_elems % 8 == 0, "mi_adamw_f32_multi: chunk_elems must be a positive multiple of 8");
-  MI_CHECK_ARG(sink_kind == 0 || sink_kind == 1, "mi_adamw_f32_multi: sink_kind must be 0 (per-tensor FP8) or 1 (MXFP8)");
-  if (n_chunks == 0) return MI_OK;
-  const mi::AdamArgs a = make_adam_args(lr, beta1, beta2, eps, weight_decay, step);
-  if (sink_kind == 0)
-    hipLaunchKernelGGL(mi::adamw_cast_multi_kernel<float>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table,
-                       n_tensors, (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, a);
-  else
-    hipLaunchKernelGGL(mi::adamw_mxcast_multi_kernel<float>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table,
-                       n_tensors, (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, a);
-  MI_CHECK_LAUNCH("mi_adamw_f32_multi launch");
-  return MI_OK;
+  if (int rc = check_multi(__func__, true, table && chunks, n_tensors, n_chunks, chunk_elems, step, sink_kind)) return rc;
+  return launch_multi(__func__, sink_kind == 0 ? mi::adamw_cast_multi_kernel<float> : mi::adamw_mxcast_multi_kernel<float>, table, n_tensors,
+                      chunks, n_chunks, chunk_elems, stream, grad_scale, make_adam_args(lr, beta1, beta2, eps, weight_decay, step));
 }
 
-// bf16 state with stochastic rounding: the SR instantiations of the same two kernels (table rows 12, 13: element base, tensor key)
+// bf16 state with stochastic rounding: the SR instantiations of the same two kernels
 extern "C" int mi_adamw_sr_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                                       const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                                       int64_t step, int sink_kind, uint64_t seed, void* stream) {
-  MI_CHECK_ARG(table && chunks, "mi_adamw_sr_bf16_multi: null pointer");
-  MI_CHECK_ARG(n_tensors >= 1 && n_chunks >= 0 && step >= 1, "mi_adamw_sr_bf16_multi: bad sizes");
-  MI_CHECK_ARG(chunk_elems >= 8 && chunk_elems % 8 == 0, "mi_adamw_sr_bf16_multi: chunk_elems must be a positive multiple of 8");
-  MI_CHECK_ARG(sink_kind == 0 || sink_kind == 1, "mi_adamw_sr_bf16_multi: sink_kind must be 0 (per-tensor FP8) or 1 (MXFP8)");
-  if (n_chunks == 0) return MI_OK;
+  if (int rc = check_multi(__func__, true, table && chunks, n_tensors, n_chunks, chunk_elems, step, sink_kind)) return rc;
   mi::AdamSrArgs a;
   static_cast<mi::AdamArgs&>(a) = make_adam_args(lr, beta1, beta2, eps, weight_decay, step);
   a.k0 = (mi::u32)(seed & 0xFFFFFFFFull);
   a.k1 = (mi::u32)(seed >> 32);
   a.step = (mi::u32)((uint64_t)step & 0xFFFFFFFFull);
-  constexpr auto cast_sr = mi::adamw_cast_multi_kernel<uint16_t, true>;
-  constexpr auto mxcast_sr = mi::adamw_mxcast_multi_kernel<uint16_t, true>;
-  if (sink_kind == 0)
-    hipLaunchKernelGGL(cast_sr, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
-                       (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, a);
-  else
-    hipLaunchKernelGGL(mxcast_sr, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, n_tensors,
-                       (const mi::ChunkRef*)chunks, chunk_elems, grad_scale, a);
-  MI_CHECK_LAUNCH("mi_adamw_sr_bf16_multi launch");
-  return MI_OK;
+  return launch_multi(__func__, sink_kind == 0 ? mi::adamw_cast_multi_kernel<uint16_t, true> : mi::adamw_mxcast_multi_kernel<uint16_t, true>,
+                      table, n_tensors, chunks, n_chunks, chunk_elems, stream, grad_scale, a);
 }
 
 extern "C" int mi_sumsq_bf16(const void* g_bf16, int64_t n, float* partial, int n_partials, void* stream) {

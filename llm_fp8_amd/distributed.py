@@ -535,7 +535,7 @@ class ShardedFP8DP(GradArenaDP):
     def _gather_ops(self, sink):
         """The all-gathers of one operand as (dst, src) pairs plus the fix-ups to run once they have landed."""
         ops_, fix = [], []
-        mx = hasattr(sink, "sc")
+        mx = sink.kind == 1
         K = sink.w8.shape[1]
         for w, row_off, n in sink.parts:
             rows = n // self.world
@@ -598,7 +598,7 @@ class ShardedFP8DP(GradArenaDP):
             w.wait()
         for dst, tmp in fix:  # [world, R, rows] -> [R, world * rows]
             dst.view(dst.shape[0], self.world, tmp.shape[2]).copy_(tmp.permute(1, 0, 2))
-        if hasattr(sink, "w8t"):
+        if sink.kind == 0:
             ops.transpose_u8(sink.w8, out=sink.w8t)
         sink.stamp = stamp
 

@@ -13,7 +13,66 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .pytorch.module import stepped_tensor
+from .pytorch.module import MXWeightSink, WeightSink, stepped_tensor
+
+CHUNK = 65536  # elements per workgroup of the multi-tensor kernels (128 KiB of bf16)
+TILE = 128  # a sink tensor's chunks are TILE x TILE tiles of the weight matrix
+
+# Rows of the device table [rows, tensors] int64, the one contract between this file and the kernels.  include/mi_fp8.h states the
+# layout (mi_adamw_cast_bf16_multi ff.), csrc/mi_optim.hip's `TabRow` carries the same numbers.  Rows 6..11 are the sink's own
+# (WeightSink.table_rows / MXWeightSink.table_rows); 12 rows with bf16 state, 13 with fp32 state, 14 with stochastic rounding.
+ROW_P, ROW_G, ROW_EXP_AVG, ROW_EXP_AVG_SQ, ROW_NUMEL, ROW_COLS, ROW_SINK, ROW_SINK_END = 0, 1, 2, 3, 4, 5, 6, 12
+ROW_Y, ROW_YT = 6, 7  # per-tensor sink: the FP8 copy and its transpose (what MI_DEBUG_SINK masks off)
+ROW_MASTER = ROW_SR_BASE = 12  # fp32 state: the master weight | stochastic rounding: global index of the tensor's first element
+ROW_SR_KEY = 13
+
+
+def chunk_refs(sizes, shapes, sinks):
+    """(flat, cast) chunk lists [(tensor, chunk)] of one table: `flat` cuts every tensor into CHUNK elements; `cast` walks a tensor
+    with a sink in TILE x TILE tiles (row-major over the tiles) and leaves the others their flat chunks."""
+    flat, cast = [], []
+    for t, (n, shape, s) in enumerate(zip(sizes, shapes, sinks)):
+        own = [(t, c) for c in range((n + CHUNK - 1) // CHUNK)]
+        flat.extend(own)
+        if s is not None:
+            own = [(t, c) for c in range(((shape[0] + TILE - 1) // TILE) * ((shape[1] + TILE - 1) // TILE))]
+        cast.extend(own)
+    return flat, cast
+
+
+def table_rows(addrs, sizes, shapes, sinks, mode, sr_keys=None):
+    """The table as a list of rows.  `addrs`: per tensor the addresses of (p, grad, exp_avg, exp_avg_sq, master); `sinks`: per tensor
+    None or (sink, first row in the operand, rows); `mode`: "bf16" | "fp32" | "bf16_sr"; `sr_keys`: per tensor (key, element base)."""
+    rows = [[a[r] for a in addrs] for r in range(ROW_NUMEL)] + [list(sizes)] + [[0] * len(sizes) for _ in range(ROW_COLS, ROW_SINK_END)]
+    dbg = os.environ.get("MI_DEBUG_SINK", "full")  # tools/bench_adamw.py: mask the FP8 outputs off (timing only)
+    for t, (shape, s) in enumerate(zip(shapes, sinks)):
+        if s is None:
+            continue
+        sink, r0, _ = s
+        rows[ROW_COLS][t] = shape[1]
+        for r, x in zip(range(ROW_SINK, ROW_SINK_END), sink.table_rows(r0, shape[1])):
+            rows[r][t] = x
+        if sink.kind == 0 and dbg in ("none", "noT"):
+            rows[ROW_YT][t] = 0
+            if dbg == "none":
+                rows[ROW_Y][t] = 0
+    if mode == "fp32":
+        rows.append([a[4] for a in addrs])  # ROW_MASTER
+    elif mode == "bf16_sr":
+        for s, (_, base) in zip(sinks, sr_keys):
+            if s is not None and base % 8:
+                raise ValueError(f"ClippedAdamW: element base {base} of a weight with an FP8 sink must be a multiple of 8")
+        rows.append([base for _, base in sr_keys])  # ROW_SR_BASE
+        rows.append([key for key, _ in sr_keys])    # ROW_SR_KEY
+    return rows
+
+
+# (mode, the partition walks the cast list) -> (entry point for sink kind 0 / 1, the plan's chunk list, how many of (sink kind, seed)
+# follow `step` in the argument list, what to tell _lib.require where the entry point is younger than the ABI version)
+_LAUNCH = {("bf16", False): (("mi_adamw_bf16_multi",) * 2, "chunks", 0, None),
+           ("bf16", True): (("mi_adamw_cast_bf16_multi", "mi_adamw_mxcast_bf16_multi"), "chunks_cast", 0, None),
+           ("fp32", True): (("mi_adamw_f32_multi",) * 2, "chunks_cast", 1, "ClippedAdamW(state_dtype=torch.float32)"),
+           ("bf16_sr", True): (("mi_adamw_sr_bf16_multi",) * 2, "chunks_cast", 2, "ClippedAdamW(stochastic_rounding=True)")}
 
 
 class ClippedAdamW(torch.optim.Optimizer):
@@ -58,6 +117,7 @@ class ClippedAdamW(torch.optim.Optimizer):
         self.max_grad_norm = max_grad_norm
         self.state_dtype = state_dtype
         self._f32 = state_dtype == torch.float32
+        self._mode = "fp32" if self._f32 else "bf16_sr" if self._sr else "bf16"  # train.OPTIMIZER_STATES
         self._plans = {}
         self.last_grad_norm: Optional[torch.Tensor] = None
 
@@ -71,26 +131,31 @@ class ClippedAdamW(torch.optim.Optimizer):
                     out.append((group, p))
         return out
 
-    CHUNK = 65536  # elements per workgroup of the multi-tensor kernels (128 KiB of bf16)
+    CHUNK, TILE = CHUNK, TILE
 
-    TILE = 128  # a sink tensor's chunks are TILE x TILE tiles of the weight matrix (mi_adamw_cast_bf16_multi)
-
-    def _sink_of(self, p):
-        """(sink, row offset, rows) when the FP8 copies of this weight are kept current by the optimiser (module.WeightSink)."""
+    def _sink_of(self, p, cls=WeightSink):
+        """(sink, row offset, rows) when the FP8 copies of this weight are kept current by the optimiser: `cls` = module.WeightSink
+        (delayed scaling) or module.MXWeightSink."""
         if os.environ.get("LLM_FP8_AMD_NO_OPT_WCAST") == "1":  # the switch of module.weight_sinks_enabled: the forward casts
             return None
-        s = getattr(p, "_mi_fp8_sink", None)
+        s = getattr(p, cls.attr, None)
         sh = getattr(p, "_mi_shard_of", None)
         if sh is not None:  # a row shard of a master weight (distributed.ShardedFP8DP): rows [r0, r0 + n) of the full operand part
             full, sr0, sn = sh
-            fs = getattr(full, "_mi_fp8_sink", None)
+            fs = getattr(full, cls.attr, None)
             s = None if fs is None else (fs[0], fs[1] + sr0, sn)
         if s is None or not p.is_contiguous() or p.dim() != 2 or not self._aligned16(p):
             return None
         sink, r0, n = s
-        if n != p.shape[0] or sink.w8.shape[1] != p.shape[1] or p.shape[0] % 8 or p.shape[1] % 8:
+        u = cls.unit
+        if n != p.shape[0] or sink.w8.shape[1] != p.shape[1] or p.shape[0] % u or p.shape[1] % u:
+            return None
+        if cls is MXWeightSink and r0 % u:  # the E8M0 scales of the column blocks are per 32 rows of the OPERAND
             return None
         return s
+
+    def _mx_sink_of(self, p):
+        return self._sink_of(p, MXWeightSink)
 
     def _aligned16(self, p) -> bool:
         """The tile path of the *_cast kernels issues 16-byte loads / stores on the parameter, its gradient, both moments and
@@ -99,23 +164,6 @@ class ClippedAdamW(torch.optim.Optimizer):
         st = self.state.get(p, {})
         others = (p.grad, st.get("exp_avg"), st.get("exp_avg_sq"), st.get("master") if self._f32 else None)
         return p.data_ptr() % 16 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in others)
-
-    def _mx_sink_of(self, p):
-        """(sink, row offset, rows) when the MXFP8 copies of this weight are kept current by the optimiser (module.MXWeightSink)."""
-        if os.environ.get("LLM_FP8_AMD_NO_OPT_WCAST") == "1":
-            return None
-        s = getattr(p, "_mi_mx_sink", None)
-        sh = getattr(p, "_mi_shard_of", None)
-        if sh is not None:  # a row shard of a master weight (distributed.ShardedFP8DP)
-            full, sr0, sn = sh
-            fs = getattr(full, "_mi_mx_sink", None)
-            s = None if fs is None else (fs[0], fs[1] + sr0, sn)
-        if s is None or not p.is_contiguous() or p.dim() != 2 or not self._aligned16(p):
-            return None
-        sink, r0, n = s
-        if n != p.shape[0] or sink.w8.shape[1] != p.shape[1] or p.shape[0] % 32 or p.shape[1] % 32 or r0 % 32:
-            return None
-        return s
 
     def _sr_key(self, p):
         """(tensor key, global index of the first element) of the stochastic-rounding generator for `p`."""
@@ -130,78 +178,33 @@ class ClippedAdamW(torch.optim.Optimizer):
             raise ValueError(f"ClippedAdamW: _mi_sr_key {k!r}: the tensor key must be in [0, 2^30) and the element base >= 0")
         return key, base
 
-    def _plan(self, group_items, dev, mx=False):
-        """Device tables of one parameter group for the multi-tensor kernels.  The chunk lists only depend on the tensor sizes
-        (and on which tensors have an FP8 sink) and are built once; the address table is re-uploaded when an address changed
-        (gradients are new tensors every step, though the caching allocator usually hands back the same blocks)."""
+    def _plan(self, group_items, sinks, dev, mx=False):
+        """Device tables of one parameter group for the multi-tensor kernels; `sinks` = per tensor None or (sink, row offset, rows),
+        of the kind `mx` says.  The chunk lists only depend on the tensor sizes (and on which tensors have an FP8 sink) and are built
+        once; the address table is re-uploaded when an address changed (gradients are new tensors every step, though the caching
+        allocator usually hands back the same blocks)."""
         # one plan per PARTITION (the parameters of a group that share a step count), not per group: two partitions of one
         # group must not share address table / partial sums
         key = (id(group_items[0][0]), tuple(id(p) for _, p in group_items), mx)
         sizes = tuple(p.numel() for _, p in group_items)
-        sinks = tuple((self._mx_sink_of(p) if mx else self._sink_of(p)) for _, p in group_items)
+        shapes = [p.shape for _, p in group_items]
         sink_sig = tuple(None if s is None else (id(s[0]), s[1]) for s in sinks)
         plan = self._plans.get(key)
         if plan is None or plan["sizes"] != sizes or plan["sink_sig"] != sink_sig:
-            refs, refs_cast = [], []
-            for t, (n, (_, p), s) in enumerate(zip(sizes, group_items, sinks)):
-                flat = [(t, c) for c in range((n + self.CHUNK - 1) // self.CHUNK)]
-                refs.extend(flat)
-                if s is None:
-                    refs_cast.extend(flat)
-                else:
-                    tr, tc = (p.shape[0] + self.TILE - 1) // self.TILE, (p.shape[1] + self.TILE - 1) // self.TILE
-                    refs_cast.extend((t, c) for c in range(tr * tc))
-            chunks = torch.tensor(refs, dtype=torch.int32).to(dev)
+            refs, refs_cast = chunk_refs(sizes, shapes, sinks)
             # mi_adamw_f32_multi and mi_adamw_sr_bf16_multi always walk the cast list
-            any_sink = self._f32 or self._sr or any(s is not None for s in sinks)
-            nrows = 13 if self._f32 else 14 if self._sr else 12
-            plan = {"sizes": sizes, "sink_sig": sink_sig, "chunks": chunks, "n_chunks": len(refs), "addr": None,
+            any_sink = self._mode != "bf16" or any(s is not None for s in sinks)
+            nrows = {"bf16": ROW_MASTER, "fp32": ROW_MASTER + 1, "bf16_sr": ROW_SR_KEY + 1}[self._mode]
+            plan = {"sizes": sizes, "sink_sig": sink_sig, "chunks": torch.tensor(refs, dtype=torch.int32).to(dev), "n_chunks": len(refs), "addr": None,
                     "chunks_cast": torch.tensor(refs_cast, dtype=torch.int32).to(dev) if any_sink else None, "n_chunks_cast": len(refs_cast),
                     "table": torch.empty((nrows, len(sizes)), dtype=torch.int64, device=dev),
                     "host": [torch.empty((nrows, len(sizes)), dtype=torch.int64).pin_memory() for _ in range(2)], "flip": 0,
                     "uploaded": [None, None],
                     "partials": torch.empty(len(refs), dtype=torch.float64, device=dev)}
             self._plans[key] = plan
-        rows = [[], [], [], [], list(sizes), [], [], [], [], [], [], []]
-        if self._f32:
-            rows.append([self.state[p]["master"].data_ptr() for _, p in group_items])  # 12: the fp32 master weight
-        if self._sr:
-            keys = [self._sr_key(p) for _, p in group_items]
-            for (_, p), s, (_, base) in zip(group_items, sinks, keys):
-                if s is not None and base % 8:
-                    raise ValueError(f"ClippedAdamW: element base {base} of a weight with an FP8 sink must be a multiple of 8")
-            rows.append([base for _, base in keys])  # 12: global index of the tensor's first element
-            rows.append([key for key, _ in keys])    # 13: tensor key
-        for (_, p), s in zip(group_items, sinks):
-            st = self.state[p]
-            rows[0].append(p.data_ptr())
-            rows[1].append(p.grad.data_ptr())
-            rows[2].append(st["exp_avg"].data_ptr())
-            rows[3].append(st["exp_avg_sq"].data_ptr())
-            if s is None:
-                for r in range(5, 12):
-                    rows[r].append(0)
-            elif mx:  # mi_adamw_mxcast_bf16_multi: 6 y_row  7 s_row  8 y_colT  9 s_colT  10 ldr  11 unused
-                sink, r0, _ = s
-                K, N = p.shape[1], sink.w8.shape[0]
-                rows[5].append(K)
-                rows[6].append(sink.w8.data_ptr() + r0 * K)
-                rows[7].append(sink.sc.data_ptr() + r0)
-                rows[8].append(sink.wt8.data_ptr() + r0)
-                rows[9].append(sink.sct.data_ptr() + (r0 // 32) * K)
-                rows[10].append(N)
-                rows[11].append(0)
-            else:
-                sink, r0, _ = s
-                K, N = p.shape[1], sink.w8.shape[0]
-                rows[5].append(K)
-                dbg = os.environ.get("MI_DEBUG_SINK", "full")  # tools/bench_adamw.py: mask the FP8 outputs off (timing only)
-                rows[6].append(0 if dbg == "none" else sink.w8.data_ptr() + r0 * K)
-                rows[7].append(0 if dbg in ("none", "noT") else sink.w8t.data_ptr() + r0)
-                rows[8].append(K)
-                rows[9].append(N)
-                rows[10].append(sink.scale.data_ptr())
-                rows[11].append(sink.amax.data_ptr())
+        addrs = [(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["master"].data_ptr() if self._f32 else None)
+                 for p, st in ((p, self.state[p]) for _, p in group_items)]
+        rows = table_rows(addrs, sizes, shapes, sinks, self._mode, [self._sr_key(p) for _, p in group_items] if self._sr else None)
         plan["sinks"] = sinks
         plan["mx"] = mx
         if plan["addr"] != rows:
@@ -267,6 +270,16 @@ class ClippedAdamW(torch.optim.Optimizer):
             else:
                 self._seed_master(p, st)
 
+    def _launch(self, lib, plan, n_tensors, coef_ptr, group, step, st):
+        """The update of one plan: fp32 state also passes the partition's sink kind, stochastic rounding the kind and the group's seed."""
+        names, chunks, n_extra, _ = _LAUNCH[self._mode, plan["chunks_cast"] is not None]
+        kind = 1 if plan["mx"] else 0
+        b1, b2 = group["betas"]
+        rc = getattr(lib, names[kind])(plan["table"].data_ptr(), n_tensors, plan[chunks].data_ptr(), plan["n_" + chunks], CHUNK, coef_ptr,
+                                       float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], step,
+                                       *(kind, int(group.get("sr_seed", self.sr_seed)) & 0xFFFFFFFFFFFFFFFF)[:n_extra], st)
+        _lib.check(rc, names[kind])
+
     @torch.no_grad()
     def step(self, closure=None):
         assert closure is None
@@ -274,8 +287,9 @@ class ClippedAdamW(torch.optim.Optimizer):
         if not items:
             return None
         lib = _lib.load()
-        f32_step = _lib.require("mi_adamw_f32_multi", "ClippedAdamW(state_dtype=torch.float32)") if self._f32 else None
-        sr_step = _lib.require("mi_adamw_sr_bf16_multi", "ClippedAdamW(stochastic_rounding=True)") if self._sr else None
+        names, _, _, why = _LAUNCH[self._mode, True]
+        if why is not None:
+            _lib.require(names[0], why)
         dev = items[0][1].device
         st = torch.cuda.current_stream().cuda_stream
         by_group = {}
@@ -298,15 +312,19 @@ class ClippedAdamW(torch.optim.Optimizer):
             by_group.setdefault((id(group), state["step"]), []).append((group, p))
         # The squared norm is taken over the partitions above (ONE fixed summation order, whatever sinks exist); the update of a
         # partition that holds weights with an MXFP8 sink is split in two launches (another kernel and another table layout).
-        plans = [(gi, self._plan(gi, dev)) for gi in by_group.values()]
+        # Every parameter's sinks are looked up here, once per step: (per-tensor sink, MXFP8 sink).
+        fp8 = {id(p): self._sink_of(p) for _, p in items}
+        mxs = {id(p): self._sink_of(p, MXWeightSink) for _, p in items}
+        plan_of = lambda gi, found, mx=False: self._plan(gi, tuple(found[id(p)] for _, p in gi), dev, mx)
+        plans = [(gi, plan_of(gi, fp8)) for gi in by_group.values()]
         updates = []
         for gi, plan in plans:
-            gi_mx = [it for it in gi if self._mx_sink_of(it[1]) is not None]
+            gi_mx = [it for it in gi if mxs[id(it[1])] is not None]
             if gi_mx:
-                gi_rest = [it for it in gi if self._mx_sink_of(it[1]) is None]
-                updates.append((gi_mx, self._plan(gi_mx, dev, mx=True)))
+                gi_rest = [it for it in gi if mxs[id(it[1])] is None]
+                updates.append((gi_mx, plan_of(gi_mx, mxs, True)))
                 if gi_rest:
-                    updates.append((gi_rest, self._plan(gi_rest, dev)))
+                    updates.append((gi_rest, plan_of(gi_rest, fp8)))
             else:
                 updates.append((gi, plan))
         coef_ptr = None
@@ -314,7 +332,7 @@ class ClippedAdamW(torch.optim.Optimizer):
             # squared norm: one launch per parameter group, one FLOAT64 partial per 64 Ki-element chunk (exact squares, fp64 sums)
             for gi, plan in plans:
                 _lib.check(lib.mi_sumsq_bf16_multi(plan["table"].data_ptr(), len(gi), plan["chunks"].data_ptr(), plan["n_chunks"],
-                                                   self.CHUNK, plan["partials"].data_ptr(), st), "mi_sumsq_bf16_multi")
+                                                   CHUNK, plan["partials"].data_ptr(), st), "mi_sumsq_bf16_multi")
             # Partials and totals stay in FLOAT64 and the norm is rounded to fp32 once: the wrappers partition the parameters
             # differently (distributed.ShardedFP8DP: one group of row shards + the replicated rest, summed over ranks), and in
             # fp32 the association of those sums moves the last bit of the clip coefficient -- a handful of weights then round
@@ -342,29 +360,7 @@ class ClippedAdamW(torch.optim.Optimizer):
             group = gi[0][0]
             for _, p in gi:
                 self.state[p]["step"] += 1
-            b1, b2 = group["betas"]
-            if self._f32:  # fp32 master + moments: one entry point, the sink layout of the partition as an argument
-                rc = f32_step(plan["table"].data_ptr(), len(gi), plan["chunks_cast"].data_ptr(), plan["n_chunks_cast"], self.CHUNK,
-                              coef_ptr, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                              int(self.state[gi[0][1]]["step"]), 1 if plan["mx"] else 0, st)
-                _lib.check(rc, "mi_adamw_f32_multi")
-            elif self._sr:  # bf16 state, stochastic rounding: the counter is the partition's step, the key the group's seed
-                rc = sr_step(plan["table"].data_ptr(), len(gi), plan["chunks_cast"].data_ptr(), plan["n_chunks_cast"], self.CHUNK,
-                             coef_ptr, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                             int(self.state[gi[0][1]]["step"]), 1 if plan["mx"] else 0,
-                             int(group.get("sr_seed", self.sr_seed)) & 0xFFFFFFFFFFFFFFFF, st)
-                _lib.check(rc, "mi_adamw_sr_bf16_multi")
-            elif plan["chunks_cast"] is not None:  # some weights of this partition have FP8 sinks: update + cast in one pass
-                fn = lib.mi_adamw_mxcast_bf16_multi if plan["mx"] else lib.mi_adamw_cast_bf16_multi
-                rc = fn(plan["table"].data_ptr(), len(gi), plan["chunks_cast"].data_ptr(), plan["n_chunks_cast"],
-                                                  self.CHUNK, coef_ptr, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                                                  int(self.state[gi[0][1]]["step"]), st)
-                _lib.check(rc, "mi_adamw_mxcast_bf16_multi" if plan["mx"] else "mi_adamw_cast_bf16_multi")
-            else:
-                rc = lib.mi_adamw_bf16_multi(plan["table"].data_ptr(), len(gi), plan["chunks"].data_ptr(), plan["n_chunks"], self.CHUNK,
-                                             coef_ptr, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                                             int(self.state[gi[0][1]]["step"]), st)
-                _lib.check(rc, "mi_adamw_bf16_multi")
+            self._launch(lib, plan, len(gi), coef_ptr, group, int(self.state[gi[0][1]]["step"]), st)
             # the kernels write through raw addresses: tell autograd (and every cache keyed on `_version`, wcast.py)
             torch.autograd.graph.increment_version([p for _, p in gi])
             if self._f32:

@@ -127,12 +127,15 @@ class _Sink:
     weights themselves, and `stamp` = what `_now()` gave when the optimiser last rewrote every part (the copies are current while
     it still gives that)."""
     __slots__ = ("parts", "stamp")
+    # what the optimiser needs to know of a sink class (optim.ClippedAdamW): `attr` = the name the parts are announced under,
+    # `unit` = what rows, cols (and, MXFP8, the row offset of a part) must be multiples of, `kind` = sink_kind of the C ABI;
+    # table_rows(r0, K) = rows 6..11 of the device table for the [*, K] part at row r0 of the operand (include/mi_fp8.h)
 
-    def _register(self, weights, ns, attr: str) -> None:
+    def _register(self, weights, ns) -> None:
         self.parts, r = [], 0
         for w, n in zip(weights, ns):
             self.parts.append((w, r, n))
-            setattr(w, attr, (self, r, n))
+            setattr(w, self.attr, (self, r, n))
             r += n
         self.stamp = None
 
@@ -158,12 +161,16 @@ class WeightSink(_Sink):
     only while both still match (no other write to the weights, no scale update in between: an evaluation pass or a second
     micro-batch re-casts as before)."""
     __slots__ = ("w8", "w8t", "arena", "scale", "amax")
+    attr, unit, kind = "_mi_fp8_sink", 8, 0
 
     def __init__(self, weights, ns, N, K, dev, mf, slot):
         self.w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
         self.w8t = torch.empty((K, N), dtype=torch.uint8, device=dev)
         self.arena, self.scale, self.amax = mf.arena, mf.scale(slot), mf.amax(slot)
-        self._register(weights, ns, "_mi_fp8_sink")
+        self._register(weights, ns)
+
+    def table_rows(self, r0, K):  # y, yT, ld_y, ld_yT, scale, amax
+        return (self.w8.data_ptr() + r0 * K, self.w8t.data_ptr() + r0, K, self.w8.shape[0], self.scale.data_ptr(), self.amax.data_ptr())
 
     def holds(self, weights, mf) -> bool:
         return self.arena is mf.arena and super().holds(weights, mf)
@@ -177,13 +184,18 @@ class MXWeightSink(_Sink):
     weight operand that the OPTIMISER keeps current (optim.ClippedAdamW -> mi_adamw_mxcast_bf16_multi).  Block scaling has no
     state, so the only condition for using them is that nobody wrote the weights since: `stamp` = versions of the parts."""
     __slots__ = ("w8", "sc", "wt8", "sct")
+    attr, unit, kind = "_mi_mx_sink", 32, 1
 
     def __init__(self, weights, ns, N, K, dev):
         self.w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
         self.sc = torch.empty((K // 32, N), dtype=torch.uint8, device=dev)
         self.wt8 = torch.empty((K, N), dtype=torch.uint8, device=dev)
         self.sct = torch.empty((N // 32, K), dtype=torch.uint8, device=dev)
-        self._register(weights, ns, "_mi_mx_sink")
+        self._register(weights, ns)
+
+    def table_rows(self, r0, K):  # y_row, s_row, y_colT, s_colT, ldr, unused
+        return (self.w8.data_ptr() + r0 * K, self.sc.data_ptr() + r0, self.wt8.data_ptr() + r0, self.sct.data_ptr() + (r0 // 32) * K,
+                self.w8.shape[0], 0)
 
 
 def stepped_tensor(w):
