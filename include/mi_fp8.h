@@ -70,9 +70,11 @@ extern "C" {
  *   3  mi_blockfp8_quantize_ex, mi_blockfp8_norm_quantize, mi_blockfp8_swiglu_quantize, mi_blockfp8_dswiglu_quantize
  *      (Float8BlockScaling: 1 x 128 and 128 x 128 power-of-two block scales in the MX operand layout)
  *   4  mi_adamw_sr_bf16_multi (stochastic rounding of the bf16 weight and moments in the fused AdamW + FP8 cast pass)
+ *   5  no new entry point: every mi_adamw_* call reads a NON-FINITE *grad_scale as "skip the step" (THE STEP GUARD below, at
+ *      mi_sumsq_bf16).  A caller that sends NaN to drop a step needs a library of this revision; finite values and NULL are unchanged.
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 4
+#define MI_ABI_REVISION 5
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -435,6 +437,15 @@ int mi_ce_backward_cast(const void* logits_bf16, const int64_t* labels, const fl
  *   mi_adamw_bf16: torch.optim.AdamW update on bf16 p / exp_avg / exp_avg_sq with fp32 math; the gradient is
  *                  multiplied by *grad_scale (device scalar, NULL = 1) -- the clip coefficient, so the gradients are
  *                  not rescaled in a separate pass.  `step` is the 1-based step count for the bias corrections.
+ * THE STEP GUARD (ABI 5 revision 5), the same for mi_adamw_bf16 and every mi_adamw_*_multi call below.  A NON-FINITE *grad_scale
+ * (NaN, +Inf, -Inf: all exponent bits set) means "skip": the launch behaves as after an update of exactly zero.  p, exp_avg,
+ * exp_avg_sq and the fp32 master are not written, not even with their own values; the gradient and the moments are not loaded; no
+ * random bits are drawn.  A tensor without an FP8 sink (and every flat chunk) is left alone.  A tensor WITH a sink still gets its
+ * copies: a tile loads p only and emits what mi_cast_amax (per-tensor sink: y, yT from the stored weight with the current
+ * *scale, its amax published) or mi_mxfp8_quantize (MXFP8 sink: all four buffers) would emit from the stored weight -- the
+ * sink may never have been filled, and under delayed scaling *scale has moved since the last emission.  The test is made once per
+ * workgroup, on the bits of the value, before anything else is loaded.  NULL and every finite value: the update, as before.
+ * A caller makes the decision on the device: a clip coefficient formed from a non-finite gradient norm is sent as NaN.
  */
 int mi_sumsq_bf16(const void* g_bf16, int64_t n, float* partial, int n_partials, void* stream);
 /*
@@ -443,6 +454,7 @@ int mi_sumsq_bf16(const void* g_bf16, int64_t n, float* partial, int n_partials,
  * index inside the tensor); each workgroup handles one chunk of chunk_elems (multiple of 8) elements.
  * mi_sumsq_bf16_multi writes partial[n_chunks] in FLOAT64 (exact fp32 squares accumulated in fp64: the total is independent of the
  * chunking and of how a caller groups or shards the tensors, to 2^-52); mi_adamw_bf16_multi = mi_adamw_bf16 on every tensor.
+ * Non-finite *grad_scale: the step guard above -- the launch returns at once, nothing is read or written.
  */
 int mi_sumsq_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                         double* partial, void* stream);
@@ -458,6 +470,8 @@ int mi_adamw_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chun
  * For a sink tensor every element is updated, rounded to bf16 and stored, and that rounded value is quantised exactly as
  * mi_cast_amax would: y = sat_cast_e4m3(float(bf16) * *scale), *amax = max(*amax, |bf16|) -- bitwise the bytes of a
  * mi_cast_amax call on the updated weight.  rows and cols multiples of 8.
+ * Non-finite *grad_scale: the step guard above -- tensors with cols == 0 are left alone; a sink tensor's p, exp_avg and exp_avg_sq
+ * are not written, and y / yT / *amax are those of mi_cast_amax on p as it stands, with *scale as it is now.
  */
 int mi_adamw_cast_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                              const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -470,6 +484,8 @@ int mi_adamw_cast_bf16_multi(const int64_t* table, int n_tensors, const int32_t*
  *   10 ldr (row count of the operand the tensor is a row-block of: query | key | value form one operand), 11 unused.
  * Rows 6-9 point at the tensor's first row inside the operand's buffers.  Bitwise the bytes of mi_mxfp8_quantize(_ex) on the
  * updated, bf16-rounded weight.  rows and cols multiples of 32; the row offset of a part a multiple of 32.
+ * Non-finite *grad_scale: the step guard above -- tensors with cols == 0 are left alone; a sink tensor's p, exp_avg and exp_avg_sq
+ * are not written, and y_row / s_row / y_colT / s_colT are those of mi_mxfp8_quantize on p as it stands.
  */
 int mi_adamw_mxcast_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                                const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -489,6 +505,8 @@ int mi_adamw_mxcast_bf16_multi(const int64_t* table, int n_tensors, const int32_
  * in 128 x 128 tiles and needs all five arrays 16-byte aligned (the caller sends anything else down the flat chunks).
  * MI_ERR_ARG before any launch: null table / chunks, n_tensors < 1, chunk_elems not a positive multiple of 8, sink_kind outside
  * {0, 1}, step < 1.  n_chunks == 0 is MI_OK (nothing to do).
+ * Non-finite *grad_scale, both sink kinds: the step guard above -- master, exp_avg, exp_avg_sq and p are not written; the copies of a
+ * sink tensor are quantised from the bf16 p as it stands (the master is not read).
  */
 int mi_adamw_f32_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                        const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -517,6 +535,8 @@ int mi_adamw_f32_multi(const int64_t* table, int n_tensors, const int32_t* chunk
  * mi_mxfp8_quantize of the updated p.  Alignment rules and refusals as for mi_adamw_f32_multi: MI_ERR_ARG before any launch for a
  * null table / chunks, n_tensors < 1, chunk_elems not a positive multiple of 8, sink_kind outside {0, 1}, step < 1; n_chunks == 0
  * is MI_OK.
+ * Non-finite *grad_scale, both sink kinds: the step guard above -- nothing of the state is written and NO random bits are drawn (the
+ * stream is counted by `step`, which the caller advances all the same); the copies of a sink tensor are quantised from p as it stands.
  */
 int mi_adamw_sr_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                            const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -532,6 +552,7 @@ int mi_adamw_sr_bf16_multi(const int64_t* table, int n_tensors, const int32_t* c
  */
 int mi_embedding_grad_add(void* grad_bf16, const void* dy_bf16, const int64_t* sorted_ids, const int64_t* perm, int64_t tokens,
                           int64_t hidden, int64_t vocab, float alpha, int64_t padding_idx, void* stream);
+/* mi_adamw_bf16 (stated at mi_sumsq_bf16 above).  Non-finite *grad_scale: the step guard -- the launch returns at once. */
 int mi_adamw_bf16(void* p_bf16, const void* g_bf16, void* exp_avg_bf16, void* exp_avg_sq_bf16, int64_t n,
                   const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                   int64_t step, void* stream);

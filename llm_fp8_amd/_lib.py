@@ -13,7 +13,8 @@ LAB_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "bin", "libmi_fp8_l
 MI_FMT_E4M3 = 0
 MI_FMT_E5M2 = 1
 ABI_VERSION = 5
-ABI_REVISION = 4  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
+ABI_REVISION = 5  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
+# revision 5 adds no symbol: from it on every mi_adamw_* entry point reads a non-finite *grad_scale as "skip the step" (optim.py)
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int

@@ -81,10 +81,19 @@ __device__ __forceinline__ void adam_one(T& p, T g, T& m, T& v, const AdamArgs& 
 template <typename ST> struct AdamMath { typedef float T; };
 template <> struct AdamMath<float> { typedef double T; };
 
+// THE STEP GUARD (include/mi_fp8.h, "non-finite *grad_scale"): the caller's clip coefficient is NaN when the gradient norm was
+// Inf or NaN, and the launch then behaves as after an update of exactly zero -- p, the moments and the master are neither loaded
+// (p: only where an FP8 sink needs it) nor written, the gradient is not loaded, no random bits are drawn; a weight with a sink
+// still gets its FP8 copies, quantised from the weight as stored.  Every AdamW kernel loads *grad_scale first and tests it
+// here, once, the same way in every lane of the launch.  The exponent bits are tested as an integer: no floating-point flag
+// of the build can fold the test away.
+__device__ __forceinline__ bool skip_step(float gs) { return (__float_as_uint(gs) & 0x7F800000u) == 0x7F800000u; }
+
 __global__ __launch_bounds__(256) void adamw_kernel(uint16_t* __restrict__ p, const uint16_t* __restrict__ g,
                                                     uint16_t* __restrict__ m, uint16_t* __restrict__ v, int64_t n,
                                                     const float* __restrict__ grad_scale, AdamArgs a) {
   const float gs = grad_scale ? *grad_scale : 1.0f;
+  if (skip_step(gs)) return;
   const int64_t nvec = n >> 3;
   const bool aligned = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
   const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
@@ -375,6 +384,15 @@ __device__ __forceinline__ void adam_vec8(const AdamPtrs<ST>& t, int64_t i, floa
   mv.store(t.m, i);
   vv.store(t.v, i);
 }
+// A skipped step's form of adam_vec8 (skip_step): f = the lane's 8 weights as they stand in p; nothing else is read, nothing written.
+__device__ __forceinline__ void stored_vec8(const uint16_t* p, int64_t i, float (&f)[8]) {
+  const v4i pv = reinterpret_cast<const v4i*>(p)[i];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[2 * j] = __uint_as_float((u32)pv[j] << 16);
+    f[2 * j + 1] = __uint_as_float((u32)pv[j] & 0xFFFF0000u);
+  }
+}
 
 // Flat walk of one chunk: elements [chunk * chunk_elems, + chunk_elems) of the tensor, 8 per lane where every array is 16-byte
 // aligned, one per lane otherwise and on the tail.  SR: a tensor whose first element is not at a multiple of 8 of the global index
@@ -414,10 +432,11 @@ __device__ __forceinline__ void adam_flat_chunk(const AdamPtrs<ST>& t, int64_t n
 
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
                                                           int chunk_elems, const float* __restrict__ grad_scale, AdamArgs a) {
+  const float gs = grad_scale ? *grad_scale : 1.0f;
+  if (skip_step(gs)) return;  // no tensor of this launch has a sink
   const ChunkRef cr = chunks[blockIdx.x];
   const AdamPtrs<uint16_t> t(tab, T, cr.tensor);
   const int64_t n = tab_at(tab, T, ROW_NUMEL, cr.tensor);
-  const float gs = grad_scale ? *grad_scale : 1.0f;
   adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, SrCtx<false>(a, tab, T, cr.tensor), threadIdx.x);
 }
 
@@ -442,19 +461,14 @@ struct TileBlock {
 // element is updated, rounded to bf16, stored -- and that ROUNDED value is quantised exactly as mi_cast_amax would
 // (y = sat(float(bf16) * scale), amax = max |bf16|), into y [rows, ld_y] and the transposed copy yT [cols, ld_yT].
 // Tensors without a sink (cols == 0) take the flat path of adamw_multi_kernel.  Table: the per-tensor rows of THE TABLE above.
-template <typename ST, bool SR = false>
-__global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
-                                                               int chunk_elems, const float* __restrict__ grad_scale,
-                                                               typename AdamKernelArgs<SR>::T a) {
-  const ChunkRef cr = chunks[blockIdx.x];
-  const AdamPtrs<ST> t(tab, T, cr.tensor);
-  const SrCtx<SR> sr(a, tab, T, cr.tensor);
-  const int64_t n = tab_at(tab, T, ROW_NUMEL, cr.tensor);
-  const int64_t cols = tab_at(tab, T, ROW_COLS, cr.tensor);
-  const float gs = grad_scale ? *grad_scale : 1.0f;
-  const int tid = threadIdx.x, tensor = cr.tensor;
-  if (cols == 0) return adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);  // the walk of adamw_multi_kernel
-  // tile of a weight with an FP8 sink
+// SKIP (a skipped step, skip_step): the tile's values are the weight as it stands in p (stored_vec8) instead of the update's
+// results; everything after them is the same code.  The kernel picks one of the two instantiations per workgroup, so the
+// update's instantiation carries nothing of the other.
+template <typename ST, bool SR, bool SKIP>
+__device__ __forceinline__ void adamw_cast_tile(const int64_t* __restrict__ tab, int T, const ChunkRef cr, const AdamPtrs<ST>& t, int64_t n,
+                                                int64_t cols, float gs, const typename AdamKernelArgs<SR>::T& a, const SrCtx<SR>& sr,
+                                                int tid) {
+  const int tensor = cr.tensor;
   uint8_t* y = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_Y, tensor));
   uint8_t* yT = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_YT, tensor));
   const int64_t ld_y = tab_at(tab, T, ROW_LD_Y, tensor), ld_yT = tab_at(tab, T, ROW_LD_YT, tensor);
@@ -468,7 +482,8 @@ __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       float f[8];  // the ROUNDED weight: what the next forward's cast would read
-      adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, sr, f);
+      if constexpr (SKIP) stored_vec8(t.p, ((r0 + i) * cols + c0) >> 3, f);
+      else adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, sr, f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) amax = fmaxf(amax, (f[j] != f[j]) ? 0.0f : fabsf(f[j]));
       lo[i] = cvt4_fp8<MI_FMT_E4M3>(f[0] * scale, f[1] * scale, f[2] * scale, f[3] * scale);
@@ -481,24 +496,36 @@ __global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __
   }
   publish_amax(amax, amax_out);
 }
+template <typename ST, bool SR = false>
+__global__ __launch_bounds__(256) void adamw_cast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
+                                                               int chunk_elems, const float* __restrict__ grad_scale,
+                                                               typename AdamKernelArgs<SR>::T a) {
+  const float gs = grad_scale ? *grad_scale : 1.0f;
+  const bool skip = skip_step(gs);
+  const ChunkRef cr = chunks[blockIdx.x];
+  const int64_t cols = tab_at(tab, T, ROW_COLS, cr.tensor);
+  if (skip && cols == 0) return;  // a skipped step leaves a tensor without a sink alone
+  const AdamPtrs<ST> t(tab, T, cr.tensor);
+  const SrCtx<SR> sr(a, tab, T, cr.tensor);
+  const int64_t n = tab_at(tab, T, ROW_NUMEL, cr.tensor);
+  const int tid = threadIdx.x;
+  if (cols == 0) return adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);  // the walk of adamw_multi_kernel
+  // tile of a weight with an FP8 sink
+  if (skip) adamw_cast_tile<ST, SR, true>(tab, T, cr, t, n, cols, gs, a, sr, tid);
+  else adamw_cast_tile<ST, SR, false>(tab, T, cr, t, n, cols, gs, a, sr, tid);
+}
 
 // AdamW + MXFP8 weight quantisation in one pass: the MXFP8 form of the weight-cast hand-off.  Block scaling has no state -- the
 // E8M0 scale of a 32-element block comes from the block itself -- so the copies the NEXT forward needs (row-wise blocks for
 // fprop, column-wise blocks, stored transposed, for dgrad) can be emitted as soon as the weight is updated.  Same tile walk as
 // adamw_cast_multi_kernel (128 x 128 tile per workgroup, 8 x 8 block per lane); the quantisation of the ROUNDED bf16 weight is
 // mxfp8_quant_kernel's: both call mx_quant_rows / mx_quant_cols (mi_common.h).  Table: the MXFP8 rows of THE TABLE above.
-template <typename ST, bool SR = false>
-__global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
-                                                                 int chunk_elems, const float* __restrict__ grad_scale,
-                                                                 typename AdamKernelArgs<SR>::T a) {
-  const ChunkRef cr = chunks[blockIdx.x];
-  const AdamPtrs<ST> t(tab, T, cr.tensor);
-  const SrCtx<SR> sr(a, tab, T, cr.tensor);
-  const int64_t n = tab_at(tab, T, ROW_NUMEL, cr.tensor);
-  const int64_t cols = tab_at(tab, T, ROW_COLS, cr.tensor);
-  const float gs = grad_scale ? *grad_scale : 1.0f;
-  const int tid = threadIdx.x, lane = tid & 63, tensor = cr.tensor;
-  if (cols == 0) return adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);  // the walk of adamw_multi_kernel
+// SKIP: as in adamw_cast_tile
+template <typename ST, bool SR, bool SKIP>
+__device__ __forceinline__ void adamw_mxcast_tile(const int64_t* __restrict__ tab, int T, const ChunkRef cr, const AdamPtrs<ST>& t, int64_t n,
+                                                  int64_t cols, float gs, const typename AdamKernelArgs<SR>::T& a, const SrCtx<SR>& sr,
+                                                  int tid) {
+  const int lane = tid & 63, tensor = cr.tensor;
   uint8_t* y_row = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_Y_ROW, tensor));
   uint8_t* s_row = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_S_ROW, tensor));
   uint8_t* y_colT = reinterpret_cast<uint8_t*>(tab_at(tab, T, ROW_Y_COLT, tensor));
@@ -510,8 +537,9 @@ __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* 
   float f[8][8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    if (active) {
-      adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, sr, f[i]);  // the ROUNDED weight: what the next forward's quantiser would read
+    if (active) {  // the ROUNDED weight: what the next forward's quantiser would read
+      if constexpr (SKIP) stored_vec8(t.p, ((r0 + i) * cols + c0) >> 3, f[i]);
+      else adam_vec8(t, ((r0 + i) * cols + c0) >> 3, gs, a, sr, f[i]);
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) f[i][j] = 0.0f;
@@ -530,6 +558,23 @@ __global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* 
     store_cols8<true>(y_colT + c0 * ldr + r0, ldr, lo, hi);
     if (((lane >> 3) & 3) == 0) store_scales8(s_colT + (r0 / 32) * cols + c0, sbytes);
   }
+}
+template <typename ST, bool SR = false>
+__global__ __launch_bounds__(256) void adamw_mxcast_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
+                                                                 int chunk_elems, const float* __restrict__ grad_scale,
+                                                                 typename AdamKernelArgs<SR>::T a) {
+  const float gs = grad_scale ? *grad_scale : 1.0f;
+  const bool skip = skip_step(gs);
+  const ChunkRef cr = chunks[blockIdx.x];
+  const int64_t cols = tab_at(tab, T, ROW_COLS, cr.tensor);
+  if (skip && cols == 0) return;  // a skipped step leaves a tensor without a sink alone
+  const AdamPtrs<ST> t(tab, T, cr.tensor);
+  const SrCtx<SR> sr(a, tab, T, cr.tensor);
+  const int64_t n = tab_at(tab, T, ROW_NUMEL, cr.tensor);
+  const int tid = threadIdx.x;
+  if (cols == 0) return adam_flat_chunk(t, n, cr.chunk, chunk_elems, gs, a, sr, tid);  // the walk of adamw_multi_kernel
+  if (skip) adamw_mxcast_tile<ST, SR, true>(tab, T, cr, t, n, cols, gs, a, sr, tid);
+  else adamw_mxcast_tile<ST, SR, false>(tab, T, cr, t, n, cols, gs, a, sr, tid);
 }
 
 // Embedding weight gradient added IN PLACE into an existing [V, H] bf16 gradient (the tied lm_head / embedding table already

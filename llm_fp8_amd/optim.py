@@ -74,6 +74,18 @@ _LAUNCH = {("bf16", False): (("mi_adamw_bf16_multi",) * 2, "chunks", 0, None),
            ("fp32", True): (("mi_adamw_f32_multi",) * 2, "chunks_cast", 1, "ClippedAdamW(state_dtype=torch.float32)"),
            ("bf16_sr", True): (("mi_adamw_sr_bf16_multi",) * 2, "chunks_cast", 2, "ClippedAdamW(stochastic_rounding=True)")}
 
+GUARD_REVISION = 5  # include/mi_fp8.h: from this revision on the update kernels take a non-finite *grad_scale as "skip"
+
+
+def guarded_clip_coefficient(total_sq: torch.Tensor, max_norm: float):
+    """(norm, coefficient) from the float64 sum of the squared gradients: `norm` = its root rounded once to fp32, `coefficient`
+    [1] fp32 = clip_grad_norm_'s `(max_norm / (norm + 1e-6)).clamp(max=1)` where the norm is finite -- bit for bit -- and NaN
+    where it is Inf or NaN, which the update kernels read as "skip this step".  `norm - norm` is +0 for a finite norm and NaN
+    otherwise, and the coefficient of a finite norm is positive, so adding it changes no bit.  Torch ops only, no host sync."""
+    norm = total_sq.sqrt().to(torch.float32)
+    coef = (max_norm / (norm + 1e-6)).clamp(max=1.0) + (norm - norm)
+    return norm, coef.reshape(1)
+
 
 class ClippedAdamW(torch.optim.Optimizer):
     """`state_dtype` is the precision the optimiser state is KEPT in between steps (a step is evaluated in fp32 for bf16 state and in fp64 for fp32 state).
@@ -99,10 +111,26 @@ class ClippedAdamW(torch.optim.Optimizer):
     its rows would draw in the whole weight.  Key and first element index of a tensor are `p._mi_sr_key = (key, base)` when set,
     else (position of the parameter over the param groups, 0).  With fp32 state the master carries the residue and
     `p = RNE(master)` is right: the combination is refused.  `stochastic_rounding` and `sr_seed` are kept in the param groups
-    (and so in `state_dict()`) only in this mode."""
+    (and so in `state_dict()`) only in this mode.
+
+    `skip_nonfinite` (the step guard): a step whose gradient norm is Inf or NaN is DROPPED on the device, as AMP's GradScaler
+    drops one, instead of writing NaN into every weight, moment and FP8 copy.  The clip coefficient of such a step is NaN
+    (`guarded_clip_coefficient`) and the update kernels read a non-finite coefficient as "skip" (include/mi_fp8.h, revision 5):
+    parameter, moments and master are not written; the FP8 / MXFP8 copies of the weight sinks are still emitted, from the
+    unchanged weight with the current scale.  No launch is added and the host never waits.  `None` (default): on where the
+    loaded library has revision >= 5, off with an older build (LLM_FP8_AMD_LIB, for A/B timing); `True`: an older library is
+    refused; `False`: off, a non-finite norm poisons the state as it always did.  The guard needs the norm: with
+    `max_grad_norm=None` it is inactive whatever the keyword says, and the launch sequence is unchanged.
+    `last_step_skipped` is a 0-dim bool tensor on the device saying whether the last `step()` was dropped (None while the guard
+    is inactive) and `skipped_steps` an int64 device counter of the dropped steps (None before the first guarded step); the
+    optimiser never reads either, and neither is part of `state_dict()`.  The host does not know that a step was dropped, so
+    everything it does after a step happens as after any other: `state["step"]` counts the dropped step (the bias corrections
+    and the stochastic-rounding stream move on, and so does the caller's LR scheduler), the sinks are stamped current,
+    `p._version` moves and `master_version` follows it."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm: Optional[float] = 1.0,
-                 state_dtype: torch.dtype = torch.bfloat16, stochastic_rounding: bool = False, sr_seed: int = 0):
+                 state_dtype: torch.dtype = torch.bfloat16, stochastic_rounding: bool = False, sr_seed: int = 0,
+                 skip_nonfinite: Optional[bool] = None):
         if state_dtype not in (torch.bfloat16, torch.float32):
             raise ValueError(f"ClippedAdamW: state_dtype must be torch.bfloat16 or torch.float32, not {state_dtype!r}")
         if stochastic_rounding and state_dtype == torch.float32:
@@ -120,6 +148,27 @@ class ClippedAdamW(torch.optim.Optimizer):
         self._mode = "fp32" if self._f32 else "bf16_sr" if self._sr else "bf16"  # train.OPTIMIZER_STATES
         self._plans = {}
         self.last_grad_norm: Optional[torch.Tensor] = None
+        if skip_nonfinite not in (None, True, False):
+            raise ValueError(f"ClippedAdamW: skip_nonfinite must be None, True or False, not {skip_nonfinite!r}")
+        self.skip_nonfinite = skip_nonfinite
+        self.last_step_skipped: Optional[torch.Tensor] = None
+        self.skipped_steps: Optional[torch.Tensor] = None
+        if skip_nonfinite:
+            self._guard_active()  # refuse an older library now, not at the first step
+
+    def _guard_active(self) -> bool:
+        """Whether step() forms the guarded coefficient: there is a norm, the keyword allows it and the library's kernels know
+        the contract."""
+        if self.max_grad_norm is None or self.skip_nonfinite is False:
+            return False
+        rev = _lib.revision()
+        if rev >= GUARD_REVISION:
+            return True
+        if self.skip_nonfinite:
+            raise RuntimeError(f"ClippedAdamW(skip_nonfinite=True) needs update kernels that skip on a non-finite grad_scale, which "
+                               f"{_lib.LIB_PATH} (ABI {_lib.ABI_VERSION} revision {rev}) does not have: it was built before revision "
+                               f"{GUARD_REVISION}; rebuild it, or unset LLM_FP8_AMD_LIB")
+        return False
 
     def _grads(self):
         out = []
@@ -327,7 +376,7 @@ class ClippedAdamW(torch.optim.Optimizer):
                     updates.append((gi_rest, plan_of(gi_rest, fp8)))
             else:
                 updates.append((gi, plan))
-        coef_ptr = None
+        coef_ptr = self.last_step_skipped = None
         if self.max_grad_norm is not None:
             # squared norm: one launch per parameter group, one FLOAT64 partial per 64 Ki-element chunk (exact squares, fp64 sums)
             for gi, plan in plans:
@@ -351,9 +400,17 @@ class ClippedAdamW(torch.optim.Optimizer):
                 if dist.is_available() and dist.is_initialized() and dist.get_world_size(grp) > 1:
                     dist.all_reduce(shard_total, op=dist.ReduceOp.SUM, group=grp)
                 total = shard_total if total is None else total + shard_total
-            total = total.sqrt().to(torch.float32)
+            if self._guard_active():
+                # a non-finite norm makes the coefficient NaN, which every update kernel below reads as "skip"
+                total, coef = guarded_clip_coefficient(total, self.max_grad_norm)
+                self.last_step_skipped = torch.isnan(coef).reshape(())
+                if self.skipped_steps is None:
+                    self.skipped_steps = torch.zeros((), dtype=torch.int64, device=dev)
+                self.skipped_steps += self.last_step_skipped
+            else:
+                total = total.sqrt().to(torch.float32)
+                coef = (self.max_grad_norm / (total + 1e-6)).clamp(max=1.0).reshape(1)  # clip_grad_norm_'s coefficient
             self.last_grad_norm = total
-            coef = (self.max_grad_norm / (total + 1e-6)).clamp(max=1.0).reshape(1)  # clip_grad_norm_'s coefficient
             coef_ptr = coef.data_ptr()
         touched, sinks_seen = set(), {}
         for gi, plan in updates:

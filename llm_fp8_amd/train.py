@@ -15,6 +15,7 @@ import functools
 import json
 import math
 import os
+import sys
 import time
 from dataclasses import dataclass, field
 from typing import Optional
@@ -46,6 +47,7 @@ class TrainingConfig:
     output_dir: Optional[str] = None      # ModelSaver.save_model (train_fp8.py:657-681)
     load_dir: Optional[str] = None        # local checkpoint directory (from_pretrained_local, te_llama.py:100-178)
     optimizer_state: Optional[str] = None  # "bf16" | "fp32" | "bf16_sr" (optim.ClippedAdamW); None: resolve_optimizer_state
+    skip_nonfinite_steps: bool = True     # ClippedAdamW drops a step whose gradient norm is Inf / NaN (resolve_skip_nonfinite)
 
 
 def create_model(cfg: TrainingConfig, device) -> torch.nn.Module:
@@ -132,6 +134,13 @@ def resolve_optimizer_state(cfg_or_value=None) -> str:
 # distributed.GradArenaDP; fsdp_fp8: distributed.ShardedFP8DP (FULL_SHARD counterpart with FP8 all-gather); fsdp_full / ddp: the
 # torch wrappers the reference uses (train_multi_gpu.py:414-445, :447-470); none: no wrapper
 SHARDING_MODES = ("auto", "replicated", "fsdp_fp8", "fsdp_full", "ddp", "none")
+
+
+def resolve_skip_nonfinite(cfg: TrainingConfig) -> Optional[bool]:
+    """`skip_nonfinite` of optim.ClippedAdamW: None (on where the library can) unless `--no_skip_nonfinite_steps` /
+    `TrainingConfig.skip_nonfinite_steps=False` or the A/B switch LLM_FP8_AMD_NO_STEP_GUARD=1 turn the step guard off."""
+    off = not cfg.skip_nonfinite_steps or os.environ.get("LLM_FP8_AMD_NO_STEP_GUARD") == "1"
+    return False if off else None
 
 
 def resolve_sharding_mode(mode: str, model: torch.nn.Module, device, optimizer_state: Optional[str] = None) -> str:
@@ -231,7 +240,7 @@ def create_optimizer(model, cfg: TrainingConfig):
         # sr_seed: the same on every rank (replicated ranks must stay identical; a row shard draws its rows' bits of the whole weight)
         opt = ClippedAdamW(groups if groups is not None else params, lr=cfg.learning_rate, max_grad_norm=cfg.max_grad_norm,
                            state_dtype=torch.float32 if opt_state == "fp32" else torch.bfloat16,
-                           stochastic_rounding=opt_state == "bf16_sr", sr_seed=cfg.seed)
+                           stochastic_rounding=opt_state == "bf16_sr", sr_seed=cfg.seed, skip_nonfinite=resolve_skip_nonfinite(cfg))
     else:
         if opt_state in ("fp32", "bf16_sr"):  # torch's AdamW keeps its state in the parameters' dtype and rounds to nearest: no silent downgrade
             why = ("the parameters are not all on the GPU" if not fused else
@@ -356,6 +365,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--optimizer_state", choices=OPTIMIZER_STATES, default=None,
                     help="precision of the AdamW state: bf16 (default; or $LLM_FP8_AMD_OPT_STATE) | fp32 master weights + moments | "
                          "bf16_sr: bf16 with stochastic rounding of the weight and moments")
+    ap.add_argument("--no_skip_nonfinite_steps", action="store_true",
+                    help="let a step with an Inf / NaN gradient norm through (ClippedAdamW drops it on the device by default)")
     return ap
 
 
@@ -365,7 +376,7 @@ def config_from_args(a) -> TrainingConfig:
                          sharding_mode=a.sharding_mode, learning_rate=a.learning_rate,
                          num_hidden_layers=a.num_hidden_layers, vocab_size=a.vocab_size, num_warmup_steps=a.num_warmup_steps,
                          gradient_accumulation_steps=a.gradient_accumulation_steps, output_dir=a.output_dir, load_dir=a.load_dir,
-                         optimizer_state=a.optimizer_state)
+                         optimizer_state=a.optimizer_state, skip_nonfinite_steps=not a.no_skip_nonfinite_steps)
 
 
 def main(argv=None):
@@ -392,6 +403,9 @@ def main(argv=None):
         if rank == 0:
             toks = cfg.batch_size * cfg.max_seq_length * world * acc / dt  # train_multi_gpu.py:751-755
             print(json.dumps({"step": step, "loss": lv, "ms": dt * 1e3, "tokens_per_s": toks}), flush=True)
+    skipped = getattr(opt, "skipped_steps", None)  # ClippedAdamW's device counter: read once, after the last step
+    if rank == 0:  # on stderr: stdout carries the per-step records, one JSON line per step, and nothing else that looks like one
+        print(json.dumps({"skipped_steps": 0 if skipped is None else int(skipped.item())}), file=sys.stderr, flush=True)
     if cfg.output_dir:
         if hasattr(model, "gather_master_weights"):
             model.gather_master_weights()  # a collective: every rank takes part, rank 0 writes
