@@ -72,9 +72,10 @@ extern "C" {
  *   4  mi_adamw_sr_bf16_multi (stochastic rounding of the bf16 weight and moments in the fused AdamW + FP8 cast pass)
  *   5  no new entry point: every mi_adamw_* call reads a NON-FINITE *grad_scale as "skip the step" (THE STEP GUARD below, at
  *      mi_sumsq_bf16).  A caller that sends NaN to drop a step needs a library of this revision; finite values and NULL are unchanged.
+ *   6  mi_qknorm_rope_qkv, mi_qknorm_rope_qkv_bwd (per-head QK RMSNorm fused into the RoPE split: Qwen3 attention)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 5
+#define MI_ABI_REVISION 6
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -335,6 +336,29 @@ int mi_rope_qkv(void* fused_bf16, void* q_bf16, void* k_bf16, void* v_bf16, cons
 int mi_rope_qkv_bwd_cast(const void* dq_bf16, const void* dk_bf16, const void* dv_bf16, const float* cos_tab, const float* sin_tab,
                          void* y_fp8, void* yT_fp8, const float* scale, float* amax, int64_t rows, int64_t seq, int n_q_heads,
                          int n_kv_heads, int head_dim, int fmt, void* stream);
+/*
+ * Per-head QK RMSNorm fused into the RoPE split (revision 6; HF Qwen3 `self_attn.q_norm` / `k_norm`, TE MultiheadAttention with
+ * qk_norm_type="RMSNorm", qk_norm_before_rope=True).  Layout as mi_rope_qkv: fused bf16 [rows, (n_q + 2 n_kv) * D], q / k / v
+ * separate and contiguous, cos_tab / sin_tab fp32 [>= seq, D/2], row r at position r % seq.  head_dim 64 or 128.
+ *   mi_qknorm_rope_qkv: per q / k head vector x (bf16 -> fp32): rstd = rsqrt(mean_D(x^2) + eps), n = (x * rstd) * gamma with gamma =
+ *     gamma_q / gamma_k (bf16 [D]); then the rotation out1 = n1 cos - n2 sin, out2 = n2 cos + n1 sin.  All arithmetic in fp32, one
+ *     round-to-nearest-even to bf16 at the store; v is copied.  rstd_out: fp32 [rows, n_q + n_kv] (q heads first), for backward.
+ *   mi_qknorm_rope_qkv_bwd: dn = conjugate rotation of the incoming head gradient (dn1 = d1 cos + d2 sin, dn2 = d2 cos - d1 sin),
+ *     g = gamma * dn, xhat = x * rstd (x from fused_x, the forward's input), dx = rstd * (g - xhat * mean_D(g * xhat)) into the
+ *     q | k columns of dfused; dv copied into its v columns.  dgamma_partial: fp32 [n_partials, 2 D]; the launch has n_partials
+ *     workgroups, workgroup p owns rows [p * ceil(rows / n_partials), ...) and writes row p = the sums of dn * xhat over its rows
+ *     and all q heads (columns 0 .. D-1) resp. all k heads (D .. 2D-1), zeros if it owns no row.  Fixed summation order, no
+ *     atomics: a given n_partials gives the same bits every run.  The caller finishes with mi_colsum_finish.
+ * MI_ERR_ARG before any launch: a null pointer, head_dim outside {64, 128}, rows < 0 or >= 2^31, seq <= 0, head counts < 1,
+ * n_partials < 1, a pointer that is not 16-byte aligned, eps negative or not finite.
+ */
+int mi_qknorm_rope_qkv(const void* fused_bf16, void* q_bf16, void* k_bf16, void* v_bf16, const void* gamma_q_bf16,
+                       const void* gamma_k_bf16, float* rstd_out, const float* cos_tab, const float* sin_tab, int64_t rows,
+                       int64_t seq, int n_q_heads, int n_kv_heads, int head_dim, float eps, void* stream);
+int mi_qknorm_rope_qkv_bwd(const void* dq_bf16, const void* dk_bf16, const void* dv_bf16, const void* fused_x_bf16,
+                           const float* rstd, const void* gamma_q_bf16, const void* gamma_k_bf16, const float* cos_tab,
+                           const float* sin_tab, void* dfused_bf16, float* dgamma_partial, int n_partials, int64_t rows,
+                           int64_t seq, int n_q_heads, int n_kv_heads, int head_dim, void* stream);
 
 /*
  * K10  SwiGLU fused with the FP8 cast of fc2's input  [TE LayerNormMLP activation="swiglu", te_llama.py:58-63].

@@ -59,7 +59,7 @@ def load_into(model: torch.nn.Module, path: str, config, strict: bool = False) -
     covered, fused, unexpected = set(), set(), set()
     hf_fused = ("input_layernorm.weight", "self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
                 "self_attn.o_proj.weight", "post_attention_layernorm.weight", "mlp.down_proj.weight", "mlp.gate_proj.weight",
-                "mlp.up_proj.weight")
+                "mlp.up_proj.weight", "self_attn.q_norm.weight", "self_attn.k_norm.weight")
     for shard in shards:
         state = load_shard(shard)
         replace_params(state, own, config, written=fused)    # parameters that live under fused TE names

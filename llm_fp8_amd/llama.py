@@ -84,12 +84,12 @@ def scenario_recipes(scenario: str):
 _ROPE_CACHE: Dict[tuple, torch.Tensor] = {}
 
 
-def _rope_table(dim: int, max_len: int, device) -> torch.Tensor:
-    """One shared RoPE angle table per (dim, length, device).  The reference builds one 131072-row table PER
+def _rope_table(dim: int, max_len: int, device, base: float = 10000.0) -> torch.Tensor:
+    """One shared RoPE angle table per (dim, length, device, base).  The reference builds one 131072-row table PER
     LAYER (te_llama.py:65-66); sharing it is value-identical and saves (L-1) x 64 MB of HBM on the 3B model."""
-    key = (dim, max_len, str(device))
+    key = (dim, max_len, str(device), float(base))
     if key not in _ROPE_CACHE:
-        _ROPE_CACHE[key] = te.attention.RotaryPositionEmbedding(dim)(max_seq_len=max_len).to(device)
+        _ROPE_CACHE[key] = te.attention.RotaryPositionEmbedding(dim, rotary_base=base)(max_seq_len=max_len).to(device)
     return _ROPE_CACHE[key]
 
 
@@ -107,7 +107,11 @@ class TELlamaDecoderLayer(torch.nn.Module):
 
     scenario = "default"
 
-    def __init__(self, config, *args, dropout_rate: float = 0.0, **kwargs):
+    def __init__(self, config, *args, dropout_rate: float = 0.0, _attention_kwargs: Optional[dict] = None,
+                 _mlp_kwargs: Optional[dict] = None, _rope_base: float = 10000.0, **kwargs):
+        """`_attention_kwargs` / `_mlp_kwargs` / `_rope_base`: for subclasses of another model family (qwen.TEQwen3DecoderLayer):
+        further MultiheadAttention / LayerNormMLP arguments and the rotary base (the reference's Llama layer leaves the MLP norm's
+        eps and the table's base at TE's defaults)."""
         super().__init__()
         dev = "cuda" if torch.cuda.is_available() else "cpu"
         self.attn_recipe, self.mlp_recipe = scenario_recipes(self.scenario)
@@ -124,6 +128,7 @@ class TELlamaDecoderLayer(torch.nn.Module):
             qkv_format="bshd",
             input_layernorm=True,
             device=dev,
+            **(_attention_kwargs or {}),
         )
         self.layernorm_mlp = te.LayerNormMLP(
             hidden_size=config.hidden_size,
@@ -131,9 +136,10 @@ class TELlamaDecoderLayer(torch.nn.Module):
             normalization="RMSNorm",
             activation="swiglu",
             device=dev,
+            **(_mlp_kwargs or {}),
         )
         head_dim = getattr(config, "head_dim", None) or config.hidden_size // config.num_attention_heads
-        self.te_rope_emb = _rope_table(head_dim, config.max_position_embeddings, dev)
+        self.te_rope_emb = _rope_table(head_dim, config.max_position_embeddings, dev, base=_rope_base)
 
     # "fused": the build's own wiring (private `_with_skip` / `_rstd` kwargs: residual gradient folded into the RMSNorm
     # backward, residual add fused with the next norm's statistics).  "reference": the call pattern of te_llama.py:76-81
@@ -322,6 +328,8 @@ def replace_params(hf_state_dict, te_state_dict, config, written: Optional[set] 
         "self_attn.o_proj.weight": "self_attention.proj.weight",
         "post_attention_layernorm.weight": "layernorm_mlp.layer_norm_weight",
         "mlp.down_proj.weight": "layernorm_mlp.fc2_weight",
+        "self_attn.q_norm.weight": "self_attention.q_norm.weight",  # Qwen3 only (qwen.py): absent from a Llama checkpoint
+        "self_attn.k_norm.weight": "self_attention.k_norm.weight",
     }
     f = config.intermediate_size
     with torch.no_grad():
@@ -358,6 +366,8 @@ def to_hf_state_dict(te_state_dict, config, keep_extra: bool = False):
         "self_attention.proj.weight": "self_attn.o_proj.weight",
         "layernorm_mlp.layer_norm_weight": "post_attention_layernorm.weight",
         "layernorm_mlp.fc2_weight": "mlp.down_proj.weight",
+        "self_attention.q_norm.weight": "self_attn.q_norm.weight",  # Qwen3 only (qwen.py)
+        "self_attention.k_norm.weight": "self_attn.k_norm.weight",
     }
     for k, v in te_state_dict.items():
         m = re.match(r"(model\.layers\.\d+\.)(.*)", k)

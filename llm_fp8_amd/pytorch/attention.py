@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .module import DyHandoff, LayerNormLinear, Linear, handoff_readers
+from .module import DyHandoff, LayerNormLinear, Linear, RMSNorm, handoff_readers
 
 __all__ = ["RotaryPositionEmbedding", "apply_rotary_pos_emb", "DotProductAttention", "MultiheadAttention"]
 
@@ -119,6 +119,31 @@ class _RoPESplitFn(torch.autograd.Function):
         return g.view(B, S, -1), None, None, None, None, None, None
 
 
+class _QKNormRoPESplitFn(torch.autograd.Function):
+    """_RoPESplitFn with the per-head RMSNorm of q and k (weights gq, gk [d]) in front of the rotation: one HIP launch each way
+    (mi_qknorm_rope_qkv / mi_qknorm_rope_qkv_bwd) plus the finish of the gamma partials.  Backward always writes the bf16 d(qkv):
+    there is no FP8-emitting form, so the caller withdraws the projection's DyHandoff."""
+
+    @staticmethod
+    def forward(ctx, qkv, gq, gk, cos, sin, n_q, n_kv, d, eps):
+        B, S, W = qkv.shape
+        x = qkv.reshape(B * S, W)
+        x = x if x.is_contiguous() else x.contiguous()
+        q, k, v, rstd = ops.qknorm_rope_qkv_forward(x, gq, gk, cos, sin, n_q, n_kv, d, S, eps)
+        ctx.save_for_backward(x, rstd, gq, gk, cos, sin)
+        ctx.meta = (B, S, n_q, n_kv, d)
+        return q.view(B, S, n_q, d), k.view(B, S, n_kv, d), v.view(B, S, n_kv, d)
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        x, rstd, gq, gk, cos, sin = ctx.saved_tensors
+        B, S, n_q, n_kv, d = ctx.meta
+        T = B * S
+        g, dgq, dgk = ops.qknorm_rope_qkv_backward(dq.reshape(T, n_q * d), dk.reshape(T, n_kv * d), dv.reshape(T, n_kv * d), x, rstd,
+                                                   gq, gk, cos, sin, n_q, n_kv, d, S, dgamma_dtype=gq.dtype)
+        return g.view(B, S, -1), dgq, dgk, None, None, None, None, None, None
+
+
 class _FlashAttnFn(torch.autograd.Function):
     """bshd attention core on mi_attn_fwd / mi_attn_bwd; saves q, k, v, o and the log-sum-exp, never the scores."""
 
@@ -194,10 +219,15 @@ class MultiheadAttention(torch.nn.Module):
                  input_layernorm: bool = False, attention_type: str = "self", fuse_qkv_params: bool = False,
                  zero_centered_gamma: bool = False, qkv_weight_interleaved: bool = True, bias: bool = True,
                  normalization: str = "LayerNorm", qkv_format: str = "sbhd", params_dtype=None, device="cuda",
-                 **_ignored):
+                 qk_norm_type: Optional[str] = None, qk_norm_eps: float = 1e-6, qk_norm_before_rope: bool = True, **_ignored):
         super().__init__()
         assert attention_type == "self", "only self-attention is on the reference path"
         assert qkv_format in ("sbhd", "bshd")
+        if qk_norm_type not in (None, "RMSNorm"):
+            raise NotImplementedError(f"qk_norm_type={qk_norm_type!r}: only None and 'RMSNorm' are implemented")
+        if not qk_norm_before_rope:
+            raise NotImplementedError("qk_norm_before_rope=False is not implemented: the QK norm is applied before RoPE")
+        self.qk_norm_type, self.qk_norm_eps = qk_norm_type, qk_norm_eps
         self.hidden_size, self.h = hidden_size, num_attention_heads
         self.d = kv_channels or hidden_size // num_attention_heads
         self.g = num_gqa_groups or num_attention_heads
@@ -219,6 +249,9 @@ class MultiheadAttention(torch.nn.Module):
         self.core_attention = DotProductAttention(self.h, self.d, self.g, attention_dropout, attn_mask_type, qkv_format)
         self.proj = Linear(q_out, hidden_size, bias=bias, params_dtype=params_dtype, device=device,
                            init_method=output_layer_init_method or init_method)
+        if qk_norm_type == "RMSNorm":  # per-head norm over head_dim (HF Qwen3 `q_norm` / `k_norm`): one weight [d] each
+            self.q_norm = RMSNorm(self.d, eps=qk_norm_eps, params_dtype=params_dtype, device=device)
+            self.k_norm = RMSNorm(self.d, eps=qk_norm_eps, params_dtype=params_dtype, device=device)
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 rotary_pos_emb=None, _with_skip: bool = False, _rstd=None, **_ignored):
@@ -235,7 +268,34 @@ class MultiheadAttention(torch.nn.Module):
         qkv = self.layernorm_qkv(hidden_states) if self.input_layernorm else self.qkv(hidden_states)
         return self._attend(qkv, attention_mask, rotary_pos_emb)
 
+    def _attend_qk_norm(self, qkv: torch.Tensor, attention_mask, rotary_pos_emb, handoff) -> torch.Tensor:
+        """`_attend` with the per-head RMSNorm of q and k in front of RoPE.  Neither route has an FP8-emitting backward, so the
+        q|k|v projection quantises its own grad_output: the hand-off is withdrawn on both."""
+        if handoff is not None:
+            handoff.withdraw()
+        gq, gk = self.q_norm.weight, self.k_norm.weight
+        if (rotary_pos_emb is not None and not isinstance(rotary_pos_emb, (tuple, list)) and qkv.is_cuda
+                and qkv.dtype == torch.bfloat16 and self.qkv_format == "bshd" and self.d in (64, 128)
+                and rotary_pos_emb.shape[-1] == self.d and gq.dtype == gk.dtype == torch.bfloat16
+                and os.environ.get("LLM_FP8_AMD_NO_QK_NORM_FUSION") != "1"):
+            cos, sin = _cos_sin_tables(rotary_pos_emb, qkv.shape[1])
+            q, k, v = _QKNormRoPESplitFn.apply(qkv, gq, gk, cos, sin, self.h, self.g, self.d, float(self.qk_norm_eps))
+            return self.proj(self.core_attention(q, k, v, attention_mask))
+        # the torch route (and the CPU route): split, norm on the [.., h, d] views, rotate
+        q, k, v = torch.split(qkv, self.split, dim=-1)
+        a, b = qkv.shape[0], qkv.shape[1]
+        q = self.q_norm(q.reshape(a, b, self.h, self.d)).to(qkv.dtype)  # (autocast runs the norm in fp32)
+        k = self.k_norm(k.reshape(a, b, self.g, self.d)).to(qkv.dtype)
+        v = v.reshape(a, b, self.g, self.d)
+        if rotary_pos_emb is not None:
+            fq, fk = rotary_pos_emb if isinstance(rotary_pos_emb, (tuple, list)) else (rotary_pos_emb, rotary_pos_emb)
+            q = apply_rotary_pos_emb(q, fq, self.qkv_format)
+            k = apply_rotary_pos_emb(k, fk, self.qkv_format)
+        return self.proj(self.core_attention(q, k, v, attention_mask))
+
     def _attend(self, qkv: torch.Tensor, attention_mask, rotary_pos_emb, handoff=None) -> torch.Tensor:
+        if self.qk_norm_type is not None:
+            return self._attend_qk_norm(qkv, attention_mask, rotary_pos_emb, handoff)
         if (rotary_pos_emb is not None and not isinstance(rotary_pos_emb, (tuple, list)) and qkv.is_cuda
                 and qkv.dtype == torch.bfloat16 and self.qkv_format == "bshd" and self.d % 16 == 0
                 and rotary_pos_emb.shape[-1] == self.d):

@@ -354,6 +354,50 @@ def rope_qkv_backward(dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor, cos:
     return out
 
 
+def qknorm_rope_qkv_forward(qkv: torch.Tensor, gamma_q: torch.Tensor, gamma_k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                            n_q: int, n_kv: int, head_dim: int, seq: int, eps: float):
+    """rope_qkv_forward with the per-head RMSNorm (over head_dim, weights gamma_q / gamma_k bf16 [D]) of every q and k head in
+    front of the rotation: (q, k, v, rstd fp32 [T, n_q + n_kv]).  head_dim 64 or 128."""
+    _dev(qkv, gamma_q, gamma_k, cos, sin)
+    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.dim() == 2
+    T, W = qkv.shape
+    assert W == (n_q + 2 * n_kv) * head_dim and cos.dtype == torch.float32 and cos.shape[-1] == head_dim // 2 and cos.shape[0] >= seq
+    assert sin.dtype == torch.float32 and sin.shape == cos.shape and cos.is_contiguous() and sin.is_contiguous()
+    for g in (gamma_q, gamma_k):
+        assert g.dtype == torch.bfloat16 and g.shape == (head_dim,) and g.is_contiguous()
+    q = torch.empty((T, n_q * head_dim), dtype=torch.bfloat16, device=qkv.device)
+    k = torch.empty((T, n_kv * head_dim), dtype=torch.bfloat16, device=qkv.device)
+    v = torch.empty((T, n_kv * head_dim), dtype=torch.bfloat16, device=qkv.device)
+    rstd = torch.empty((T, n_q + n_kv), dtype=torch.float32, device=qkv.device)
+    fn = _lib.require("mi_qknorm_rope_qkv", "the fused QK norm + RoPE split")
+    rc = fn(qkv.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), gamma_q.data_ptr(), gamma_k.data_ptr(), rstd.data_ptr(),
+            cos.data_ptr(), sin.data_ptr(), T, seq, n_q, n_kv, head_dim, float(eps), _stream())
+    _lib.check(rc, "mi_qknorm_rope_qkv")
+    return q, k, v, rstd
+
+
+def qknorm_rope_qkv_backward(dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor, qkv: torch.Tensor, rstd: torch.Tensor,
+                             gamma_q: torch.Tensor, gamma_k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_q: int,
+                             n_kv: int, head_dim: int, seq: int, n_partials: int = 1024, dgamma_dtype: torch.dtype = torch.float32):
+    """Backward of qknorm_rope_qkv_forward: (d(qkv) bf16 [T, W], dgamma_q [D], dgamma_k [D] in `dgamma_dtype`).  The gamma
+    gradients are fixed-order sums of per-workgroup partials (the same bits every run for the same shape)."""
+    _dev(dq, dk, dv, qkv, rstd, gamma_q, gamma_k, cos, sin)
+    dq, dk, dv = (t.contiguous() for t in (dq, dk, dv))
+    assert dq.dtype == dk.dtype == dv.dtype == qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and rstd.dtype == torch.float32
+    T, W = qkv.shape
+    assert W == (n_q + 2 * n_kv) * head_dim and dq.numel() == T * n_q * head_dim and dk.numel() == dv.numel() == T * n_kv * head_dim
+    assert rstd.is_contiguous() and rstd.numel() == T * (n_q + n_kv)
+    n_partials = max(1, min(n_partials, (T + 3) // 4))
+    out = torch.empty((T, W), dtype=torch.bfloat16, device=qkv.device)
+    part = torch.empty((n_partials, 2 * head_dim), dtype=torch.float32, device=qkv.device)
+    fn = _lib.require("mi_qknorm_rope_qkv_bwd", "the fused QK norm + RoPE split")
+    rc = fn(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), qkv.data_ptr(), rstd.data_ptr(), gamma_q.data_ptr(), gamma_k.data_ptr(),
+            cos.data_ptr(), sin.data_ptr(), out.data_ptr(), part.data_ptr(), n_partials, T, seq, n_q, n_kv, head_dim, _stream())
+    _lib.check(rc, "mi_qknorm_rope_qkv_bwd")
+    dg = colsum_finish(part, dgamma_dtype)
+    return out, dg[:head_dim], dg[head_dim:]
+
+
 def mxfp8_rope_bwd_quantize(dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_q: int,
                             n_kv: int, head_dim: int, seq: int, fmt: int, rowwise: bool = True, colwise: bool = True):
     """rope_qkv_backward + mxfp8_quantize of its result in one launch (same four outputs); the bf16 d(qkv) is never written."""

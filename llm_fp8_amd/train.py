@@ -52,21 +52,31 @@ class TrainingConfig:
 
 def create_model(cfg: TrainingConfig, device) -> torch.nn.Module:
     """ModelManager.create_model (train_fp8.py:83-124): TE-style wrapper when --use_te, else plain HF bf16."""
-    from transformers.models.llama.modeling_llama import LlamaForCausalLM
     over = {}
     if cfg.num_hidden_layers is not None:
         over["num_hidden_layers"] = cfg.num_hidden_layers
     if cfg.vocab_size is not None:
         over["vocab_size"] = cfg.vocab_size
-    config = llama.llama_config(cfg.model_name, **over)
+    # the family follows the name: `qwen3...` / `qwen/qwen3...` is Qwen3 (qwen.py), everything else Llama
+    from . import qwen
+    try:
+        if qwen.is_qwen3_name(cfg.model_name):
+            from transformers.models.qwen3.modeling_qwen3 import Qwen3ForCausalLM as hf_cls
+            config, te_cls = qwen.qwen3_config(cfg.model_name, **over), qwen.TEQwen3ForCausalLM
+        else:
+            from transformers.models.llama.modeling_llama import LlamaForCausalLM as hf_cls
+            config, te_cls = llama.llama_config(cfg.model_name, **over), llama.TELlamaForCausalLM
+    except KeyError:
+        raise KeyError(f"unknown model {cfg.model_name!r}; known: {sorted(llama.LLAMA_CONFIGS)} (Llama), "
+                       f"{sorted(qwen.QWEN3_CONFIGS)} (Qwen3)") from None
     prev = torch.get_default_dtype()
     torch.set_default_dtype(torch.bfloat16)
     try:
         with torch.device(device):
             if cfg.use_te:
-                model = llama.TELlamaForCausalLM(config, cfg.fp8_scenario)
+                model = te_cls(config, cfg.fp8_scenario)
             else:
-                model = LlamaForCausalLM(config)
+                model = hf_cls(config)
     finally:
         torch.set_default_dtype(prev)
     model.to(device)
@@ -198,7 +208,8 @@ def wrap_distributed(model: torch.nn.Module, cfg: TrainingConfig, device) -> tor
         from torch.distributed.fsdp import BackwardPrefetch, FullyShardedDataParallel as FSDP, MixedPrecision, ShardingStrategy
         from torch.distributed.fsdp.wrap import transformer_auto_wrap_policy
         from transformers.models.llama.modeling_llama import LlamaDecoderLayer
-        layer_cls = {llama.TELlamaDecoderLayer, LlamaDecoderLayer}
+        from transformers.models.qwen3.modeling_qwen3 import Qwen3DecoderLayer
+        layer_cls = {llama.TELlamaDecoderLayer, LlamaDecoderLayer, Qwen3DecoderLayer}  # (TEQwen3DecoderLayer is a TELlamaDecoderLayer)
         policy = functools.partial(transformer_auto_wrap_policy, transformer_layer_cls=layer_cls)
         mp = MixedPrecision(param_dtype=torch.bfloat16, reduce_dtype=torch.bfloat16, buffer_dtype=torch.bfloat16)
         return FSDP(model, sharding_strategy=ShardingStrategy.FULL_SHARD, auto_wrap_policy=policy, mixed_precision=mp,
