@@ -5,7 +5,8 @@ Mirrors the behaviour of `transformer_engine.pytorch.fp8` that the reference rel
     autocast, utils/transformer_engine.py:129-134);
   * forward amaxes are reduced and ALL forward scales updated when the OUTERMOST autocast exits with
     grad enabled; backward scales are updated after the backward of the first FP8 module that ran in
-    that outermost region (SURVEY.md Appendix A "Scale update");
+    that outermost region (SURVEY.md Appendix A "Scale update") -- the first that HAS a backward: frozen
+    modules at the bottom of the model pass the duty on;
   * with torch.distributed initialised and `recipe.reduce_amax`, the amax vector is MAX-all-reduced
     (one RCCL call per direction per step) before the update.
 
@@ -164,7 +165,8 @@ class FP8GlobalStateManager:
 
     @classmethod
     def is_first_fp8_module(cls) -> bool:
-        """True exactly once per outermost autocast region (its first FP8 module's backward runs last)."""
+        """True exactly once per outermost autocast region.  Asked by the GEMM Functions that will have a backward
+        (module._claim_bwd_update): the first of them runs its backward last and carries the backward scale update."""
         tmp = cls.IS_FIRST_FP8_MODULE
         cls.IS_FIRST_FP8_MODULE = False
         return tmp

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import io
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -702,6 +702,60 @@ def _skip_2d(dskip: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torc
     return d if (d.dtype == torch.bfloat16 and d.is_contiguous()) else d.to(torch.bfloat16).contiguous()
 
 
+class LinearPlan(NamedTuple):
+    """What one FP8 Linear node computes and keeps, decided once from which of its inputs need a gradient."""
+    dgrad: bool     # the dX GEMM (and the RMSNorm backward of a fused norm): the input or the norm weight needs a gradient
+    wgrad: bool     # the dW GEMM: any weight part needs one
+    dbias: bool     # column sums of grad_output
+    x_col: bool     # forward keeps the column-wise copy of the input (wgrad's operand)
+    w_col: bool     # forward makes and keeps the column-wise copy of the weight (dgrad's operand)
+
+
+def linear_plan(need_x: bool, need_bias: bool, need_ln: bool, need_w: bool) -> LinearPlan:
+    dgrad, wgrad = bool(need_x or need_ln), bool(need_w)
+    return LinearPlan(dgrad, wgrad, bool(need_bias), x_col=wgrad, w_col=dgrad)
+
+
+class MLPPlan(NamedTuple):
+    """The same for the fused fc1 -> SwiGLU -> fc2 node.  `dact`: anything upstream of the activation needs a gradient, so the
+    fc2 dgrad GEMM and dSwiGLU run; without it (only fc2's own parameters train) backward ends at fc2."""
+    dgrad: bool     # fc1's dX GEMM (+ RMSNorm backward)
+    w1: bool        # fc1's dW GEMM
+    b1: bool
+    w2: bool        # fc2's dW GEMM
+    b2: bool
+    dact: bool
+    x_col: bool     # forward keeps: column-wise input (fc1 wgrad)
+    w1_col: bool    # ... column-wise fc1 weight (fc1 dgrad)
+    h: bool         # ... the fc1 output (dSwiGLU)
+    a_col: bool     # ... column-wise activation (fc2 wgrad)
+    w2_col: bool    # ... column-wise fc2 weight (fc2 dgrad)
+
+
+def mlp_plan(need_x: bool, need_w1: bool, need_b1: bool, need_w2: bool, need_b2: bool, need_ln: bool) -> MLPPlan:
+    dgrad, w1, b1, w2, b2 = bool(need_x or need_ln), bool(need_w1), bool(need_b1), bool(need_w2), bool(need_b2)
+    dact = dgrad or w1 or b1
+    return MLPPlan(dgrad, w1, b1, w2, b2, dact, x_col=w1, w1_col=dgrad, h=dact, a_col=w2, w2_col=dact)
+
+
+def grad_copies(need_row: bool, need_col: bool, colsum: bool) -> Optional[Tuple[bool, bool]]:
+    """(row-wise, column-wise): the FP8 copies of a grad_output to ask its quantiser for -- `need_row` for the dgrad GEMM, `need_col`
+    for the wgrad GEMM, `colsum` when a bias gradient rides on the pass.  None: nothing to do.  No cast kernel has a form that
+    writes neither copy (they refuse it), so column sums alone ride on the row-wise one: the bias gradient stays the fixed-order
+    sum it is on every other pattern, and the site's amax is published as always."""
+    if need_row or need_col:
+        return need_row, need_col
+    return (True, False) if colsum else None
+
+
+def _claim_bwd_update(ctx, spec: _GemmSpec) -> None:
+    """The first GEMM Function of the outermost autocast region THAT WILL HAVE A BACKWARD carries the delayed-scaling backward
+    update: every later Function consumes (part of) its output, so its backward is the region's last.  A Function none of whose
+    inputs needs a gradient (a frozen module fed by a frozen embedding) has no backward and leaves the claim to the next."""
+    if any(ctx.needs_input_grad):
+        spec.trigger_bwd_update = FP8GlobalStateManager.is_first_fp8_module()
+
+
 def _quantize_input(ctx, spec: _GemmSpec, x2, ln_w, want_t: bool, need_dgrad: bool):
     """The input of GEMM spec.g as an FP8 operand.  `ln_w` (with spec.eps): K9 -- x2 is the UN-normalised input and RMSNorm is
     fused into its quantisation; ctx.norm keeps what the RMSNorm backward needs."""
@@ -736,7 +790,7 @@ def _finish_dx(ctx, dx, dskip, colsums=None):
             colsums = [None if t is None else next(done) for t in colsums]
             dln = None if dln is None else next(done)
     if ctx.spec.trigger_bwd_update:
-        # this GEMM belongs to the first FP8 module of the outermost autocast: its backward is the last
+        # this is the first GEMM Function of the outermost autocast that has a backward (_claim_bwd_update): its backward is the last
         FP8GlobalStateManager.reduce_and_update_fp8_tensors(forward=False)
     if dx is not None:
         dx = dx.view(ctx.x_shape).to(ctx.x_dtype)
@@ -760,10 +814,12 @@ class _FP8LinearFn(torch.autograd.Function):
         N = sum(ns)
         q, g = spec.q, spec.g
         # (forward runs in no-grad mode; needs_input_grad is all-False when grad was disabled at apply time)
-        need_dgrad = bool(ctx.needs_input_grad[0]) or bool(ctx.needs_input_grad[3])
-        need_wgrad = any(ctx.needs_input_grad[4:])
-        x8 = _quantize_input(ctx, spec, x2, ln_w, need_wgrad, need_dgrad)
-        w8 = _weight_operand(spec, g, weights, ns, N, K, x2.device, need_dgrad)
+        nig = ctx.needs_input_grad
+        plan = linear_plan(nig[0], nig[1], nig[3], any(nig[4:]))
+        need_dgrad, need_wgrad = plan.dgrad, plan.wgrad
+        _claim_bwd_update(ctx, spec)
+        x8 = _quantize_input(ctx, spec, x2, ln_w, plan.x_col, need_dgrad)
+        w8 = _weight_operand(spec, g, weights, ns, N, K, x2.device, plan.w_col)
         y = q.gemm(x8[0], w8[0], None if bias is None else bias.to(torch.bfloat16).contiguous())
         ctx.saved_fp8 = (x8[1], w8[1])
         if spec.dy_handoff is not None and bias is None and (need_wgrad or need_dgrad):
@@ -771,8 +827,8 @@ class _FP8LinearFn(torch.autograd.Function):
         ctx.spec, ctx.ns, ctx.x_shape, ctx.x_dtype = spec, ns, x.shape, x.dtype
         ctx.w_dtypes = [w.dtype for w in weights]
         ctx.w_refs = weights if need_wgrad else None  # the Parameters themselves (not saved tensors): for _wgrad_out
-        ctx.has_bias, ctx.bias_dtype = bias is not None, (None if bias is None else bias.dtype)
-        ctx.need_wgrad, ctx.need_dgrad = need_wgrad, need_dgrad
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.plan = plan
         if spec.with_skip:
             ctx.set_materialize_grads(False)
             return y.view(*x.shape[:-1], N), x
@@ -785,17 +841,22 @@ class _FP8LinearFn(torch.autograd.Function):
         g2 = _as_bf16_2d(dy)
         x_col, w_col = ctx.saved_fp8
         ctx.saved_fp8 = None
-        db = None
+        plan = ctx.plan
+        db, dx, dw = None, None, None
+        ride = plan.dbias and (q.colsum_dtypes is None or ctx.bias_dtype in q.colsum_dtypes)  # the bias gradient rides on the cast
+        copies = grad_copies(plan.dgrad, plan.wgrad, ride)
         if spec.dy_handoff is not None and spec.dy_handoff.fp8 is not None:
             grad = q.taken(spec.dy_handoff.take(dy), g)  # already quantised by the op that produced it (dy is a placeholder)
-        elif ctx.has_bias and (q.colsum_dtypes is None or ctx.bias_dtype in q.colsum_dtypes):  # the bias gradient rides on it
-            grad = q.quantize_grad(g2, g, ctx.need_dgrad, ctx.need_wgrad, colsum=True)
-            db = ops.colsum_finish(grad[2], ctx.bias_dtype)
+        elif copies is None:
+            grad = None                                  # only a bias gradient no quantiser pass can carry is wanted
         else:
-            grad = q.quantize_grad(g2, g, ctx.need_dgrad, ctx.need_wgrad)
-        dx, dw = _grouped_or_two(q, grad, w_col, x_col, _wgrad_out(ctx.w_refs, x_col[0].shape[0]) if ctx.need_wgrad else None,
-                                 ctx.need_dgrad, ctx.need_wgrad)
-        if ctx.has_bias and db is None:
+            grad = q.quantize_grad(g2, g, *copies, colsum=ride)
+            if ride:
+                db = ops.colsum_finish(grad[2], ctx.bias_dtype)
+        if plan.dgrad or plan.wgrad:
+            dx, dw = _grouped_or_two(q, grad, w_col, x_col, _wgrad_out(ctx.w_refs, x_col[0].shape[0]) if plan.wgrad else None,
+                                     plan.dgrad, plan.wgrad)
+        if plan.dbias and db is None:
             db = g2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
         dx, dln, _ = _finish_dx(ctx, dx, dskip)
         dws: List[Optional[torch.Tensor]] = [None] * len(ctx.ns)
@@ -817,26 +878,27 @@ class _FP8SwiGLUMLPFn(torch.autograd.Function):
         if M % 8 or K % 16:
             raise RuntimeError(f"FP8 LayerNormMLP needs tokens % 8 == 0 and hidden % 16 == 0, got {M} x {K}")
         q, dev = spec.q, x2.device
-        need_dgrad = bool(ctx.needs_input_grad[0]) or bool(ctx.needs_input_grad[6])
-        need_w = bool(ctx.needs_input_grad[1]) or bool(ctx.needs_input_grad[3])
-        bwd = need_dgrad or need_w
-        x8 = _quantize_input(ctx, spec, x2, ln_w, need_w, need_dgrad)
-        w1_8 = _weight_operand(spec, 0, (w1,), [w1.shape[0]], w1.shape[0], K, dev, bwd)
+        nig = ctx.needs_input_grad
+        # (the unfused route applies this Function without `ln_w`: needs_input_grad then has six entries)
+        plan = mlp_plan(nig[0], nig[1], nig[2], nig[3], nig[4], len(nig) > 6 and nig[6])
+        _claim_bwd_update(ctx, spec)
+        x8 = _quantize_input(ctx, spec, x2, ln_w, plan.x_col, plan.dgrad)
+        w1_8 = _weight_operand(spec, 0, (w1,), [w1.shape[0]], w1.shape[0], K, dev, plan.w1_col)
         # fc1: where the SwiGLU kernels take a bias the GEMM leaves it out and they add it (fp32) to the gate / up values they
         # unpack anyway; else it stays in the GEMM's epilogue
         b1_bf = None if b1 is None else b1.detach().to(torch.bfloat16).contiguous()
         fuse_b1 = b1_bf is not None and q.swiglu_adds_bias and _FUSE_MLP_BIAS and (b1_bf.data_ptr() % 16 == 0)
         h = q.gemm(x8[0], w1_8[0], None if fuse_b1 else b1_bf)
-        a8 = q.swiglu(h, 1, need_w, b1_bf if fuse_b1 else None)
+        a8 = q.swiglu(h, 1, plan.a_col, b1_bf if fuse_b1 else None)
         ctx.b1_fused = b1_bf if fuse_b1 else None
-        w2_8 = _weight_operand(spec, 1, (w2,), [w2.shape[0]], w2.shape[0], w2.shape[1], dev, bwd)
+        w2_8 = _weight_operand(spec, 1, (w2,), [w2.shape[0]], w2.shape[0], w2.shape[1], dev, plan.w2_col)
         # fc2: with defer_bias the caller adds the bias in its residual add (LayerNormMLP.forward hands it over)
         y = q.gemm(a8[0], w2_8[0], None if (b2 is None or spec.defer_bias) else b2.to(torch.bfloat16).contiguous())
-        ctx.saved_fp8 = (x8[1], w1_8[1], a8[1], w2_8[1], h if bwd else None)
+        ctx.saved_fp8 = (x8[1], w1_8[1], a8[1], w2_8[1], h if plan.h else None)
         ctx.spec, ctx.x_shape, ctx.x_dtype = spec, x.shape, x.dtype
         ctx.dtypes = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype)
-        ctx.need_dgrad, ctx.need_w = need_dgrad, need_w
-        ctx.w_refs = (w1, w2) if need_w else None  # the Parameters themselves: for _wgrad_out
+        ctx.plan = plan
+        ctx.w_refs = (w1, w2) if (plan.w1 or plan.w2) else None  # the Parameters themselves: for _wgrad_out
         if spec.with_skip:
             ctx.set_materialize_grads(False)
             return y.view(*x.shape[:-1], w2.shape[0]), x
@@ -848,16 +910,23 @@ class _FP8SwiGLUMLPFn(torch.autograd.Function):
         x_col, w1_col, a_col, w2_col, h = ctx.saved_fp8
         ctx.saved_fp8 = None
         dt_w1, dt_b1, dt_w2, dt_b2 = ctx.dtypes
+        plan = ctx.plan
+        db1 = db2 = dact = dw2 = dx = dw1 = None
         # fc2 backward (GEMM 1); its bias gradient rides on the quantisation of dy
-        grad = q.quantize_grad(_as_bf16_2d(dy), 1, True, ctx.need_w, colsum=dt_b2 is not None)
-        db2 = None if dt_b2 is None else (grad[2], dt_b2)  # partial sums: finished with the layer's other column sums in _finish_dx
-        dact, dw2 = _grouped_or_two(q, grad, w2_col, a_col, _wgrad_out(ctx.w_refs[1:], a_col[0].shape[0]) if ctx.need_w else None,
-                                    True, ctx.need_w)
-        # dSwiGLU + quantisation of fc1's grad_output (GEMM 0) + fc1 bias gradient
-        grad = q.dswiglu(h, dact, 0, ctx.need_dgrad, ctx.need_w, dt_b1 is not None, ctx.b1_fused)
-        db1 = None if dt_b1 is None else (grad[2], dt_b1)
-        dx, dw1 = _grouped_or_two(q, grad, w1_col, x_col, _wgrad_out(ctx.w_refs[:1], x_col[0].shape[0]) if ctx.need_w else None,
-                                  ctx.need_dgrad, ctx.need_w)
+        grad = q.quantize_grad(_as_bf16_2d(dy), 1, *grad_copies(plan.dact, plan.w2, plan.b2), colsum=plan.b2)
+        if plan.b2:
+            db2 = (grad[2], dt_b2)  # partial sums: finished with the layer's other column sums in _finish_dx
+        if plan.dact or plan.w2:
+            dact, dw2 = _grouped_or_two(q, grad, w2_col, a_col, _wgrad_out(ctx.w_refs[1:], a_col[0].shape[0]) if plan.w2 else None,
+                                        plan.dact, plan.w2)
+        if plan.dact:
+            # dSwiGLU + quantisation of fc1's grad_output (GEMM 0) + fc1 bias gradient
+            grad = q.dswiglu(h, dact, 0, *grad_copies(plan.dgrad, plan.w1, plan.b1), plan.b1, ctx.b1_fused)
+            if plan.b1:
+                db1 = (grad[2], dt_b1)
+            if plan.dgrad or plan.w1:
+                dx, dw1 = _grouped_or_two(q, grad, w1_col, x_col, _wgrad_out(ctx.w_refs[:1], x_col[0].shape[0]) if plan.w1 else None,
+                                          plan.dgrad, plan.w1)
         dx, dln, (db1, db2) = _finish_dx(ctx, dx, dskip, (db1, db2))
         if dw1 is not None and dw1.dtype != dt_w1:
             dw1 = dw1.to(dt_w1)
@@ -884,26 +953,25 @@ class _FP8Module(torch.nn.Module):
         self.default_is_first_microbatch = None
 
     def _spec(self, st, is_first_microbatch, g: int = 0, eps: float = 1e-5, **kw) -> _GemmSpec:
-        """The spec of this module's GEMM `g` from what _prepare returned.  GEMM 0's backward is the module's last FP8 op: it
-        carries the update trigger."""
-        recipe, mf, mb, first = st
+        """The spec of this module's GEMM `g` from what _prepare returned.  (Which Function carries the backward update trigger is
+        settled in its forward: _claim_bwd_update.)"""
+        recipe, mf, mb = st
         if is_first_microbatch is None:
             is_first_microbatch = self.default_is_first_microbatch
-        return _GemmSpec(recipe, mf, mb, g, first and g == 0, self.training, eps, self._wcache, is_first_microbatch, **kw)
+        return _GemmSpec(recipe, mf, mb, g, False, self.training, eps, self._wcache, is_first_microbatch, **kw)
 
     def _norm(self, x):  # (the modules with a norm in front)
         if self.normalization == "RMSNorm":
             return _rmsnorm(x, self.layer_norm_weight, self.eps, self.zero_centered_gamma)
         return _layernorm(x, self.layer_norm_weight, self.layer_norm_bias, self.eps, self.zero_centered_gamma)
 
-    def _prepare(self, device) -> Optional[Tuple[Recipe, Optional[ModuleMeta], Optional[ModuleMeta], bool]]:
+    def _prepare(self, device) -> Optional[Tuple[Recipe, Optional[ModuleMeta], Optional[ModuleMeta]]]:
         """Called at the top of forward.  None -> run the plain bf16 path."""
         if not FP8GlobalStateManager.is_fp8_enabled():
             return None
         recipe = FP8GlobalStateManager.get_fp8_recipe()
-        first = FP8GlobalStateManager.is_first_fp8_module()
         if recipe.mxfp8() or recipe.current() or recipe.block():  # no state: no meta windows, no arenas, an empty _extra_state
-            return recipe, None, None, first
+            return recipe, None, None
         key = (recipe.fp8_format, recipe.amax_history_len, recipe.amax_compute_algo, recipe.margin, str(device))
         if self._meta_key != key:
             fa = FP8GlobalStateManager.arena(recipe, True, device)
@@ -918,7 +986,7 @@ class _FP8Module(torch.nn.Module):
         else:  # arenas may carry a new group / reduce flag
             FP8GlobalStateManager.arena(recipe, True, device)
             FP8GlobalStateManager.arena(recipe, False, device)
-        return recipe, self._meta_fwd, self._meta_bwd, first
+        return recipe, self._meta_fwd, self._meta_bwd
 
     def get_extra_state(self):
         if self._meta_fwd is None:
