@@ -124,16 +124,21 @@ class ModuleMeta:
         return {"scale": a.scale[s:s + n].clone(), "scale_inv": a.scale_inv[s:s + n].clone(),
                 "amax_history": a.hist[:, s:s + n].clone()}
 
+    @staticmethod
+    def check_history(st: Dict[str, torch.Tensor], H: int) -> None:
+        """A state saved under another amax_history_len does not fit the arena: refuse it before anything is written."""
+        h = st["amax_history"]
+        if h.shape[0] != H:
+            raise RuntimeError(f"amax history length {h.shape[0]} in checkpoint != recipe's {H}")
+
     def load_state(self, st: Dict[str, torch.Tensor]) -> None:
         a, s, n = self.arena, self.start, self.n
+        self.check_history(st, a.H)
         a._snap = None
         a.generation += 1
         a.scale[s:s + n].copy_(st["scale"])
         a.scale_inv[s:s + n].copy_(st["scale_inv"])
-        h = st["amax_history"]
-        if h.shape[0] != a.H:
-            raise RuntimeError(f"amax history length {h.shape[0]} in checkpoint != recipe's {a.H}")
-        a.hist[:, s:s + n].copy_(h)
+        a.hist[:, s:s + n].copy_(st["amax_history"])
 
 
 class FP8GlobalStateManager:

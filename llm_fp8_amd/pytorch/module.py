@@ -974,6 +974,9 @@ class _FP8Module(torch.nn.Module):
             return recipe, None, None
         key = (recipe.fp8_format, recipe.amax_history_len, recipe.amax_compute_algo, recipe.margin, str(device))
         if self._meta_key != key:
+            if self._pending_state is not None:  # before any slot is taken: a refused state leaves the arenas and this module as they were
+                for d in ("fwd", "bwd"):
+                    ModuleMeta.check_history(self._pending_state[d], recipe.amax_history_len)
             fa = FP8GlobalStateManager.arena(recipe, True, device)
             ba = FP8GlobalStateManager.arena(recipe, False, device)
             self._meta_fwd = ModuleMeta(fa, fa.alloc(3 * self.num_gemms), 3 * self.num_gemms)
@@ -989,11 +992,16 @@ class _FP8Module(torch.nn.Module):
         return recipe, self._meta_fwd, self._meta_bwd
 
     def get_extra_state(self):
-        if self._meta_fwd is None:
+        to_cpu = lambda d: {k: v.cpu() for k, v in d.items()}
+        if self._meta_fwd is not None:
+            st = {"fwd": to_cpu(self._meta_fwd.state()), "bwd": to_cpu(self._meta_bwd.state())}
+        elif self._pending_state is not None:
+            # loaded, no FP8 forward yet (the meta windows do not exist): a save now must carry what was loaded, not drop it
+            st = {"fwd": to_cpu(self._pending_state["fwd"]), "bwd": to_cpu(self._pending_state["bwd"])}
+        else:
             return torch.empty(0, dtype=torch.uint8)
         buf = io.BytesIO()
-        to_cpu = lambda d: {k: v.cpu() for k, v in d.items()}
-        torch.save({"fwd": to_cpu(self._meta_fwd.state()), "bwd": to_cpu(self._meta_bwd.state())}, buf)
+        torch.save(st, buf)
         return torch.frombuffer(bytearray(buf.getvalue()), dtype=torch.uint8)
 
     def set_extra_state(self, state):

@@ -99,6 +99,19 @@ def save_model(model, cfg: TrainingConfig, layout: str = "hf"):
     return checkpoint.save_pretrained(checkpoint.unwrap(model), cfg.output_dir, layout=layout, save_fp8_state=True)
 
 
+def check_save_layout(model, layout: str) -> None:
+    """Refuse, before any step is spent, a run whose save cannot succeed: the HF layout has no place for the TE-only MLP biases
+    (llama.to_hf_state_dict refuses them once they are non-zero), and a trainable one is non-zero after the first step."""
+    if layout != "hf":
+        return
+    biases = [n for n, p in model.named_parameters()
+              if p.requires_grad and n.endswith(("layernorm_mlp.fc1_bias", "layernorm_mlp.fc2_bias"))]
+    if biases:
+        raise ValueError(f"--save_layout hf cannot hold the {len(biases)} trainable TE-only MLP biases ({biases[0]} ...): HF Llama has no "
+                         "MLP bias, so the save after the last step would be refused.  Use --save_layout te (the module tree's own "
+                         "names, FP8 state included), or freeze these biases")
+
+
 def prepare_model(model: torch.nn.Module, cfg: TrainingConfig) -> torch.nn.Module:
     """Accelerator.prepare's model steps for mixed_precision in {bf16, fp8}."""
     if cfg.mixed_precision == "fp8":
@@ -371,7 +384,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--gradient_accumulation_steps", type=int, default=1)
     ap.add_argument("--output_dir", default=None, help="save config.json + safetensors (HF parameter names) here after training")
     ap.add_argument("--load_dir", default=None, help="local checkpoint directory (model.safetensors[.index.json]) to start from")
-    ap.add_argument("--save_layout", choices=["hf", "te"], default="hf")
+    ap.add_argument("--save_layout", choices=["hf", "te"], default="hf",
+                    help="hf: HF parameter names (+ fp8_extra_state.safetensors); refused up front with --use_te while the TE-only MLP "
+                         "biases train, which HF Llama cannot hold | te: the module tree's own names, biases and FP8 state included")
     ap.add_argument("--repeat_batch", action="store_true", help="debug: train on one fixed synthetic batch")
     ap.add_argument("--optimizer_state", choices=OPTIMIZER_STATES, default=None,
                     help="precision of the AdamW state: bf16 (default; or $LLM_FP8_AMD_OPT_STATE) | fp32 master weights + moments | "
@@ -396,6 +411,8 @@ def main(argv=None):
     rank, local, world, device = setup_distributed()
     torch.manual_seed(cfg.seed + rank)
     model = prepare_model(create_model(cfg, device), cfg)
+    if cfg.output_dir:
+        check_save_layout(model, a.save_layout)
     vocab = model.config.vocab_size
     model = wrap_distributed(model, cfg, device)
     opt, sched = create_optimizer(model, cfg)

@@ -136,6 +136,42 @@ def test_train_harness_saves_and_reloads(tmp_path):
     train.main(args + ["--load_dir", str(out), "--use_te"])  # TE-layer model started from the saved HF-layout checkpoint
 
 
+def test_train_harness_refuses_an_unsavable_layout_before_the_first_step(tmp_path, capsys, monkeypatch):
+    """--use_te trains the TE-only MLP biases, which the HF layout (the default --save_layout) cannot hold: the run must say so
+    before it spends a step, not after its last one; with --save_layout te it saves, and a second run starts from the files."""
+    from safetensors.torch import load_file
+    from llm_fp8_amd import train
+    args = ["--model_name", "llama-3.2-1b", "--batch_size", "1", "--max_seq_length", "16", "--mixed_precision", "bf16", "--use_te",
+            "--num_hidden_layers", "1", "--vocab_size", "256", "--num_steps", "2", "--sharding_mode", "none"]
+    capsys.readouterr()
+    with pytest.raises(ValueError, match="--save_layout te"):
+        train.main(args + ["--output_dir", str(tmp_path / "hf")])
+    assert '"step"' not in capsys.readouterr().out, "the harness trained before it refused"
+    assert not (tmp_path / "hf").exists()
+    out = tmp_path / "te"
+    train.main(args + ["--output_dir", str(out), "--save_layout", "te"])
+    printed = capsys.readouterr().out
+    assert printed.count('"step"') == 2 and '"saved"' in printed
+    saved = load_file(str(out / "model.safetensors"))
+    bias = saved["model.layers.0.layernorm_mlp.fc1_bias"]
+    assert bool(torch.count_nonzero(bias)), "the bias did not train: the refusal above would have been for nothing"
+    seen = {}
+    real = train.create_optimizer
+
+    def spy(model, cfg):
+        seen.update({n: p.detach().clone() for n, p in model.named_parameters()})
+        return real(model, cfg)
+
+    monkeypatch.setattr(train, "create_optimizer", spy)
+    train.main(args + ["--load_dir", str(out), "--num_steps", "1"])
+    assert '"step": 0' in capsys.readouterr().out
+    assert len(seen) > 0
+    for n, p in seen.items():  # what the second run started from: the files, bit for bit (lm_head.weight is tied, not stored)
+        if n in saved:
+            assert torch.equal(p.view(torch.int16), saved[n].view(torch.int16)), n
+    assert "model.layers.0.layernorm_mlp.fc1_bias" in seen and "model.layers.0.self_attention.proj.weight" in seen
+
+
 def test_gradient_accumulation_matches_the_large_batch():
     """train_step with N micro-batches = one step on the N x batch (loss / N, one optimiser step; train_multi_gpu.py:661,714-737)."""
     from llm_fp8_amd import train

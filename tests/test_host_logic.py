@@ -172,3 +172,78 @@ def test_sink_stamp_follows_the_shard_of_a_row_sharded_weight():
             if isinstance(sink, WeightSink):
                 arena.generation += 1
                 assert not sink.fresh()
+
+
+def _extra_blob(n_fwd=3, n_bwd=2, H=16, seed=0):
+    """A blob with the layout of _FP8Module.get_extra_state for a one-GEMM module, filled with values no default state has."""
+    import io
+    g = torch.Generator().manual_seed(seed)
+    side = lambda n: {"scale": 1 + torch.rand(n, generator=g), "scale_inv": 0.1 + torch.rand(n, generator=g),
+                      "amax_history": torch.rand(H, n, generator=g)}
+    st = {"fwd": side(n_fwd), "bwd": side(n_bwd)}
+    buf = io.BytesIO()
+    torch.save(st, buf)
+    return st, torch.frombuffer(bytearray(buf.getvalue()), dtype=torch.uint8)
+
+
+def _decode_extra(blob):
+    import io
+    return torch.load(io.BytesIO(blob.cpu().numpy().tobytes()), weights_only=True)
+
+
+def test_loaded_fp8_state_survives_a_save_before_the_first_forward():
+    """set_extra_state parks the blob until the first FP8 forward allocates the meta windows.  A save in between (a layout
+    conversion, a checkpoint at step 0) must write what was loaded, not an empty tensor: load -> state_dict() -> load into a third
+    module carries every scale and the whole amax history."""
+    import llm_fp8_amd.pytorch as te
+    st, blob = _extra_blob()
+    a = te.Linear(64, 64, device="cpu")
+    sd = a.state_dict()
+    assert sd["_extra_state"].numel() == 0          # nothing loaded, no forward: still the empty tensor
+    sd["_extra_state"] = blob
+    b = te.Linear(64, 64, device="cpu")
+    b.load_state_dict(sd)
+    assert b._pending_state is not None and b._meta_fwd is None
+    sd_b = b.state_dict()
+    assert sd_b["_extra_state"].numel() > 0, "a save before the first forward dropped the loaded FP8 state"
+    c = te.Linear(64, 64, device="cpu")
+    c.load_state_dict(sd_b)
+    for got in (_decode_extra(sd_b["_extra_state"]), c._pending_state, _decode_extra(c.state_dict()["_extra_state"])):
+        assert set(got) == {"fwd", "bwd"}
+        for d in ("fwd", "bwd"):
+            assert set(got[d]) == {"scale", "scale_inv", "amax_history"}
+            for k, v in st[d].items():
+                assert got[d][k].dtype == v.dtype and torch.equal(got[d][k], v), (d, k)
+
+
+def test_a_state_of_another_history_length_is_refused_before_anything_is_written():
+    """ModuleMeta.load_state checks the amax-history length first: scale and scale_inv of the window are not overwritten, the
+    arena's generation does not move.  A module whose pending state does not fit refuses at every FP8 forward and takes no slots."""
+    import llm_fp8_amd.pytorch as te
+    from llm_fp8_amd.common.recipe import DelayedScaling, Format
+    from llm_fp8_amd.pytorch.fp8 import FP8GlobalStateManager as G, MetaArena, ModuleMeta
+    G.reset()
+    try:
+        recipe = DelayedScaling(fp8_format=Format.HYBRID, amax_history_len=4, amax_compute_algo="max")
+        arena = G.arena(recipe, True, "cpu")
+        meta = ModuleMeta(arena, arena.alloc(3), 3)
+        st, blob = _extra_blob(H=16)
+        gen = arena.generation
+        with pytest.raises(RuntimeError, match="amax history length 16 in checkpoint != recipe's 4"):
+            meta.load_state(st["fwd"])
+        assert arena.generation == gen
+        assert torch.equal(arena.scale, torch.ones(MetaArena.CAP)) and torch.equal(arena.scale_inv, torch.ones(MetaArena.CAP))
+        assert not arena.hist.any()
+        lin = te.Linear(64, 64, device="cpu")
+        lin.set_extra_state(blob)
+        G.FP8_ENABLED, G.FP8_RECIPE = True, recipe  # FP8 "enabled" by hand: the autocast wants a GPU
+        for _ in range(2):
+            with pytest.raises(RuntimeError, match="amax history length"):
+                lin._prepare("cpu")
+            assert lin._meta_fwd is None and lin._pending_state is not None and arena.used == 3
+        fit = DelayedScaling(fp8_format=Format.HYBRID, amax_history_len=16, amax_compute_algo="max")
+        G.FP8_RECIPE = fit
+        lin._prepare("cpu")
+        assert lin._pending_state is None and torch.equal(lin._meta_fwd.state()["amax_history"], st["fwd"]["amax_history"])
+    finally:
+        G.reset()

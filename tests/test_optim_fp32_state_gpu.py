@@ -299,6 +299,44 @@ def test_fp32_state_external_write_reseeds_the_master(dev):
     assert (opt.state[p]["master"] - stale).abs().mean().item() > 1.0  # moved to `other` (|other - stale| ~ 3), not a step from `stale`
 
 
+def test_fp32_state_loaded_before_the_weights_reseeds_the_master(dev):
+    """The load order the class docstring warns of: the optimiser state first, the model's weights second.  The second load writes
+    the parameters (`copy_`, as load_state_dict does), `p._version` moves past the `master_version` the first load recorded, and
+    the next step re-seeds every master from the bf16 parameter -- the SAME bf16 values here, so only the fp32 residue is lost.
+    That step must be a valid step from master == float(p), with the loaded moments and step count kept."""
+    from llm_fp8_amd.optim import ClippedAdamW
+    gen = torch.Generator().manual_seed(78)
+    sizes = [(CHUNK + 8,), (129, 131)]
+    grads = [[torch.randn(s, generator=gen).to(torch.bfloat16).to(dev) for s in sizes] for _ in range(4)]
+    pa = [torch.nn.Parameter(torch.randn(s, generator=gen).to(torch.bfloat16).to(dev)) for s in sizes]
+    oa = ClippedAdamW(pa, max_grad_norm=1.0, state_dtype=F32, **G0)
+    for gs in grads[:3]:
+        for p, g in zip(pa, gs):
+            p.grad = g.clone()
+        oa.step()
+    saved = copy.deepcopy(oa.state_dict())
+    pb = [torch.nn.Parameter(torch.zeros_like(p)) for p in pa]       # a fresh model: not the weights the state goes with
+    ob = ClippedAdamW(pb, max_grad_norm=1.0, state_dtype=F32, **G0)
+    ob.load_state_dict(saved)                                        # the optimiser first ...
+    with torch.no_grad():
+        for p, a in zip(pb, pa):
+            p.copy_(a.detach())                                      # ... the weights second
+    for p, a, g in zip(pb, pa, grads[3]):
+        st, sa = ob.state[p], oa.state[a]
+        assert st["master_version"] != p._version, "the second load did not move the version: nothing to pin"
+        assert torch.equal(st["master"], sa["master"]) and not torch.equal(sa["master"], a.detach().float())  # a residue to lose
+        p.grad = g.clone()
+    before = [_before(ob, p, start=p.detach()) for p in pb]          # the step must start from float(p), not from the loaded master
+    for p, a, b in zip(pb, pa, before):
+        assert np.array_equal(b[2], _np(oa.state[a]["exp_avg"])) and np.array_equal(b[3], _np(oa.state[a]["exp_avg_sq"]))
+    ob.step()
+    torch.cuda.synchronize()
+    coef = _clip_coef(ob, before, 1.0)
+    for p, b in zip(pb, before):
+        print("optimiser loaded before the weights:", _check_state(ob, p, b, 4, G0, coef, f"step after the late weight load {tuple(p.shape)}"))
+        assert ob.state[p]["master_version"] == p._version
+
+
 # ------------------------------------------------------------------------------------------------ F: misaligned state
 def test_fp32_state_sink_weight_with_misaligned_moments(te_reset, dev):
     """fp32 moments that are views at a 4-byte offset (a loaded optimiser state can be): the tile walk issues 16-byte accesses on
