@@ -73,9 +73,10 @@ extern "C" {
  *   5  no new entry point: every mi_adamw_* call reads a NON-FINITE *grad_scale as "skip the step" (THE STEP GUARD below, at
  *      mi_sumsq_bf16).  A caller that sends NaN to drop a step needs a library of this revision; finite values and NULL are unchanged.
  *   6  mi_qknorm_rope_qkv, mi_qknorm_rope_qkv_bwd (per-head QK RMSNorm fused into the RoPE split: Qwen3 attention)
+ *   7  mi_grad_accum_multi (fp32 gradient accumulation over a window of micro-batches, rounded to bf16 once)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 6
+#define MI_ABI_REVISION 7
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -565,6 +566,36 @@ int mi_adamw_f32_multi(const int64_t* table, int n_tensors, const int32_t* chunk
 int mi_adamw_sr_bf16_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
                            const float* grad_scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                            int64_t step, int sink_kind, uint64_t seed, void* stream);
+
+/*
+ * fp32 gradient accumulation over a window of micro-batches (ABI 5 revision 7): ONE launch per micro-batch folds the bf16
+ * gradients of every tensor into fp32 window sums, and the last launch of the window rounds each sum to bf16 ONCE.  (Autograd's
+ * accumulation into a bf16 `.grad` rounds the running sum to bf16 after every micro-batch but the first.)
+ * table: int64 [5, n_tensors] ON THE DEVICE, one column per tensor; chunks [n_chunks, 2] int32 = (tensor, chunk) as for
+ * mi_sumsq_bf16_multi, one workgroup per chunk of chunk_elems elements.
+ *   0 g     bf16 gradient of this micro-batch; may be 0 in mode 2
+ *   1 acc   fp32 window sum
+ *   2 numel element count
+ *   3 mode  per tensor, may be mixed in one launch:
+ *           0 ADD     acc[i] = fl32(acc[i] + float(g[i])); g is not written
+ *           1 SET     acc[i] = float(g[i]); acc is not read (starts a window without a zeroing pass); g is not written
+ *           2 FINISH  out[i] = RNE_bf16(fl32(acc[i] + float(g[i]))), or RNE_bf16(acc[i]) when g is 0; acc is NOT written: its
+ *                     contents are dead afterwards and the next window starts with SET
+ *           any other value: the tensor is left alone (the host cannot read a device table).  So is a tensor with acc == 0,
+ *           with g == 0 in mode 0 or 1, or with out == 0 in mode 2.
+ *   4 out   bf16, mode 2 only; may equal g (each element is read before it is written, by the same lane)
+ * Arithmetic: exactly one IEEE fp32 add (round to nearest even) per element and launch, so a window is the micro-batches added
+ * in launch order; no FMA, no scaling (a caller's loss / N is already in the gradients).  fp32 denormals are kept, in the sums
+ * and in the conversion.  NaN and +-Inf propagate, Inf + (-Inf) = NaN.  The conversion to bf16 is round-to-nearest-even and
+ * keeps NaN; an fp32 sum beyond the bf16 range rounds to +-Inf, it does not saturate (the GEMMs' convention for bf16 output).
+ * The result is therefore bit for bit a numpy float32 restatement (NaN payloads aside).
+ * Accesses: 16 bytes per lane (8 elements: one bf16 load, two fp32 loads, two fp32 stores or one bf16 store) where g, acc and
+ * (mode 2) out are 16-byte aligned, element-wise otherwise and on the tail; 64-bit element indices.
+ * Bytes moved per element: SET 6, ADD 10, FINISH 8.
+ * MI_ERR_ARG before any launch: null table / chunks, n_tensors < 1, n_chunks < 0, chunk_elems not a positive multiple of 8.
+ * n_chunks == 0 is MI_OK (nothing to do).
+ */
+int mi_grad_accum_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems, void* stream);
 
 /*
  * Embedding weight gradient added in place: grad[id, :] += alpha * sum_{tokens t with ids[t] == id} dY[t, :]   (bf16, fp32

@@ -13,7 +13,7 @@ LAB_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "bin", "libmi_fp8_l
 MI_FMT_E4M3 = 0
 MI_FMT_E5M2 = 1
 ABI_VERSION = 5
-ABI_REVISION = 6  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
+ABI_REVISION = 7  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
 # revision 5 adds no symbol: from it on every mi_adamw_* entry point reads a non-finite *grad_scale as "skip the step" (optim.py)
 
 _c_i64 = ctypes.c_int64
@@ -116,6 +116,8 @@ REVISION_SIGNATURES = {
     # revision 6: per-head QK RMSNorm fused into the RoPE split (Qwen3 attention)
     "mi_qknorm_rope_qkv": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _c_i64, _c_i64, _c_int, _c_int, _c_int, ctypes.c_float, _p],
     "mi_qknorm_rope_qkv_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _c_int, _c_i64, _c_i64, _c_int, _c_int, _c_int, _p],
+    # revision 7: fp32 gradient accumulation over a window of micro-batches (grad_accum.GradAccumulator)
+    "mi_grad_accum_multi": [_p, _c_int, _p, _c_int, _c_int, _p],
 }
 SIGNATURES.update(REVISION_SIGNATURES)
 # entry points only the lab build exports (#ifdef MI_DIAG in include/mi_fp8.h)

@@ -3,6 +3,7 @@
 // squared-norm reduction is one streaming pass with fixed-order partial sums (bitwise reproducible).
 //   mi_sumsq_bf16   partial[b] = sum over block b's elements of g^2 (fp32), b < n_partials
 //   mi_adamw_bf16   torch.optim.AdamW semantics for bf16 parameters with bf16 exp_avg / exp_avg_sq, fp32 math
+//   mi_grad_accum_multi   the gradients of a window of micro-batches summed in fp32 and rounded to bf16 once
 #include "mi_common.h"
 #include <string>
 
@@ -152,7 +153,7 @@ enum TabRow {
   ROW_Y, ROW_YT, ROW_LD_Y, ROW_LD_YT, ROW_SCALE, ROW_AMAX, ROW_MASTER, ROW_SR_KEY,
   ROW_Y_ROW = ROW_Y, ROW_S_ROW, ROW_Y_COLT, ROW_S_COLT, ROW_LDR, ROW_SR_BASE = ROW_MASTER
 };
-__device__ __forceinline__ int64_t tab_at(const int64_t* __restrict__ tab, int T, TabRow row, int t) { return tab[(int64_t)row * T + t]; }
+__device__ __forceinline__ int64_t tab_at(const int64_t* __restrict__ tab, int T, int row, int t) { return tab[(int64_t)row * T + t]; }
 
 __global__ __launch_bounds__(256) void sumsq_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
                                                           int chunk_elems, double* __restrict__ partial) {
@@ -207,6 +208,135 @@ __global__ __launch_bounds__(256) void sumsq_multi_kernel(const int64_t* __restr
   if ((tid & 63) == 0) s_red[tid >> 6] = acc;
   __syncthreads();
   if (tid == 0) partial[blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+// ---- fp32 gradient accumulation over a window of micro-batches (include/mi_fp8.h mi_grad_accum_multi states the contract).
+// One launch per micro-batch over every tensor, the chunk walk of sumsq_multi_kernel.  Table [5, T]:
+//   0 g (bf16, this micro-batch's gradient; may be 0 in FINISH)  1 acc (fp32 window sum)  2 numel  3 mode  4 out (bf16, FINISH)
+// ADD: acc = acc + g.  SET: acc = g (acc is not read).  FINISH: out = RNE_bf16(acc + g), acc is not written; out may be g.
+// Exactly one fp32 add per element (-ffp-contract=off, and there is no multiply to contract with); nothing is reused inside a
+// launch, so every load is nontemporal.  Stores, by measurement on the 3B parameter set (profiles/grad_accum_fp32.txt): the
+// fp32 sums are stored PLAIN (nontemporal: SET 1.38 x, ADD 1.05 x the time), the bf16 result of FINISH NONTEMPORAL (plain: 1.08 x).
+// MI_ACCUM_NT_ACC_STORES / MI_ACCUM_NT_OUT_STORES build the other policy for the A/B (Makefile: accum_ab).
+#ifndef MI_ACCUM_NT_ACC_STORES
+#define MI_ACCUM_NT_ACC_STORES 0
+#endif
+#ifndef MI_ACCUM_NT_OUT_STORES
+#define MI_ACCUM_NT_OUT_STORES 1
+#endif
+enum AccumRow { ACC_ROW_G, ACC_ROW_ACC, ACC_ROW_NUMEL, ACC_ROW_MODE, ACC_ROW_OUT };
+enum AccumMode { ACCUM_ADD, ACCUM_SET, ACCUM_FINISH };
+
+template <bool NT, typename V>
+__device__ __forceinline__ void accum_store(V* dst, V v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, dst);
+  else *dst = v;
+}
+
+// One element.  HAS_G = false: FINISH of a tensor with no gradient in the last micro-batch, the sum is rounded as it stands.
+template <int MODE, bool HAS_G>
+__device__ __forceinline__ float accum_one(float acc, float g) {
+  if constexpr (MODE == ACCUM_SET) return g;
+  else if constexpr (HAS_G) return acc + g;
+  else return acc;
+}
+
+// A lane's 8 consecutive elements (vector index i): the loads and the add + stores are separate calls, so that the walk can have
+// the loads of two vectors in flight.
+template <int MODE, bool HAS_G>
+struct Accum8 {
+  v4i g;
+  v4f a[2];
+  __device__ __forceinline__ void load(const uint16_t* gp, const float* acc, int64_t i) {
+    if constexpr (HAS_G) g = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(gp) + i);
+    if constexpr (MODE != ACCUM_SET) {
+      a[0] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(acc) + 2 * i);
+      a[1] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(acc) + 2 * i + 1);
+    }
+  }
+  __device__ __forceinline__ void finish(float* acc, uint16_t* out, int64_t i) {
+    float f[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float gl = 0.0f, gh = 0.0f, al = 0.0f, ah = 0.0f;
+      if constexpr (HAS_G) {
+        gl = __uint_as_float((u32)g[j] << 16);
+        gh = __uint_as_float((u32)g[j] & 0xFFFF0000u);
+      }
+      if constexpr (MODE != ACCUM_SET) {
+        al = a[j >> 1][(2 * j) & 3];
+        ah = a[j >> 1][((2 * j) & 3) + 1];
+      }
+      f[2 * j] = accum_one<MODE, HAS_G>(al, gl);
+      f[2 * j + 1] = accum_one<MODE, HAS_G>(ah, gh);
+    }
+    if constexpr (MODE == ACCUM_FINISH) {
+      const v4i o = {(int)pack_bf16x2(f[0], f[1]), (int)pack_bf16x2(f[2], f[3]), (int)pack_bf16x2(f[4], f[5]),
+                     (int)pack_bf16x2(f[6], f[7])};
+      accum_store<MI_ACCUM_NT_OUT_STORES != 0>(reinterpret_cast<v4i*>(out) + i, o);
+    } else {
+      const v4f o0 = {f[0], f[1], f[2], f[3]}, o1 = {f[4], f[5], f[6], f[7]};
+      accum_store<MI_ACCUM_NT_ACC_STORES != 0>(reinterpret_cast<v4f*>(acc) + 2 * i, o0);
+      accum_store<MI_ACCUM_NT_ACC_STORES != 0>(reinterpret_cast<v4f*>(acc) + 2 * i + 1, o1);
+    }
+  }
+};
+
+// Elements [lo, hi) of one tensor.  g and out may be the same array (no __restrict__): a lane reads its elements before it
+// writes them and no other lane touches them.
+template <int MODE, bool HAS_G>
+__device__ __forceinline__ void accum_chunk(const uint16_t* g, float* acc, uint16_t* out, int64_t lo, int64_t hi, int tid) {
+  uintptr_t align = (uintptr_t)acc;
+  if constexpr (HAS_G) align |= (uintptr_t)g;
+  if constexpr (MODE == ACCUM_FINISH) align |= (uintptr_t)out;
+  int64_t done = lo;
+  if ((align & 15) == 0) {  // chunk_elems is a multiple of 8: chunk starts stay 16-byte (bf16) and 32-byte (fp32) aligned
+    const int64_t v1 = hi >> 3;
+    int64_t i = (lo >> 3) + tid;
+    for (; i + 256 < v1; i += 512) {
+      Accum8<MODE, HAS_G> x, y;
+      x.load(g, acc, i);
+      y.load(g, acc, i + 256);
+      x.finish(acc, out, i);
+      y.finish(acc, out, i + 256);
+    }
+    for (; i < v1; i += 256) {
+      Accum8<MODE, HAS_G> x;
+      x.load(g, acc, i);
+      x.finish(acc, out, i);
+    }
+    done = v1 << 3;
+  }
+  for (int64_t k = done + tid; k < hi; k += 256) {
+    float gv = 0.0f, av = 0.0f;
+    if constexpr (HAS_G) gv = bf16_bits_to_float(g[k]);
+    if constexpr (MODE != ACCUM_SET) av = acc[k];
+    const float f = accum_one<MODE, HAS_G>(av, gv);
+    if constexpr (MODE == ACCUM_FINISH) out[k] = (uint16_t)float_to_bf16_bits(f);
+    else acc[k] = f;
+  }
+}
+
+__global__ __launch_bounds__(256) void grad_accum_multi_kernel(const int64_t* __restrict__ tab, int T, const ChunkRef* __restrict__ chunks,
+                                                               int chunk_elems) {
+  const ChunkRef cr = chunks[blockIdx.x];
+  if ((unsigned)cr.tensor >= (unsigned)T || cr.chunk < 0) return;
+  const uint16_t* g = reinterpret_cast<const uint16_t*>(tab_at(tab, T, ACC_ROW_G, cr.tensor));
+  float* acc = reinterpret_cast<float*>(tab_at(tab, T, ACC_ROW_ACC, cr.tensor));
+  uint16_t* out = reinterpret_cast<uint16_t*>(tab_at(tab, T, ACC_ROW_OUT, cr.tensor));
+  const int64_t n = tab_at(tab, T, ACC_ROW_NUMEL, cr.tensor), mode = tab_at(tab, T, ACC_ROW_MODE, cr.tensor);
+  const int64_t lo = (int64_t)cr.chunk * chunk_elems, hi = min(n, lo + chunk_elems);
+  const int tid = threadIdx.x;
+  if (acc == nullptr) return;
+  // the mode is the tensor's, the same in every lane of the workgroup; the host cannot read the table: any other value is "do nothing"
+  if (mode == ACCUM_ADD) {
+    if (g != nullptr) accum_chunk<ACCUM_ADD, true>(g, acc, nullptr, lo, hi, tid);
+  } else if (mode == ACCUM_SET) {
+    if (g != nullptr) accum_chunk<ACCUM_SET, true>(g, acc, nullptr, lo, hi, tid);
+  } else if (mode == ACCUM_FINISH && out != nullptr) {
+    if (g != nullptr) accum_chunk<ACCUM_FINISH, true>(g, acc, out, lo, hi, tid);
+    else accum_chunk<ACCUM_FINISH, false>(nullptr, acc, out, lo, hi, tid);
+  }
 }
 
 // ---- state type of the multi-tensor AdamW kernels.  ST = uint16_t: bf16 parameter, exp_avg and exp_avg_sq (torch's fused AdamW
@@ -701,6 +831,13 @@ extern "C" int mi_adamw_sr_bf16_multi(const int64_t* table, int n_tensors, const
   a.step = (mi::u32)((uint64_t)step & 0xFFFFFFFFull);
   return launch_multi(__func__, sink_kind == 0 ? mi::adamw_cast_multi_kernel<uint16_t, true> : mi::adamw_mxcast_multi_kernel<uint16_t, true>,
                       table, n_tensors, chunks, n_chunks, chunk_elems, stream, grad_scale, a);
+}
+
+// fp32 gradient accumulation: one launch per micro-batch (include/mi_fp8.h)
+extern "C" int mi_grad_accum_multi(const int64_t* table, int n_tensors, const int32_t* chunks, int n_chunks, int chunk_elems,
+                                   void* stream) {
+  if (int rc = check_multi(__func__, true, table && chunks, n_tensors, n_chunks, chunk_elems, 1)) return rc;
+  return launch_multi(__func__, mi::grad_accum_multi_kernel, table, n_tensors, chunks, n_chunks, chunk_elems, stream);
 }
 
 extern "C" int mi_sumsq_bf16(const void* g_bf16, int64_t n, float* partial, int n_partials, void* stream) {

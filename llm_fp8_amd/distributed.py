@@ -725,19 +725,22 @@ def install_local_embedding_grad(module: torch.nn.Module) -> int:
     return n
 
 
-def replicated_state_bytes(module: torch.nn.Module, moment_bytes: int = 4, optimizer_state: str = "bf16") -> int:
+def replicated_state_bytes(module: torch.nn.Module, moment_bytes: int = 4, optimizer_state: str = "bf16", fp32_grad_accum: bool = False) -> int:
     """Weights + gradients + two AdamW moments per trainable parameter (moments counted at fp32 to be safe).  `optimizer_state`
     "fp32" (optim.ClippedAdamW(state_dtype=torch.float32)) adds 8 bytes per trainable parameter on top of the bf16 layout: a
-    4-byte master weight and two moments 2 bytes wider each (3B: +25.6 GB, 8B: +64 GB)."""
+    4-byte master weight and two moments 2 bytes wider each (3B: +25.6 GB, 8B: +64 GB).  `fp32_grad_accum`
+    (grad_accum.GradAccumulator) adds the 4-byte fp32 window sum per trainable parameter (3B: +12.8 GB)."""
     extra = 8 if optimizer_state == "fp32" else 0  # "bf16_sr" (stochastic rounding) is the bf16 layout
+    extra += 4 if fp32_grad_accum else 0
     n = sum(p.numel() * (2 * p.element_size() + 2 * moment_bytes + extra) for p in module.parameters() if p.requires_grad)
     return n + sum(p.numel() * p.element_size() for p in module.parameters() if not p.requires_grad)
 
 
-def fits_replicated(module: torch.nn.Module, device: torch.device, fraction: float = 0.5, optimizer_state: str = "bf16") -> bool:
+def fits_replicated(module: torch.nn.Module, device: torch.device, fraction: float = 0.5, optimizer_state: str = "bf16",
+                    fp32_grad_accum: bool = False) -> bool:
     """True when the replicated training state takes at most `fraction` of the device's memory (the rest is for
     activations): 3B -> 39 GB, 8B -> 96 GB of 288 GB (fp32 optimiser state: 64 GB, 160 GB)."""
     if device.type != "cuda":
         return True
     total = torch.cuda.get_device_properties(device).total_memory
-    return replicated_state_bytes(module, optimizer_state=optimizer_state) <= fraction * total
+    return replicated_state_bytes(module, optimizer_state=optimizer_state, fp32_grad_accum=fp32_grad_accum) <= fraction * total

@@ -653,6 +653,17 @@ def embedding_grad_add_(grad: torch.Tensor, dy: torch.Tensor, ids: torch.Tensor,
     _lib.check(rc, "mi_embedding_grad_add")
 
 
+def grad_accum_multi(table: torch.Tensor, n_tensors: int, chunks: torch.Tensor, n_chunks: int, chunk_elems: int) -> None:
+    """One launch of mi_grad_accum_multi (include/mi_fp8.h): `table` [5, n_tensors] int64 and `chunks` [n_chunks, 2] int32 on the
+    device.  Per tensor ADD / SET into its fp32 window sum or FINISH (round the sum to bf16 once); grad_accum.GradAccumulator
+    builds the tables.  An older library (LLM_FP8_AMD_LIB) is refused by name."""
+    _dev(table, chunks)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (5, n_tensors)
+    assert chunks.dtype == torch.int32 and chunks.is_contiguous() and chunks.numel() >= 2 * n_chunks
+    fn = _lib.require("mi_grad_accum_multi", "fp32 gradient accumulation (grad_accum_dtype=fp32)")
+    _lib.check(fn(table.data_ptr(), n_tensors, chunks.data_ptr(), n_chunks, chunk_elems, _stream()), "mi_grad_accum_multi")
+
+
 def rope_qkv_backward_cast(dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
                            n_q: int, n_kv: int, head_dim: int, seq: int, scale: torch.Tensor, amax: Optional[torch.Tensor],
                            fmt: int, want_y: bool = True, want_t: bool = True):

@@ -48,6 +48,7 @@ class TrainingConfig:
     load_dir: Optional[str] = None        # local checkpoint directory (from_pretrained_local, te_llama.py:100-178)
     optimizer_state: Optional[str] = None  # "bf16" | "fp32" | "bf16_sr" (optim.ClippedAdamW); None: resolve_optimizer_state
     skip_nonfinite_steps: bool = True     # ClippedAdamW drops a step whose gradient norm is Inf / NaN (resolve_skip_nonfinite)
+    grad_accum_dtype: Optional[str] = None  # "bf16" | "fp32" (grad_accum.GradAccumulator); None: resolve_grad_accum_dtype
 
 
 def create_model(cfg: TrainingConfig, device) -> torch.nn.Module:
@@ -153,6 +154,22 @@ def resolve_optimizer_state(cfg_or_value=None) -> str:
     return v
 
 
+GRAD_ACCUM_DTYPES = ("bf16", "fp32")
+
+
+def resolve_grad_accum_dtype(cfg_or_value=None) -> str:
+    """Precision a window of micro-batches is summed in: `TrainingConfig.grad_accum_dtype` / `--grad_accum_dtype`, else the
+    environment variable LLM_FP8_AMD_GRAD_ACCUM, else `bf16` (autograd adds each micro-batch into the bf16 `.grad`: N - 1 roundings
+    per window).  `fp32` = fp32 `main_grad` sums, rounded to bf16 once at the end of the window (grad_accum.GradAccumulator;
+    +4 bytes per trainable parameter)."""
+    v = getattr(cfg_or_value, "grad_accum_dtype", cfg_or_value)
+    if v is None:
+        v = os.environ.get("LLM_FP8_AMD_GRAD_ACCUM") or "bf16"
+    if v not in GRAD_ACCUM_DTYPES:
+        raise ValueError(f"gradient accumulation dtype {v!r}: one of {GRAD_ACCUM_DTYPES}")
+    return v
+
+
 # auto: replicated (gradient arena) while the replicated training state fits the device, else fsdp_fp8; replicated:
 # distributed.GradArenaDP; fsdp_fp8: distributed.ShardedFP8DP (FULL_SHARD counterpart with FP8 all-gather); fsdp_full / ddp: the
 # torch wrappers the reference uses (train_multi_gpu.py:414-445, :447-470); none: no wrapper
@@ -166,12 +183,14 @@ def resolve_skip_nonfinite(cfg: TrainingConfig) -> Optional[bool]:
     return False if off else None
 
 
-def resolve_sharding_mode(mode: str, model: torch.nn.Module, device, optimizer_state: Optional[str] = None) -> str:
+def resolve_sharding_mode(mode: str, model: torch.nn.Module, device, optimizer_state: Optional[str] = None,
+                          grad_accum_dtype: Optional[str] = None) -> str:
     """`auto` (DistributedConfig._auto_detect_sharding, train_multi_gpu.py:137-146, picks FSDP FULL_SHARD whenever there is
     more than one GPU): here the run shards only when it has to -- the replicated state of every BASELINE.json model fits
     one MI355X (3B: 39 GB, 8B: 96 GB of 288 GB), so `auto` = gradient-arena data parallelism (distributed.GradArenaDP),
     and the full-shard mode (`fsdp_fp8`) only for a model whose replicated state would take more than half of the device
-    (`optimizer_state` "fp32" adds 8 bytes per trainable parameter to that state: +25.6 GB for 3B, +64 GB for 8B).  An explicit
+    (`optimizer_state` "fp32" adds 8 bytes per trainable parameter to that state: +25.6 GB for 3B, +64 GB for 8B; `grad_accum_dtype`
+    "fp32" is counted with 4 more, although create_optimizer refuses it under every wrapper so far).  An explicit
     ddp / fsdp_full / replicated request is honoured even at world size 1 (rehearsal on a one-GPU box).
     A model that runs Float8CurrentScaling (scenario `current`) never resolves to `fsdp_fp8`: that mode lives on FP8 weight copies the
     optimiser emits, which current scaling does not have; where the replicated state does not fit, `auto` is torch's `fsdp_full`.
@@ -185,7 +204,8 @@ def resolve_sharding_mode(mode: str, model: torch.nn.Module, device, optimizer_s
     # does not fit: the FULL_SHARD counterpart with FP8 all-gathers (distributed.ShardedFP8DP; masters, gradients and AdamW
     # moments of every GEMM weight at 1/world per rank), not torch FSDP (bf16 gathers in forward and backward, a cast after each)
     from .distributed import uses_block_scaling, uses_current_scaling
-    if fits_replicated(model, device, optimizer_state=resolve_optimizer_state(optimizer_state)):
+    if fits_replicated(model, device, optimizer_state=resolve_optimizer_state(optimizer_state),
+                       fp32_grad_accum=resolve_grad_accum_dtype(grad_accum_dtype) == "fp32"):
         return "replicated"
     return "fsdp_full" if (uses_current_scaling(model) or uses_block_scaling(model)) else "fsdp_fp8"
 
@@ -203,7 +223,7 @@ def wrap_distributed(model: torch.nn.Module, cfg: TrainingConfig, device) -> tor
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()) or cfg.sharding_mode == "none":
         return _single_process(model, device)
-    mode = resolve_sharding_mode(cfg.sharding_mode, model, device, cfg.optimizer_state)
+    mode = resolve_sharding_mode(cfg.sharding_mode, model, device, cfg.optimizer_state, cfg.grad_accum_dtype)
     if mode == "none":
         return _single_process(model, device)
     if mode == "replicated":
@@ -247,12 +267,17 @@ def create_optimizer(model, cfg: TrainingConfig):
     """AdamW(fused=True) + linear warmup/decay (train_fp8.py:200-210).  On the single-GPU path (bf16 parameters on the
     device, no FSDP/DDP wrapper) the clip + AdamW pair runs as `ClippedAdamW` (two HIP passes, same update rule)."""
     opt_state = resolve_optimizer_state(cfg)
+    accum = resolve_grad_accum_dtype(cfg)
     if opt_state == "bf16_sr":
         assign_sr_keys(model)  # before the groups are formed: the row shards take their keys from the full parameters
     groups = model.optimizer_param_groups() if hasattr(model, "optimizer_param_groups") else None
     params = [p for g in groups for p in g["params"]] if groups is not None else [p for p in model.parameters() if p.requires_grad]
     fused = all(p.is_cuda for p in params)
     wrapped = type(model).__name__ in ("FullyShardedDataParallel", "DistributedDataParallel")
+    if accum == "fp32" and (wrapped or type(model).__name__ in ("GradArenaDP", "ShardedFP8DP")):
+        raise RuntimeError(f"grad_accum_dtype='fp32' is not supported under a data-parallel wrapper, and the model is wrapped in "
+                           f"{type(model).__name__}: its reduce hooks fire inside the last backward and would exchange the last "
+                           "micro-batch's gradient only")
     if os.environ.get("LLM_FP8_AMD_TORCH_ADAMW") == "1" and type(model).__name__ == "ShardedFP8DP":
         # torch's AdamW would step the row shards, but train_step clips over model.parameters(), where the shards are not
         # registered: the decoder weights' gradients would never enter the norm; and no FP8 copy would be kept current
@@ -274,7 +299,17 @@ def create_optimizer(model, cfg: TrainingConfig):
             need = "fp32 master weights and moments" if opt_state == "fp32" else "stochastic rounding of the bf16 state"
             raise RuntimeError(f"optimizer_state={opt_state!r} needs ClippedAdamW ({need}), but {why}: "
                                "torch.optim.AdamW would be built instead, with its state in the parameters' dtype")
+        if accum == "fp32":  # the window's sum goes into bf16 gradients on the GPU, which is what ClippedAdamW steps
+            why = " and ".join(text for applies, text in (
+                (not fused, "the parameters are not all on the GPU"),
+                (os.environ.get("LLM_FP8_AMD_TORCH_ADAMW") == "1", "LLM_FP8_AMD_TORCH_ADAMW=1 selects torch's AdamW"),
+                (not all(p.dtype == torch.bfloat16 for p in params), "the parameters are not all bf16")) if applies)
+            raise RuntimeError(f"grad_accum_dtype='fp32' needs ClippedAdamW (bf16 parameters and gradients on the GPU), but {why}: "
+                               "torch.optim.AdamW would be built instead")
         opt = torch.optim.AdamW(params, lr=cfg.learning_rate, fused=fused)
+    if accum == "fp32":
+        from .grad_accum import GradAccumulator
+        GradAccumulator(params).attach(opt)  # optimizer.grad_accumulator: train_step folds each micro-batch into it
 
     def lr_lambda(step):
         if step < cfg.num_warmup_steps:
@@ -304,9 +339,11 @@ def train_step(model, batch, optimizer, scheduler, cfg: TrainingConfig):
     """One optimiser step of Trainer._train_epoch (train_fp8.py:276-291).  `batch` is one batch dict or, with
     gradient_accumulation_steps = N > 1, a list of N micro-batches: loss / N, no gradient exchange on the non-final
     micro-batches (`no_sync`, train_multi_gpu.py:714-737), FP8 weights cast once per window, one clip + optimiser + LR
-    step at the end.  Returns the (mean) loss tensor (no host sync)."""
+    step at the end.  With `optimizer.grad_accumulator` (grad_accum_dtype fp32) and N > 1 the window is summed in fp32 and
+    rounded to bf16 once; a single batch never touches the accumulator.  Returns the (mean) loss tensor (no host sync)."""
     micro = batch if isinstance(batch, (list, tuple)) else [batch]
     n = len(micro)
+    accumulator = getattr(optimizer, "grad_accumulator", None) if n > 1 else None
     total = None
     for i, mb in enumerate(micro):
         last = i == n - 1
@@ -318,6 +355,8 @@ def train_step(model, batch, optimizer, scheduler, cfg: TrainingConfig):
             if n > 1:
                 loss = loss / n
             loss.backward()
+        if accumulator is not None:
+            accumulator.accumulate(last)
         total = loss.detach() if total is None else total + loss.detach()
     if n > 1:
         _set_first_microbatch(model, None)
@@ -391,6 +430,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--optimizer_state", choices=OPTIMIZER_STATES, default=None,
                     help="precision of the AdamW state: bf16 (default; or $LLM_FP8_AMD_OPT_STATE) | fp32 master weights + moments | "
                          "bf16_sr: bf16 with stochastic rounding of the weight and moments")
+    ap.add_argument("--grad_accum_dtype", choices=GRAD_ACCUM_DTYPES, default=None,
+                    help="what a window of --gradient_accumulation_steps micro-batches is summed in: bf16 (default; or "
+                         "$LLM_FP8_AMD_GRAD_ACCUM; autograd's adds into .grad) | fp32 main_grad sums, rounded to bf16 once")
     ap.add_argument("--no_skip_nonfinite_steps", action="store_true",
                     help="let a step with an Inf / NaN gradient norm through (ClippedAdamW drops it on the device by default)")
     return ap
@@ -402,7 +444,8 @@ def config_from_args(a) -> TrainingConfig:
                          sharding_mode=a.sharding_mode, learning_rate=a.learning_rate,
                          num_hidden_layers=a.num_hidden_layers, vocab_size=a.vocab_size, num_warmup_steps=a.num_warmup_steps,
                          gradient_accumulation_steps=a.gradient_accumulation_steps, output_dir=a.output_dir, load_dir=a.load_dir,
-                         optimizer_state=a.optimizer_state, skip_nonfinite_steps=not a.no_skip_nonfinite_steps)
+                         optimizer_state=a.optimizer_state, skip_nonfinite_steps=not a.no_skip_nonfinite_steps,
+                         grad_accum_dtype=a.grad_accum_dtype)
 
 
 def main(argv=None):
