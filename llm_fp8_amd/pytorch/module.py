@@ -251,60 +251,73 @@ def _weight_ok_for_sink(w, K: int) -> bool:
 # (data, scale) pair -- None data where the copy was not asked for.  `scale` is the one-element scale-inverse under delayed and
 # current scaling and the block-major E8M0 tensor under MXFP8.  A GEMM contracts the row-wise copies of its operands: the forward takes `row` of
 # the input and the weight, the backward pair takes `col` of both with the two copies of grad_output.  `g` is the GEMM's index in
-# its module.
+# its module.  Each scaling granularity has ONE host path: _TensorQ (one scale per tensor) for delayed and current scaling, _MXQ
+# (block scales) for MXFP8 and Float8BlockScaling; the concrete classes only say where a quantisation's numbers come from.
 
 
-class _DelayedQ:
-    """Delayed scaling.  Meta slots of GEMM `g`: forward 3g = input, 3g + 1 = weight; backward 2g = grad_output.  What the forward
-    saves for backward (`col` of an activation, both copies of a weight) carries the scale-inverse from scale_inv_snapshot() as
-    of its quantisation -- the arena is rewritten at autocast exit, before backward; the snapshot is not -- while `row` of an
-    activation and both copies of a grad_output, consumed in the pass that makes them, carry the live one."""
-    __slots__ = ("mf", "mb", "fmt_f", "fmt_b")
-    mx = False
-    cache_key, sink_key = "ds", "sink"
-    no_sink = "row-sharded weights of this shape cannot take an FP8 sink"
-    swiglu_adds_bias = True     # the fc1 bias of the fused MLP is added inside the SwiGLU kernels
-    colsum_dtypes = None        # a Linear's bias gradient rides on the cast of dy whatever the bias dtype
+def _bf16_rows(w):
+    """A weight part as the cast kernels read it: bf16 and contiguous -- the part itself where it already is both."""
+    return (w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous()
 
-    def __init__(self, mf, mb, fmt_f: int, fmt_b: int):
-        self.mf, self.mb, self.fmt_f, self.fmt_b = mf, mb, fmt_f, fmt_b
 
-    def _act(self, y, yT, s: int):
-        return (y, self.mf.scale_inv(s)), (yT, self.mf.scale_inv_snapshot()[s:s + 1])
+class _TensorQ:
+    """Per-tensor scaling, what delayed and current scaling share: one fp32 scale per quantisation read by the cast kernels
+    (ops.cast_amax and its fused producers), operands = FP8 bytes with a one-element scale-inverse, ops.gemm_fp8.  A subclass
+    answers the two hooks -- where the numbers of one quantisation come from -- and keeps what is its own: the DyHandoff
+    (`offer`, `taken`) and the optimiser-filled weight copies (`new_sink`, `refresh`, `sink_flat`)."""
+    __slots__ = ("fmt_f", "fmt_b")
+
+    # -- the two hooks; `role` is "x" (input of GEMM `g`), "w" (its weight) or "grad" (its grad_output) --
+    def _scale(self, role: str, g: int, measure):
+        """Asked before the cast is launched: (scale the cast reads, where it publishes its amax or None, `own`: handed back to
+        _scale_inv).  `measure()` runs the amax pass(es) over the value the cast will see and returns their partials; a recipe that
+        knows its scale in advance never calls it."""
+        raise NotImplementedError
+
+    def _scale_inv(self, role: str, g: int, own):
+        """Asked after the cast was launched: the scale-inverse carried by (the row-wise copy, the column-wise copy)."""
+        raise NotImplementedError
+
+    @staticmethod
+    def _amax_pass(fn, dev, grid, *args):
+        """The measure step of one tensor: the pass `fn` (ops.amax_*) over `args` with ops.amax_grid(*grid) workgroups, into the
+        device's partial buffer."""
+        def measure():
+            part = ops.amax_partial(dev, ops.amax_grid(*grid))
+            fn(*args, part)
+            return part
+        return measure
+
+    def _pairs(self, role: str, g: int, own, y, yT):
+        si, si_t = self._scale_inv(role, g, own)
+        return (y, si), (yT, si_t)
 
     def quantize(self, x2, g: int, want_t: bool, norm=None):
         """`norm` = (rstd, gamma): x2 is un-normalised and RMSNorm is fused into the cast."""
-        mf, s = self.mf, 3 * g
         if norm is None:
-            return self._act(*ops.cast_amax(x2, mf.scale(s), mf.amax(s), self.fmt_f, want_t=want_t), s)
-        return self._act(*ops.norm_cast(x2, norm[0], norm[1], mf.scale(s), mf.amax(s), self.fmt_f, want_t=want_t), s)
+            scale, amax, own = self._scale("x", g, self._amax_pass(ops.amax_bf16, x2.device, x2.shape, x2))
+            y, yT = ops.cast_amax(x2, scale, amax, self.fmt_f, want_t=want_t)
+        else:
+            scale, amax, own = self._scale("x", g, self._amax_pass(ops.amax_norm, x2.device, x2.shape, x2, norm[0], norm[1]))
+            y, yT = ops.norm_cast(x2, norm[0], norm[1], scale, amax, self.fmt_f, want_t=want_t)
+        return self._pairs("x", g, own, y, yT)
 
     def swiglu(self, h, g: int, want_t: bool, bias):
-        mf, s = self.mf, 3 * g
-        return self._act(*ops.swiglu_cast(h, mf.scale(s), mf.amax(s), self.fmt_f, want_t=want_t, bias=bias), s)
-
-    def _grad(self, y, yT, cs, s: int):
-        si = self.mb.scale_inv(s)
-        return (y, si), (yT, si), cs
+        scale, amax, own = self._scale("x", g, self._amax_pass(ops.amax_swiglu, h.device, (h.shape[0], h.shape[1] // 2, 32), h, bias))
+        y, yT = ops.swiglu_cast(h, scale, amax, self.fmt_f, want_t=want_t, bias=bias)
+        return self._pairs("x", g, own, y, yT)
 
     def quantize_grad(self, g2, g: int, want_y: bool, want_t: bool, colsum: bool = False):
         """-> (row, col, partial column sums or None)"""
-        mb, s = self.mb, 2 * g
-        out = ops.cast_amax(g2, mb.scale(s), mb.amax(s), self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum)
-        return self._grad(out[0], out[1], out[2] if colsum else None, s)
+        scale, amax, own = self._scale("grad", g, self._amax_pass(ops.amax_bf16, g2.device, g2.shape, g2))
+        out = ops.cast_amax(g2, scale, amax, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum)
+        return (*self._pairs("grad", g, own, out[0], out[1]), out[2] if colsum else None)
 
     def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
-        mb, s = self.mb, 2 * g
-        return self._grad(*ops.dswiglu_cast(h, dact, mb.scale(s), mb.amax(s), self.fmt_b, want_y=want_y, want_t=want_t,
-                                            want_colsum=colsum, bias=bias), s)
-
-    def offer(self, handoff: DyHandoff, g: int, want_y: bool, want_t: bool) -> None:
-        if self.mb is not None:
-            handoff.offer(self.mb.scale(2 * g), self.mb.amax(2 * g), self.fmt_b, want_y, want_t)
-
-    def taken(self, fp8, g: int):
-        """(y, yT) that a DyHandoff producer `put`, as quantize_grad returns them."""
-        return self._grad(fp8[0], fp8[1], None, 2 * g)
+        scale, amax, own = self._scale("grad", g, self._amax_pass(ops.amax_dswiglu, h.device, (h.shape[0], h.shape[1] // 2, 32),
+                                                                   h, bias, dact))
+        y, yT, cs = ops.dswiglu_cast(h, dact, scale, amax, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum, bias=bias)
+        return (*self._pairs("grad", g, own, y, yT), cs)
 
     def operands(self, a, b):
         """One GEMM's operand tuple as ops.gemm_fp8 and _grouped_or_two take it."""
@@ -319,16 +332,68 @@ class _DelayedQ:
         return (w8, siw), (w8t, siw)
 
     def quantize_weights(self, weights, ns, N: int, K: int, dev, g: int, want_t: bool):
-        mf, s = self.mf, 3 * g + 1
+        """One scale for the whole operand (query | key | value), every part cast into its row-block.  Where the scale is measured,
+        every part's amax pass fills its own segment of the partial buffer and ONE scale kernel covers all segments."""
+        ws_ = list(weights)
+
+        def measure():
+            ws_[:] = [_bf16_rows(w) for w in ws_]           # (the casts below then take these as they are)
+            grids = [ops.amax_grid(n, K) for n in ns]
+            part, o = ops.amax_partial(dev, sum(grids)), 0
+            for w, n in zip(ws_, grids):
+                ops.amax_bf16(w, part[o:o + n])
+                o += n
+            return part
+
+        scale, amax, own = self._scale("w", g, measure)
         w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
         w8t = torch.empty((K, N), dtype=torch.uint8, device=dev) if want_t else None
         r = 0
-        for w, n in zip(weights, ns):
-            wb = w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
-            ops.cast_amax(wb.contiguous(), mf.scale(s), mf.amax(s), self.fmt_f,
-                          y=w8[r:r + n], yT=None if w8t is None else w8t[:, r:r + n], want_t=want_t)
+        for w, n in zip(ws_, ns):
+            ops.cast_amax(_bf16_rows(w), scale, amax, self.fmt_f, y=w8[r:r + n], yT=None if w8t is None else w8t[:, r:r + n], want_t=want_t)
             r += n
-        return w8, w8t, mf.scale_inv_snapshot()[s:s + 1]
+        return w8, w8t, self._scale_inv("w", g, own)[1]
+
+
+class _DelayedQ(_TensorQ):
+    """Delayed scaling.  Meta slots of GEMM `g`: forward 3g = input, 3g + 1 = weight; backward 2g = grad_output: the scale is known in
+    advance, the cast publishes its amax into the slot, nothing is measured.  What the forward saves for backward (`col` of an
+    activation, both copies of a weight) carries the scale-inverse from scale_inv_snapshot() as of its quantisation -- the arena is
+    rewritten at autocast exit, before backward; the snapshot is not -- while `row` of an activation and both copies of a
+    grad_output, consumed in the pass that makes them, carry the live one."""
+    __slots__ = ("mf", "mb")
+    mx = False
+    cache_key, sink_key = "ds", "sink"
+    no_sink = "row-sharded weights of this shape cannot take an FP8 sink"
+    swiglu_adds_bias = True     # the fc1 bias of the fused MLP is added inside the SwiGLU kernels
+    colsum_dtypes = None        # a Linear's bias gradient rides on the cast of dy whatever the bias dtype
+
+    def __init__(self, mf, mb, fmt_f: int, fmt_b: int):
+        self.mf, self.mb, self.fmt_f, self.fmt_b = mf, mb, fmt_f, fmt_b
+
+    def _slot(self, role: str, g: int):
+        return (self.mb, 2 * g) if role == "grad" else (self.mf, 3 * g + (role == "w"))
+
+    def _scale(self, role: str, g: int, measure):
+        m, s = self._slot(role, g)
+        return m.scale(s), m.amax(s), None
+
+    def _scale_inv(self, role: str, g: int, own):
+        m, s = self._slot(role, g)
+        if role == "grad":
+            si = m.scale_inv(s)
+            return si, si
+        # (the arena makes its snapshot -- one device copy per step -- when first asked: behind the step's first cast)
+        saved = m.scale_inv_snapshot()[s:s + 1]
+        return (m.scale_inv(s) if role == "x" else saved), saved
+
+    def offer(self, handoff: DyHandoff, g: int, want_y: bool, want_t: bool) -> None:
+        if self.mb is not None:
+            handoff.offer(self.mb.scale(2 * g), self.mb.amax(2 * g), self.fmt_b, want_y, want_t)
+
+    def taken(self, fp8, g: int):
+        """(y, yT) that a DyHandoff producer `put`, as quantize_grad returns them."""
+        return (*self._pairs("grad", g, None, fp8[0], fp8[1]), None)
 
     def new_sink(self, weights, ns, N: int, K: int, dev, g: int):  # None: an operand of this shape cannot take a sink
         return WeightSink(weights, ns, N, K, dev, self.mf, 3 * g + 1) if N % 8 == 0 and K % 8 == 0 else None
@@ -411,7 +476,7 @@ class _MXQ:
         """Every part is quantised straight into its row-block of the operand's buffers (mi_mxfp8_quantize_ex / mi_blockfp8_quantize_ex),
         no bf16 concatenation -- unless a part's rows are no multiple of _part_rows().  One launch per part emits both copies."""
         fmt = self.fmt_f
-        ws_ = [(w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous() for w in weights]
+        ws_ = [_bf16_rows(w) for w in weights]
         if len(ws_) == 1:
             return self._plain("w", ws_[0], fmt, rowwise=True, colwise=want_t)
         if any(n % self._part_rows() for n in ns):
@@ -477,14 +542,15 @@ class _BlockQ(_MXQ):
         return None
 
 
-class _CurrentQ:
-    """Current scaling (Float8CurrentScaling): every quantisation is an amax pass over the tensor (ops.amax_*: the value the cast
-    will see, recomputed where the producer is fused), the scale kernel (ops.current_scale -> a fresh [amax, scale, scale_inv]) and
-    the cast kernel delayed scaling uses, reading that scale and publishing no amax.  No history, no meta slots, nothing to update
-    at autocast exit.  Operands are those of delayed scaling -- FP8 bytes with a one-element scale-inverse, here a view of the
-    quantisation's own triple, which is what the saved column-wise copies carry into backward -- so the GEMMs, the grouped
-    dgrad + wgrad launch and the algorithm table apply unchanged."""
-    __slots__ = ("recipe", "fmt_f", "fmt_b")
+class _CurrentQ(_TensorQ):
+    """Current scaling (Float8CurrentScaling): every quantisation is an amax pass over the tensor (the measure step, ops.amax_*: the
+    value the cast will see, recomputed where the producer is fused), the scale kernel (ops.current_scale -> a fresh [amax, scale,
+    scale_inv]) and the cast kernel delayed scaling uses, reading that scale and publishing no amax.  No history, no meta slots,
+    nothing to update at autocast exit.  Operands are those of delayed scaling -- FP8 bytes with a one-element scale-inverse, here a
+    view of the quantisation's own triple, which is what the saved column-wise copies carry into backward -- so the GEMMs, the
+    grouped dgrad + wgrad launch and the algorithm table apply unchanged."""
+    __slots__ = ("recipe",)
+    _QPARAMS = {"x": "fp8_quant_fwd_inp", "w": "fp8_quant_fwd_weight", "grad": "fp8_quant_bwd_grad"}
     mx = False
     cache_key, sink_key = "cs", "cssink"
     # the optimiser cannot emit current-scaled bytes in its single pass over a weight (the scale needs the updated weight's amax
@@ -498,43 +564,13 @@ class _CurrentQ:
     def __init__(self, recipe: Float8CurrentScaling, fmt_f: int, fmt_b: int):
         self.recipe, self.fmt_f, self.fmt_b = recipe, fmt_f, fmt_b
 
-    @staticmethod
-    def _triple(part, fmt: int, qp):
-        return ops.current_scale(part, ops.FP8_MAX[fmt], qp.amax_epsilon, qp.power_2_scale)
+    def _scale(self, role: str, g: int, measure):
+        qp = getattr(self.recipe, self._QPARAMS[role])
+        t3 = ops.current_scale(measure(), ops.FP8_MAX[self.fmt_b if role == "grad" else self.fmt_f], qp.amax_epsilon, qp.power_2_scale)
+        return t3[1:2], None, t3
 
-    def quantize(self, x2, g: int, want_t: bool, norm=None):
-        part = ops.amax_partial(x2.device, ops.amax_grid(*x2.shape))
-        if norm is None:
-            ops.amax_bf16(x2, part)
-        else:
-            ops.amax_norm(x2, norm[0], norm[1], part)
-        t3 = self._triple(part, self.fmt_f, self.recipe.fp8_quant_fwd_inp)
-        if norm is None:
-            y, yT = ops.cast_amax(x2, t3[1:2], None, self.fmt_f, want_t=want_t)
-        else:
-            y, yT = ops.norm_cast(x2, norm[0], norm[1], t3[1:2], None, self.fmt_f, want_t=want_t)
-        return (y, t3[2:3]), (yT, t3[2:3])
-
-    def swiglu(self, h, g: int, want_t: bool, bias):
-        part = ops.amax_partial(h.device, ops.amax_grid(h.shape[0], h.shape[1] // 2, 32))
-        ops.amax_swiglu(h, bias, part)
-        t3 = self._triple(part, self.fmt_f, self.recipe.fp8_quant_fwd_inp)
-        y, yT = ops.swiglu_cast(h, t3[1:2], None, self.fmt_f, want_t=want_t, bias=bias)
-        return (y, t3[2:3]), (yT, t3[2:3])
-
-    def quantize_grad(self, g2, g: int, want_y: bool, want_t: bool, colsum: bool = False):
-        part = ops.amax_partial(g2.device, ops.amax_grid(*g2.shape))
-        ops.amax_bf16(g2, part)
-        t3 = self._triple(part, self.fmt_b, self.recipe.fp8_quant_bwd_grad)
-        out = ops.cast_amax(g2, t3[1:2], None, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum)
-        return (out[0], t3[2:3]), (out[1], t3[2:3]), out[2] if colsum else None
-
-    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
-        part = ops.amax_partial(h.device, ops.amax_grid(h.shape[0], h.shape[1] // 2, 32))
-        ops.amax_dswiglu(h, bias, dact, part)
-        t3 = self._triple(part, self.fmt_b, self.recipe.fp8_quant_bwd_grad)
-        y, yT, cs = ops.dswiglu_cast(h, dact, t3[1:2], None, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum, bias=bias)
-        return (y, t3[2:3]), (yT, t3[2:3]), cs
+    def _scale_inv(self, role: str, g: int, t3):
+        return t3[2:3], t3[2:3]
 
     def offer(self, handoff: DyHandoff, g: int, want_y: bool, want_t: bool) -> None:
         """Nothing: a DyHandoff producer needs the scale of grad_output before it has produced it.  RoPE backward and cross-entropy
@@ -542,29 +578,6 @@ class _CurrentQ:
 
     def taken(self, fp8, g: int):
         raise RuntimeError("Float8CurrentScaling offers no DyHandoff, so no producer can have put FP8 copies into one")
-
-    operands = _DelayedQ.operands
-    gemm = _DelayedQ.gemm
-    unflat = _DelayedQ.unflat
-
-    def quantize_weights(self, weights, ns, N: int, K: int, dev, g: int, want_t: bool):
-        """One scale for the whole operand (query | key | value): every part's amax pass fills its own segment of the partial
-        buffer, ONE scale kernel covers all segments, then every part is cast into its row-block."""
-        ws_ = [(w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)).contiguous() for w in weights]
-        grids = [ops.amax_grid(n, K) for n in ns]
-        part = ops.amax_partial(dev, sum(grids))
-        o = 0
-        for w, n in zip(ws_, grids):
-            ops.amax_bf16(w, part[o:o + n])
-            o += n
-        t3 = self._triple(part, self.fmt_f, self.recipe.fp8_quant_fwd_weight)
-        w8 = torch.empty((N, K), dtype=torch.uint8, device=dev)
-        w8t = torch.empty((K, N), dtype=torch.uint8, device=dev) if want_t else None
-        r = 0
-        for w, n in zip(ws_, ns):
-            ops.cast_amax(w, t3[1:2], None, self.fmt_f, y=w8[r:r + n], yT=None if w8t is None else w8t[:, r:r + n], want_t=want_t)
-            r += n
-        return w8, w8t, t3[2:3]
 
     def new_sink(self, weights, ns, N: int, K: int, dev, g: int):
         return None

@@ -3,6 +3,7 @@ function raises if handed a CPU tensor -- there is no PyTorch/CPU fallback for t
 from __future__ import annotations
 
 import ctypes
+import heapq
 import os
 from typing import Optional, Tuple
 
@@ -66,6 +67,27 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _launch(fn, args, name: str, kind: str, span) -> None:
+    """fn(*args), checked under `name`.  Where a KernelTimer is installed the call runs inside its span of `kind`; `span()` ->
+    (tag, work, bytes) is evaluated only then."""
+    t = KernelTimer.active
+    if t is None:
+        rc = fn(*args)
+    else:
+        with t.span(kind, *span()):
+            rc = fn(*args)
+    _lib.check(rc, name)
+
+
+def _u8_pair(R: int, C: int, dev, want_y: bool, want_t: bool, y=None, yT=None):
+    """The FP8 copies a cast writes, y [R, C] and yT [C, R]: fresh where wanted and not handed in, None where not wanted."""
+    if want_y and y is None:
+        y = torch.empty((R, C), dtype=torch.uint8, device=dev)
+    if want_t and yT is None:
+        yT = torch.empty((C, R), dtype=torch.uint8, device=dev)
+    return y, yT
+
+
 def colsum_finish(partial: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """[P, C] fp32 partial column sums -> [C] in `dtype` (bf16 / fp32): one launch instead of sum + cast."""
     _dev(partial)
@@ -81,7 +103,6 @@ def colsum_finish(partial: torch.Tensor, dtype: torch.dtype = torch.bfloat16) ->
 
 def colsum_finish_multi(items):
     """colsum_finish for a list of (partial [P, C] fp32, dtype) in as few launches as possible (4 per launch); same results."""
-    import ctypes
     outs = [None] * len(items)
     todo = []
     for i, (partial, dtype) in enumerate(items):
@@ -114,10 +135,7 @@ def cast_amax(x: torch.Tensor, scale: torch.Tensor, amax: Optional[torch.Tensor]
     assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
     assert scale.dtype == torch.float32 and (amax is None or amax.dtype == torch.float32)
     R, C = x.shape
-    if want_y and y is None:
-        y = torch.empty((R, C), dtype=torch.uint8, device=x.device)
-    if want_t and yT is None:
-        yT = torch.empty((C, R), dtype=torch.uint8, device=x.device)
+    y, yT = _u8_pair(R, C, x.device, want_y, want_t, y, yT)
     if y is not None:
         assert y.dtype == torch.uint8 and y.shape == (R, C) and y.stride(1) == 1
     if yT is not None:
@@ -127,14 +145,8 @@ def cast_amax(x: torch.Tensor, scale: torch.Tensor, amax: Optional[torch.Tensor]
     head = (x.data_ptr(), _ptr(y), _ptr(yT), scale.data_ptr(), _ptr(amax))
     fn = _lib.load().mi_cast_amax_colsum if want_colsum else _lib.load().mi_cast_amax
     args = head + ((cs.data_ptr(),) if want_colsum else ()) + tail
-    t = KernelTimer.active
-    if t is None:
-        rc = fn(*args)
-    else:
-        nb = R * C * (2 + (y is not None) + (yT is not None))
-        with t.span("cast_amax", f"{R}x{C}", float(R * C), float(nb)):
-            rc = fn(*args)
-    _lib.check(rc, "mi_cast_amax")
+    _launch(fn, args, "mi_cast_amax", "cast_amax",
+            lambda: (f"{R}x{C}", float(R * C), float(R * C * (2 + (y is not None) + (yT is not None)))))
     return (y, yT, cs) if want_colsum else (y, yT)
 
 
@@ -165,14 +177,7 @@ def amax_partial(device: torch.device, n: int) -> torch.Tensor:
 
 
 def _amax_call(name: str, args, label: str, elems: float, nbytes: float) -> None:
-    fn = _lib.require(name, "Float8CurrentScaling")
-    t = KernelTimer.active
-    if t is None:
-        rc = fn(*args)
-    else:
-        with t.span("amax", label, elems, nbytes):
-            rc = fn(*args)
-    _lib.check(rc, name)
+    _launch(_lib.require(name, "Float8CurrentScaling"), args, name, "amax", lambda: (label, elems, nbytes))
 
 
 def _partial_ok(partial: torch.Tensor) -> int:
@@ -280,13 +285,8 @@ def gemm_fp8(a8: torch.Tensor, b8: torch.Tensor, sa_inv: torch.Tensor, sb_inv: t
     args = (a8.data_ptr(), b8.data_ptr(), out.data_ptr(), sa_inv.data_ptr(), sb_inv.data_ptr(), _ptr(bias), M, N, K,
             a8.stride(0), b8.stride(0), out.stride(0), fmt_a, fmt_b, 0 if out.dtype == torch.bfloat16 else 1, algo,
             _stream())
-    t = KernelTimer.active
-    if t is None:
-        rc = _lib.load().mi_gemm_fp8(*args)
-    else:
-        with t.span("gemm_fp8", f"{M}x{N}x{K}", 2.0 * M * N * K, M * K + N * K + out.element_size() * M * N):
-            rc = _lib.load().mi_gemm_fp8(*args)
-    _lib.check(rc, "mi_gemm_fp8")
+    _launch(_lib.load().mi_gemm_fp8, args, "mi_gemm_fp8", "gemm_fp8",
+            lambda: (f"{M}x{N}x{K}", 2.0 * M * N * K, M * K + N * K + out.element_size() * M * N))
     return out
 
 
@@ -317,13 +317,8 @@ def gemm_mxfp8(a8, sa, b8, sb, fmt_a: int = E4M3, fmt_b: int = E4M3, bias=None, 
     assert out.is_contiguous() and out.shape == (M, N)
     args = (a8.data_ptr(), sa.data_ptr(), b8.data_ptr(), sb.data_ptr(), out.data_ptr(), _ptr(bias), M, N, K, fmt_a,
             fmt_b, 0 if out.dtype == torch.bfloat16 else 1, algo, _stream())
-    t = KernelTimer.active
-    if t is None:
-        rc = _lib.load().mi_gemm_mxfp8(*args)
-    else:
-        with t.span("gemm_mxfp8", f"{M}x{N}x{K}", 2.0 * M * N * K, M * K + N * K + out.element_size() * M * N):
-            rc = _lib.load().mi_gemm_mxfp8(*args)
-    _lib.check(rc, "mi_gemm_mxfp8")
+    _launch(_lib.load().mi_gemm_mxfp8, args, "mi_gemm_mxfp8", "gemm_mxfp8",
+            lambda: (f"{M}x{N}x{K}", 2.0 * M * N * K, M * K + N * K + out.element_size() * M * N))
     return out
 
 
@@ -419,17 +414,9 @@ def _group_shapes(problems, mx: bool):
 def _grouped_launch(entry: str, span: str, arr, shapes, fmt_a: int, fmt_b: int, tile_cfg: int) -> None:
     """The tail gemm_fp8_grouped and gemm_mxfp8_grouped share: the launch of `entry` over the marshalled problems `arr` of the
     given (M, N, K), inside a KernelTimer span `span` where a timer is active."""
-    fn = getattr(_lib.load(), entry)
-    args = (ctypes.byref(arr), len(shapes), fmt_a, fmt_b, tile_cfg, _stream())
-    t = KernelTimer.active
-    if t is None:
-        rc = fn(*args)
-    else:
-        work = sum(2.0 * M * N * K for M, N, K in shapes)
-        nbytes = sum(M * K + N * K + 2 * M * N for M, N, K in shapes)
-        with t.span(span, "+".join(f"{M}x{N}x{K}" for M, N, K in shapes), work, nbytes):
-            rc = fn(*args)
-    _lib.check(rc, entry)
+    _launch(getattr(_lib.load(), entry), (ctypes.byref(arr), len(shapes), fmt_a, fmt_b, tile_cfg, _stream()), entry, span,
+            lambda: ("+".join(f"{M}x{N}x{K}" for M, N, K in shapes), sum(2.0 * M * N * K for M, N, K in shapes),
+                     sum(M * K + N * K + 2 * M * N for M, N, K in shapes)))
 
 
 def gemm_fp8_grouped(problems, fmt_a: int, fmt_b: int, tile_cfg: int = -1) -> None:
@@ -490,7 +477,6 @@ def grouped_gemm_plan(shapes, n_cu: int = 256) -> int:
     key = (tuple(shapes), n_cu)
     if key in _GROUP_PLAN:
         return _GROUP_PLAN[key]
-    import heapq
     best = -1
     if grouped_gemm_ok(shapes):
         fixed = 4.0
@@ -544,7 +530,7 @@ def grouped_gemm_choice(problems, fmt_a: int, fmt_b: int, mx: bool = False) -> i
     if mode == "off":
         return -1
     if mode == "auto":
-        import torch.distributed as dist
+        dist = torch.distributed
         mode = "plan" if (dist.is_available() and dist.is_initialized()) else "autotune"
     if mode == "plan":
         return grouped_gemm_plan(_group_shapes(problems, mx))
@@ -672,17 +658,11 @@ def rope_qkv_backward_cast(dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor,
     dq, dk, dv = (t.contiguous() for t in (dq, dk, dv))
     T = dq.shape[0]
     W = (n_q + 2 * n_kv) * head_dim
-    y = torch.empty((T, W), dtype=torch.uint8, device=dq.device) if want_y else None
-    yT = torch.empty((W, T), dtype=torch.uint8, device=dq.device) if want_t else None
+    y, yT = _u8_pair(T, W, dq.device, want_y, want_t)
     args = (dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), cos.data_ptr(), sin.data_ptr(), _ptr(y), _ptr(yT), scale.data_ptr(),
             _ptr(amax), T, seq, n_q, n_kv, head_dim, fmt, _stream())
-    t = KernelTimer.active
-    if t is None:
-        rc = _lib.load().mi_rope_qkv_bwd_cast(*args)
-    else:
-        with t.span("cast_amax", f"rope {T}x{W}", float(T * W), float(T * W * (2 + (y is not None) + (yT is not None)))):
-            rc = _lib.load().mi_rope_qkv_bwd_cast(*args)
-    _lib.check(rc, "mi_rope_qkv_bwd_cast")
+    _launch(_lib.load().mi_rope_qkv_bwd_cast, args, "mi_rope_qkv_bwd_cast", "cast_amax",
+            lambda: (f"rope {T}x{W}", float(T * W), float(T * W * (2 + (y is not None) + (yT is not None)))))
     return y, yT
 
 
@@ -694,20 +674,13 @@ def swiglu_cast(h: torch.Tensor, scale: torch.Tensor, amax: Optional[torch.Tenso
     assert h.dtype == torch.bfloat16 and h.dim() == 2 and h.is_contiguous() and h.shape[1] % 2 == 0
     R, F2 = h.shape
     F = F2 // 2
-    y = torch.empty((R, F), dtype=torch.uint8, device=h.device) if want_y else None
-    yT = torch.empty((F, R), dtype=torch.uint8, device=h.device) if want_t else None
+    y, yT = _u8_pair(R, F, h.device, want_y, want_t)
     if bias is None:
         fn, args = _lib.load().mi_swiglu_cast, (h.data_ptr(), _ptr(y), _ptr(yT), scale.data_ptr(), _ptr(amax), R, F, fmt, _stream())
     else:
         assert bias.dtype == torch.bfloat16 and bias.numel() == F2 and bias.is_contiguous()
         fn, args = _lib.load().mi_swiglu_cast_bias, (h.data_ptr(), bias.data_ptr(), _ptr(y), _ptr(yT), scale.data_ptr(), _ptr(amax), R, F, fmt, _stream())
-    t = KernelTimer.active
-    if t is None:
-        rc = fn(*args)
-    else:
-        with t.span("swiglu_cast", f"{R}x{F}", float(R * F), float(R * F * (4 + int(want_y) + int(want_t)))):
-            rc = fn(*args)
-    _lib.check(rc, "mi_swiglu_cast")
+    _launch(fn, args, "mi_swiglu_cast", "swiglu_cast", lambda: (f"{R}x{F}", float(R * F), float(R * F * (4 + int(want_y) + int(want_t)))))
     return y, yT
 
 
@@ -719,8 +692,7 @@ def dswiglu_cast(h: torch.Tensor, dact: torch.Tensor, scale: torch.Tensor, amax:
     R, F2 = h.shape
     F = F2 // 2
     assert dact.shape == (R, F)
-    y = torch.empty((R, F2), dtype=torch.uint8, device=h.device) if want_y else None
-    yT = torch.empty((F2, R), dtype=torch.uint8, device=h.device) if want_t else None
+    y, yT = _u8_pair(R, F2, h.device, want_y, want_t)
     cs = torch.empty(((R + 127) // 128, F2), dtype=torch.float32, device=h.device) if want_colsum else None
     if bias is None:
         fn = _lib.load().mi_dswiglu_cast
@@ -729,13 +701,8 @@ def dswiglu_cast(h: torch.Tensor, dact: torch.Tensor, scale: torch.Tensor, amax:
         assert bias.dtype == torch.bfloat16 and bias.numel() == F2 and bias.is_contiguous()
         fn = _lib.load().mi_dswiglu_cast_bias
         args = (h.data_ptr(), bias.data_ptr(), dact.data_ptr(), _ptr(y), _ptr(yT), scale.data_ptr(), _ptr(amax), _ptr(cs), R, F, fmt, _stream())
-    t = KernelTimer.active
-    if t is None:
-        rc = fn(*args)
-    else:
-        with t.span("dswiglu_cast", f"{R}x{F}", float(R * F2), float(R * F * (6 + 2 * int(want_y) + 2 * int(want_t)))):
-            rc = fn(*args)
-    _lib.check(rc, "mi_dswiglu_cast")
+    _launch(fn, args, "mi_dswiglu_cast", "dswiglu_cast",
+            lambda: (f"{R}x{F}", float(R * F2), float(R * F * (6 + 2 * int(want_y) + 2 * int(want_t)))))
     return y, yT, cs
 
 
@@ -774,16 +741,10 @@ def norm_cast(x: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, scale: t
     _dev(x, rstd, gamma, scale, amax)
     assert x.dtype == torch.bfloat16 and gamma.dtype == torch.bfloat16 and x.is_contiguous() and gamma.is_contiguous()
     R, C = x.shape
-    y = torch.empty((R, C), dtype=torch.uint8, device=x.device) if want_y else None
-    yT = torch.empty((C, R), dtype=torch.uint8, device=x.device) if want_t else None
+    y, yT = _u8_pair(R, C, x.device, want_y, want_t)
     args = (x.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), _ptr(y), _ptr(yT), scale.data_ptr(), _ptr(amax), R, C, fmt, _stream())
-    t = KernelTimer.active
-    if t is None:
-        rc = _lib.load().mi_norm_cast(*args)
-    else:
-        with t.span("norm_cast", f"{R}x{C}", float(R * C), float(R * C * (2 + int(want_y) + int(want_t)))):
-            rc = _lib.load().mi_norm_cast(*args)
-    _lib.check(rc, "mi_norm_cast")
+    _launch(_lib.load().mi_norm_cast, args, "mi_norm_cast", "norm_cast",
+            lambda: (f"{R}x{C}", float(R * C), float(R * C * (2 + int(want_y) + int(want_t)))))
     return y, yT
 
 
@@ -852,13 +813,8 @@ def _q_call(kind: str, entry: str, args, gran, R: int, C: int, in_bytes: float, 
         span, name = "blockfp8_quantize", "mi_blockfp8_" + entry
         args = (*args, _blk_dim(gran[0]), float(gran[1]), _stream())
         fn = _lib.require(name, "Float8BlockScaling")
-    t = KernelTimer.active
-    if t is None:
-        rc = fn(*args)
-    else:
-        with t.span(span, f"{kind} {R}x{C}".strip(), float(R * C), in_bytes + R * C * (1 + 1 / 32) * (int(rowwise) + int(colwise))):
-            rc = fn(*args)
-    _lib.check(rc, "mi_mxfp8_quantize" if name == "mi_mxfp8_quantize_ex" else name)  # (the plain MX form reports one name)
+    _launch(fn, args, "mi_mxfp8_quantize" if name == "mi_mxfp8_quantize_ex" else name, span,  # (the plain MX form reports one name)
+            lambda: (f"{kind} {R}x{C}".strip(), float(R * C), in_bytes + R * C * (1 + 1 / 32) * (int(rowwise) + int(colwise))))
 
 
 def _quantize(x, fmt, rowwise, colwise, out, want_colsum, gran):
@@ -974,14 +930,8 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, ca
         assert o.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1),
             v.stride(1), o.stride(1), float(scale), int(causal), _stream())
-    t = KernelTimer.active
-    flops = 4.0 * B * H * S * S * D * (0.5 if causal else 1.0)
-    if t is None:
-        rc = _lib.load().mi_attn_fwd(*args)
-    else:
-        with t.span("attn_fwd", f"{B}x{S}x{H}x{D}", flops, 2.0 * (q.numel() * 2 + k.numel() * 2)):
-            rc = _lib.load().mi_attn_fwd(*args)
-    _lib.check(rc, "mi_attn_fwd")
+    _launch(_lib.load().mi_attn_fwd, args, "mi_attn_fwd", "attn_fwd",
+            lambda: (f"{B}x{S}x{H}x{D}", 4.0 * B * H * S * S * D * (0.5 if causal else 1.0), 2.0 * (q.numel() * 2 + k.numel() * 2)))
     return o, lse
 
 
@@ -1008,12 +958,6 @@ def attn_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), delta.data_ptr(),
             dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1), v.stride(1), o.stride(1),
             do.stride(1), dq.stride(1), dk.stride(1), dv.stride(1), float(scale), int(causal), _stream())
-    t = KernelTimer.active
-    flops = 14.0 * B * H * S * S * D * (0.5 if causal else 1.0)  # 7 products: S, dP, dQ | S, dP, dV, dK
-    if t is None:
-        rc = _lib.load().mi_attn_bwd(*args)
-    else:
-        with t.span("attn_bwd", f"{B}x{S}x{H}x{D}", flops, 2.0 * (3 * q.numel() + 4 * k.numel())):
-            rc = _lib.load().mi_attn_bwd(*args)
-    _lib.check(rc, "mi_attn_bwd")
+    _launch(_lib.load().mi_attn_bwd, args, "mi_attn_bwd", "attn_bwd",   # 7 products: S, dP, dQ | S, dP, dV, dK
+            lambda: (f"{B}x{S}x{H}x{D}", 14.0 * B * H * S * S * D * (0.5 if causal else 1.0), 2.0 * (3 * q.numel() + 4 * k.numel())))
     return dq, dk, dv
