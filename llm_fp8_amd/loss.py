@@ -1,5 +1,6 @@
 """Fused causal-LM cross-entropy for the harness: same value as HF's `ForCausalLMLoss` (shift labels by one, mean over
-tokens with label != -100) computed by two streaming HIP kernels directly on the bf16 logits of the FP8 lm_head."""
+tokens with label != -100) computed by two streaming HIP kernels directly on the bf16 logits of the FP8 lm_head.  A label at or past
+the vocabulary (HF's loss raises on one) is ignored like -100, in the sum and in the count."""
 from __future__ import annotations
 
 import os
@@ -22,7 +23,8 @@ class _CEFn(torch.autograd.Function):
         rows = torch.empty(T, dtype=torch.float32, device=logits2d.device)
         _lib.check(_lib.load().mi_ce_forward(logits2d.data_ptr(), labels1d.data_ptr(), lse.data_ptr(), rows.data_ptr(), T, V, st),
                    "mi_ce_forward")
-        n_valid = (labels1d != -100).sum().clamp(min=1).to(torch.float32)
+        # what the kernels count: a label outside [0, V) -- -100 or past the vocabulary -- adds nothing to the sum and no gradient
+        n_valid = ((labels1d >= 0) & (labels1d < V)).sum().clamp(min=1).to(torch.float32)
         ctx.save_for_backward(logits2d, labels1d, lse, n_valid)
         ctx.handoff = handoff
         return rows.sum() / n_valid

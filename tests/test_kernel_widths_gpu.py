@@ -234,8 +234,8 @@ def _ce_edge_rows(V: int, seed: int):
 @pytest.mark.parametrize("V", [8, 520, 1536, 2048, 4096, 128256])
 def test_ce_edge_rows_vs_float64(ops, dev, V):
     """Edge rows against float64, directly on the kernels and through causal_lm_loss.  A label >= V is treated as ignored
-    (loss 0, zero gradient), exactly like -100, but -- being != -100 -- it still counts in causal_lm_loss's token count (the
-    mean's denominator); this test pins both.  V < 2048: whole waves (V = 8, 520: lanes too) see no columns.  Rows of -inf
+    (loss 0, zero gradient), exactly like -100, and like -100 it does not count in causal_lm_loss's token count (the mean's
+    denominator counts what the kernels count); this test pins both.  V < 2048: whole waves (V = 8, 520: lanes too) see no columns.  Rows of -inf
     logits over whole lanes (masked vocabulary) must give HF's finite loss: before ce_fwd_kernel guarded its per-lane and
     cross-wave online updates, exp(-inf - -inf) made lse NaN."""
     from llm_fp8_amd.loss import causal_lm_loss
@@ -247,11 +247,12 @@ def test_ce_edge_rows_vs_float64(ops, dev, V):
     lse, loss, d, gs = _ce_run(xd, ld, gscale)
     _check_ce_vs_f64(x_bits, labels, lse, loss, d, gscale, f"V {V}")
     _ce_cast_matches_two_kernel_sequence(ops, xd, ld, lse, d, gs, O.E5M2)
-    # the same rows through the autograd surface: mean over labels != -100, gradient = d(mean) * 2
+    # the same rows through the autograd surface: mean over the labels inside [0, V), gradient = d(mean) * 2
     la = xd[None].clone().requires_grad_(True)
     out = causal_lm_loss(la, ld[None], V, shift_labels=ld[None])
     (out * 2.0).backward()
-    n = int((labels != -100).sum())
+    n = int(((labels >= 0) & (labels < V)).sum())
+    assert n < int((labels != -100).sum())   # the rows hold a label >= V: the two counts differ
     lse_r, loss_r, _ = O.cross_entropy_f64(x_bits, labels)
     xl = np.abs(O.bf16_bits_to_f32(x_bits[np.arange(T), np.clip(labels, 0, V - 1)]).astype(np.float64))
     tol = ((LSE_REL * np.abs(lse_r) + LSE_ABS + 2.0 ** -24 * xl).sum() + T * 2.0 ** -24 * np.abs(loss_r).sum()) / n
