@@ -67,8 +67,12 @@ def main():
             rel = (g - want).abs().max().item() / denom
             if rel > worst_rel:
                 worst_rel, worst_name = rel, name
-    print(json.dumps({"rank": rank, "world": world, "loss": loss, "ref_loss": ref_loss[rank], "params": n, "exact": exact,
-                      "worst_rel": worst_rel, "worst_name": worst_name}), flush=True)
+    outs = [None] * world  # one writer: two processes printing to the same pipe can interleave their lines
+    dist.all_gather_object(outs, {"rank": rank, "world": world, "loss": loss, "ref_loss": ref_loss[rank], "params": n, "exact": exact,
+                                  "worst_rel": worst_rel, "worst_name": worst_name})
+    if rank == 0:
+        for o in outs:
+            print(json.dumps(o), flush=True)
     dist.barrier()
     dist.destroy_process_group()
 

@@ -289,14 +289,18 @@ def main():
         if "ckpt" in flags:
             ckpt = {k: info[k] for k in ("torch_adamw_refused", "save_before_gather_refused")}
             ckpt["files_equal"] = _files_equal(os.path.join(ckpt_dir, "replicated"), os.path.join(ckpt_dir, "sharded"))
-    print(json.dumps({"rank": rank, "world": world, "flags": flags, "losses_equal": l_rep == l_sh, "eval_equal": e_rep == e_sh,
-                      "weights_equal": bool(torch.equal(w_rep, w_sh)),
-                      "arenas_equal": not arena_diffs and len(a_rep) == len(a_sh) == 2, "arena_diffs": arena_diffs,
-                      "losses": l_sh, "losses_rep": l_rep, "eval": [e_rep, e_sh],
-                      "sharded_weights": info.get("sharded_weights", 0), "moment_elems": [mom_rep, mom_sh],
-                      "sinks": {k: info.get("sinks_" + k) for k in ("checked", "mismatch", "stale", "train_stale")}, "ckpt": ckpt,
-                      "mem": {k: info.get(k) for k in ("sharded_logical_bytes", "master_bytes", "shard_grad_bytes", "shard_moment_bytes",
-                                                       "module_param_storage_bytes", "fp8_operand_bytes", "full_grads_alive")}}), flush=True)
+    outs = [None] * world  # one writer: two processes printing to the same pipe can interleave their lines
+    dist.all_gather_object(outs, {"rank": rank, "world": world, "flags": flags, "losses_equal": l_rep == l_sh, "eval_equal": e_rep == e_sh,
+                                  "weights_equal": bool(torch.equal(w_rep, w_sh)),
+                                  "arenas_equal": not arena_diffs and len(a_rep) == len(a_sh) == 2, "arena_diffs": arena_diffs,
+                                  "losses": l_sh, "losses_rep": l_rep, "eval": [e_rep, e_sh],
+                                  "sharded_weights": info.get("sharded_weights", 0), "moment_elems": [mom_rep, mom_sh],
+                                  "sinks": {k: info.get("sinks_" + k) for k in ("checked", "mismatch", "stale", "train_stale")}, "ckpt": ckpt,
+                                  "mem": {k: info.get(k) for k in ("sharded_logical_bytes", "master_bytes", "shard_grad_bytes", "shard_moment_bytes",
+                                                                   "module_param_storage_bytes", "fp8_operand_bytes", "full_grads_alive")}})
+    if rank == 0:
+        for o in outs:
+            print(json.dumps(o), flush=True)
     dist.barrier()
     dist.destroy_process_group()
 

@@ -48,12 +48,16 @@ def main():
     l_rep, e_rep, w_rep, a_rep, _, _ = run("replicated", scenario, rank, device)
     l_sh, e_sh, w_sh, a_sh, info, _ = run("fsdp_fp8", scenario, rank, device)
     arena_diffs = [[when] + d for when, a, b in zip(("after training", "after evaluation"), a_rep, a_sh) for d in _arena_diffs(a, b)]
-    print(json.dumps({"rank": rank, "world": world, "losses_equal": l_rep == l_sh, "eval_equal": e_rep == e_sh,
-                      "weights_equal": bool(torch.equal(w_rep, w_sh)), "weights_finite": bool(torch.isfinite(w_sh.view(torch.bfloat16).float()).all()),
-                      "arenas_equal": not arena_diffs and len(a_rep) == len(a_sh) == 2, "arena_diffs": arena_diffs,
-                      "losses": l_sh, "losses_rep": l_rep, "eval": [e_rep, e_sh], "skipped": SKIPPED,
-                      "sharded_weights": info.get("sharded_weights", 0),
-                      "sinks": {k: info.get("sinks_" + k) for k in ("checked", "mismatch", "stale", "train_stale")}}), flush=True)
+    outs = [None] * world  # one writer: two processes printing to the same pipe can interleave their lines
+    dist.all_gather_object(outs, {"rank": rank, "world": world, "losses_equal": l_rep == l_sh, "eval_equal": e_rep == e_sh,
+                                  "weights_equal": bool(torch.equal(w_rep, w_sh)), "weights_finite": bool(torch.isfinite(w_sh.view(torch.bfloat16).float()).all()),
+                                  "arenas_equal": not arena_diffs and len(a_rep) == len(a_sh) == 2, "arena_diffs": arena_diffs,
+                                  "losses": l_sh, "losses_rep": l_rep, "eval": [e_rep, e_sh], "skipped": SKIPPED,
+                                  "sharded_weights": info.get("sharded_weights", 0),
+                                  "sinks": {k: info.get("sinks_" + k) for k in ("checked", "mismatch", "stale", "train_stale")}})
+    if rank == 0:
+        for o in outs:
+            print(json.dumps(o), flush=True)
     dist.barrier()
     dist.destroy_process_group()
 
