@@ -74,9 +74,11 @@ extern "C" {
  *      mi_sumsq_bf16).  A caller that sends NaN to drop a step needs a library of this revision; finite values and NULL are unchanged.
  *   6  mi_qknorm_rope_qkv, mi_qknorm_rope_qkv_bwd (per-head QK RMSNorm fused into the RoPE split: Qwen3 attention)
  *   7  mi_grad_accum_multi (fp32 gradient accumulation over a window of micro-batches, rounded to bf16 once)
+ *   8  mi_attn_short_fwd, mi_attn_short_bwd (the attention core at 16 <= S <= 112: one workgroup per (batch, kv head), one
+ *      launch each way)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 7
+#define MI_ABI_REVISION 8
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -655,6 +657,23 @@ int mi_attn_bwd(const void* q, const void* k, const void* v, const void* o, cons
                 float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
                 int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts, int64_t dv_ts,
                 float scale, int causal, void* stream);
+
+/*
+ * The attention core at the short lengths of the reference's collator (revision 8): S in {16, 32, .., 112}, causal only, D in
+ * {64, 128}, H % G == 0.  Operands, strides, alignment and `lse` (log2 domain) as mi_attn_fwd / mi_attn_bwd; one launch each
+ * way, one workgroup per (batch, kv head): K / V are fetched once for the H / G query heads of the group, the forward softmax
+ * is a single pass over all keys of a row, and the backward forms S and dP once and produces dq, dk and dv from them (delta =
+ * rowsum(dO * O) is computed in the kernel: no `delta` argument, no workspace).  No atomics and no sum across workgroups:
+ * results are bitwise reproducible.  Rows at or past S are neither read nor written.  Everything else is refused before any
+ * launch: S outside 16..112 or S % 16 != 0, another D, H % G != 0, causal == 0, a null or misaligned pointer, a token stride
+ * that is not a multiple of 8.
+ */
+int mi_attn_short_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G, int D,
+                      int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal, void* stream);
+int mi_attn_short_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq,
+                      void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts, int64_t k_ts, int64_t v_ts,
+                      int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts, int64_t dv_ts, float scale, int causal,
+                      void* stream);
 
 #ifdef __cplusplus
 }

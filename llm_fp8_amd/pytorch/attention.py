@@ -5,8 +5,9 @@
 The two projections (`layernorm_qkv`, `proj`) are on the FP8 hot path; the attention core is bf16 (the
 reference's core is bf16 flash-attn through TE, README.md:27-28): the hand-written flash-style HIP kernels of
 csrc/mi_attn.hip for the shapes of the reference's configs and collator (causal, head_dim 64 / 128, seq >= 128 and
-seq % 16 == 0 -- the reference pads a batch to a multiple of 16 -- no dropout), torch `scaled_dot_product_attention`
-otherwise."""
+seq % 16 == 0 -- the reference pads a batch to a multiple of 16 -- no dropout), the one-workgroup-per-(batch, kv head)
+kernels of csrc/mi_attn_short.hip for the same shapes at the lengths below 128 where they were measured faster (`_SHORT_MIN_S`;
+`LLM_FP8_AMD_NO_SHORT_ATTN=1` turns that route off), torch `scaled_dot_product_attention` otherwise."""
 from __future__ import annotations
 
 import os
@@ -165,11 +166,50 @@ class _FlashAttnFn(torch.autograd.Function):
         return dq, dk, dv, None, None
 
 
+class _ShortAttnFn(torch.autograd.Function):
+    """_FlashAttnFn at 16 <= S < 128, on mi_attn_short_fwd / mi_attn_short_bwd: one launch each way."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        o, lse = ops.attn_short_fwd(q, k, v, scale, True)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse = ctx.saved_tensors
+        ok = (do.stride(3) == 1 and do.stride(2) == do.shape[3] and do.stride(0) == do.shape[1] * do.stride(1)
+              and do.stride(1) % 8 == 0 and do.data_ptr() % 16 == 0)  # the rule of _FlashAttnFn.backward
+        do = do if ok else do.clone(memory_format=torch.contiguous_format)
+        dq, dk, dv = ops.attn_short_bwd(do, q, k, v, o, lse, ctx.scale, True)
+        return dq, dk, dv, None
+
+
 def _flash_ok(q, k, v, causal: bool, dropout: float) -> bool:
     if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and dropout == 0.0 and causal):
         return False
     B, S, H, D = q.shape
     if D not in (64, 128) or S % 16 or S < 128 or H % k.shape[2]:
+        return False
+    return all(t.stride(3) == 1 and t.stride(2) == D and t.stride(0) == S * t.stride(1) and t.stride(1) % 8 == 0
+               and S * t.stride(1) * 2 < 2 ** 31 and t.data_ptr() % 16 == 0 for t in (q, k, v))
+
+
+# The kernels take every S in 16 .. 112; the module sends them only the lengths at which forward + backward was measured faster
+# than the SDPA route by more than that route's own spread (profiles/attn_short_ab.txt, eager calls): from this S up, by head_dim.
+# Below it both routes cost one host launch path (~70 us) and SDPA's is the shorter one.
+_SHORT_MIN_S = {128: 64, 64: 80}
+
+
+def _short_ok(q, k, v, causal: bool, dropout: float) -> bool:
+    """_flash_ok's conditions at the lengths below one 128-row block: 16 <= S < 128, S % 16 == 0 (from _SHORT_MIN_S up)."""
+    if os.environ.get("LLM_FP8_AMD_NO_SHORT_ATTN") == "1":
+        return False
+    if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and dropout == 0.0 and causal):
+        return False
+    B, S, H, D = q.shape
+    if D not in (64, 128) or S % 16 or not _SHORT_MIN_S[D] <= S < 128 or H % k.shape[2]:
         return False
     return all(t.stride(3) == 1 and t.stride(2) == D and t.stride(0) == S * t.stride(1) and t.stride(1) % 8 == 0
                and S * t.stride(1) * 2 < 2 ** 31 and t.data_ptr() % 16 == 0 for t in (q, k, v))
@@ -189,8 +229,9 @@ class DotProductAttention(torch.nn.Module):
         if self.qkv_format == "sbhd":
             q, k, v = (t.transpose(0, 1) for t in (q, k, v))
         causal = self.attn_mask_type in ("causal", "padding_causal")
-        if _flash_ok(q, k, v, causal, self.p if self.training else 0.0):
-            o = _FlashAttnFn.apply(q, k, v, self.d ** -0.5, True)
+        flash = _flash_ok(q, k, v, causal, self.p if self.training else 0.0)
+        if flash or _short_ok(q, k, v, causal, self.p if self.training else 0.0):
+            o = _FlashAttnFn.apply(q, k, v, self.d ** -0.5, True) if flash else _ShortAttnFn.apply(q, k, v, self.d ** -0.5)
             if self.qkv_format == "sbhd":
                 o = o.transpose(0, 1)
             return o.reshape(*o.shape[:2], self.h * self.d)

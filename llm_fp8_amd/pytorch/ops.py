@@ -961,3 +961,58 @@ def attn_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     _launch(_lib.load().mi_attn_bwd, args, "mi_attn_bwd", "attn_bwd",   # 7 products: S, dP, dQ | S, dP, dV, dK
             lambda: (f"{B}x{S}x{H}x{D}", 14.0 * B * H * S * S * D * (0.5 if causal else 1.0), 2.0 * (3 * q.numel() + 4 * k.numel())))
     return dq, dk, dv
+
+
+def _bshd_ok_short(t: torch.Tensor, D: int):
+    if t.numel():  # (an empty operand has no layout to check: the launcher refuses S = 0 by name)
+        _bshd_ok(t, D)
+
+
+def attn_short_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True, out=None):
+    """attn_fwd at 16 <= S <= 112 (S % 16 == 0, causal only): one launch, one workgroup per (batch, kv head).  Same operands,
+    returns and `out` as attn_fwd."""
+    _dev(q, k, v)
+    B, S, H, D = q.shape
+    G = k.shape[2]
+    for t in (q, k, v):
+        _bshd_ok_short(t, D)
+    if out is None:
+        o = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
+        lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    else:
+        o, lse = out
+        _dev(o, lse)
+        _bshd_ok_short(o, D)
+        assert o.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1),
+            v.stride(1), o.stride(1), float(scale), int(causal), _stream())
+    _launch(_lib.require("mi_attn_short_fwd", "short-sequence attention"), args, "mi_attn_short_fwd", "attn_short_fwd",
+            lambda: (f"{B}x{S}x{H}x{D}", 2.0 * B * H * S * S * D, 2.0 * (q.numel() * 2 + k.numel() * 2)))
+    return o, lse
+
+
+def attn_short_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor,
+                   scale: float, causal: bool = True, out=None):
+    """Backward of attn_short_fwd -> (dq, dk, dv), one launch and no workspace.  Same operands and `out` as attn_bwd."""
+    _dev(do, q, k, v, o, lse)
+    B, S, H, D = q.shape
+    G = k.shape[2]
+    for t in (q, k, v, o, do):
+        _bshd_ok_short(t, D)
+    assert o.shape == do.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
+    if out is None:
+        dq = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
+        dk = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
+        dv = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
+    else:
+        dq, dk, dv = out
+        _dev(dq, dk, dv)
+        for t in out:
+            _bshd_ok_short(t, D)
+        assert dq.shape == q.shape and dk.shape == dv.shape == k.shape
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+            dv.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1), v.stride(1), o.stride(1), do.stride(1), dq.stride(1),
+            dk.stride(1), dv.stride(1), float(scale), int(causal), _stream())
+    _launch(_lib.require("mi_attn_short_bwd", "short-sequence attention"), args, "mi_attn_short_bwd", "attn_short_bwd",
+            lambda: (f"{B}x{S}x{H}x{D}", 5.0 * B * H * S * S * D, 2.0 * (3 * q.numel() + 4 * k.numel())))  # 5 products: S, dP, dV, dK, dQ
+    return dq, dk, dv
