@@ -76,9 +76,10 @@ extern "C" {
  *   7  mi_grad_accum_multi (fp32 gradient accumulation over a window of micro-batches, rounded to bf16 once)
  *   8  mi_attn_short_fwd, mi_attn_short_bwd (the attention core at 16 <= S <= 112: one workgroup per (batch, kv head), one
  *      launch each way)
+ *   9  mi_attn_fwd_win, mi_attn_bwd_win (sliding-window causal attention: band-limited forward, dQ and dK/dV kernels)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 8
+#define MI_ABI_REVISION 9
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -674,6 +675,23 @@ int mi_attn_short_bwd(const void* q, const void* k, const void* v, const void* o
                       void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts, int64_t k_ts, int64_t v_ts,
                       int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts, int64_t dv_ts, float scale, int causal,
                       void* stream);
+
+/*
+ * Sliding-window causal attention (revision 9): mi_attn_fwd / mi_attn_bwd with `window` in front of `stream`.  `window` = W >= 1
+ * is the number of keys a query sees, itself included: query i attends keys j with i - W < j <= i (HF `sliding_window`:
+ * kv_idx > q_idx - sliding_window; TE / flash-attn window_size = (W - 1, 0)).  `lse` is the log-sum-exp over the band, in the same
+ * log2-domain layout.  The kernels walk only the band: O(S * W) work.  W >= S is the plain causal mask and launches the kernels
+ * of mi_attn_fwd / mi_attn_bwd: the outputs are bitwise theirs.  Operands, strides, alignment, GQA, `delta` and reproducibility as
+ * there.  Refused before any launch: window < 1, causal == 0, and everything mi_attn_fwd / mi_attn_bwd refuse (S < 128 or
+ * S % 16 != 0, another D, H % G != 0, a null or misaligned pointer, a token stride that is not a multiple of 8, a batch of K / V of
+ * 2 GiB or more).
+ */
+int mi_attn_fwd_win(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G, int D,
+                    int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal, int window, void* stream);
+int mi_attn_bwd_win(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                    float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
+                    int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts, int64_t dv_ts,
+                    float scale, int causal, int window, void* stream);
 
 #ifdef __cplusplus
 }

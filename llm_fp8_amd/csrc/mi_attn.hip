@@ -17,6 +17,9 @@
 // Sequence lengths: S >= 128, S % 16 == 0 (the reference's collator pads a batch to a multiple of 16).  S % 128 == 0 launches
 // the kernels with TAIL = false, which is the code without any of the guards.  Otherwise the grids are ceil(S / 128) blocks
 // and the TAIL = true instantiations guard the one partial block / tile / slice at the end (see attn_fwd_kernel).
+//
+// Sliding window (mi_attn_fwd_win / mi_attn_bwd_win, causal only): query i sees the `window` keys i - window < j <= i.  The WIN = true
+// instantiations walk only the band (see the WIN note below); WIN = false is the code without any of it.
 #include "mi_attn_dev.h"
 
 namespace mi {
@@ -28,12 +31,29 @@ constexpr int ATT_KB = 64;   // keys per tile
 // last 32-row slice) is partial.  Rows at or past S belong to the next batch / head or lie outside the tensor: their loads
 // are clamped to row S - 1 or replaced by zeros, their stores are predicated, and a wave whose 32 rows are all past S keeps
 // staging its share of every tile and meeting every barrier but skips the arithmetic.  TAIL = false is the code as it was.
-template <int D, bool CAUSAL, bool DIAG = false, bool TAIL = false>
+//
+// WIN (all three kernels, CAUSAL only): the causal mask gets a second, lower edge, key > query - window.  With wm1 = window - 1:
+//   fwd / dQ   the tile loop starts at the first tile that ANY row of the workgroup sees, j0 = max(0, first row - wm1) / 64 (the
+//              staging is shared, so the start is the workgroup's; the double-buffer parity stays that of j).  A wave whose 32 rows
+//              all have their band above a tile (key0 + 63 < q_first - wm1) stages and meets the barrier but does no arithmetic,
+//              exactly like a tile above the diagonal.  A tile that holds a key below the band of the wave's LAST row
+//              (key0 < q_first + 31 - wm1) is masked per element, one compare + select beside the diagonal's.
+//              A row can meet a tile in which every one of its keys is masked before it meets a live one (its band starts in a
+//              later tile than the band of the wave's first row).  The running maximum starts at the FINITE -1e30: the tile's
+//              maximum is -inf, m stays -1e30, alpha = exp2(0) = 1, every p = exp2(-inf) = 0, l stays 0, and the first live tile
+//              then rescales that empty state by alpha = exp2(-huge) = 0.  No inf - inf, no NaN.  Every row below S sees its own
+//              key, so l > 0 at the end.
+//   dK / dV    the sweep over query slices ends at the last slice from which any key of the workgroup is seen (query
+//              kbi * 128 + 127 + wm1, clamped to S); a wave skips the slices past its own band (q0 > key_first + 31 + wm1), and
+//              on the slices that cross the band edge p and dS are 0 where query > key + wm1.
+// `window` sits in what was alignment padding of the argument block (fwd, dQ) or at its end (dK/dV), and only WIN reads it.
+template <int D, bool CAUSAL, bool DIAG = false, bool TAIL = false, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                           const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
-                                                          float* __restrict__ lse, int S, int H, int G, int64_t q_ts,
-                                                          int64_t k_ts, int64_t v_ts, int64_t o_ts, float c,
+                                                          float* __restrict__ lse, int S, int H, int G, int window,
+                                                          int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float c,
                                                           unsigned long long* __restrict__ dbg = nullptr) {
+  static_assert(!WIN || CAUSAL, "the window is a band below the causal diagonal");
   constexpr int TILE = ATT_KB * D * 2;  // bytes of one K (or V) tile
   constexpr int KT = D / 16, DB = D / 32;
   __shared__ __attribute__((aligned(16))) char lds[4 * TILE];
@@ -46,6 +66,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
     const int stiles = (S + ATT_KB - 1) / ATT_KB;
     ntiles = CAUSAL ? min(ntiles, stiles) : stiles;
   }
+  const int wm1 = WIN ? window - 1 : 0;
+  const int j0 = WIN ? max(0, qb * ATT_QB - wm1) / ATT_KB : 0;  // first tile any row of the workgroup sees (j0 < ntiles: the diagonal tile is later)
   const uint16_t* kbase = k + (int64_t)b * S * k_ts + (int64_t)g * D;
   const uint16_t* vbase = v + (int64_t)b * S * v_ts + (int64_t)g * D;
 
@@ -64,7 +86,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
   for (int d = 0; d < DB; ++d)
 #pragma unroll
     for (int i = 0; i < 16; ++i) oacc[d][i] = 0.0f;
-  float m = -1.0e30f, l = 0.0f;
+  float m = -1.0e30f, l = 0.0f;  // finite on purpose: a tile whose keys are all masked for a row leaves (m, l) as they are (WIN note)
 
   // K / V tiles of 64 keys go global -> LDS by DMA, double-buffered: tile j + 1 is requested at the top of tile j
   const rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, (int)((((int64_t)S - 1) * k_ts + D) * 2), 0x00020000);
@@ -72,8 +94,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
   int kvo[D / 32], vvo[D / 32];
   dma_voffsets<D>(kvo, k_ts, tid);
   dma_voffsets<D>(vvo, v_ts, tid);
-  stage_tile<D, TAIL>(rsK, kvo, 0, lds, w);
-  stage_tile<D, TAIL>(rsV, vvo, 0, lds + 2 * TILE, w);
+  if (WIN) {
+    stage_tile<D, TAIL>(rsK, kvo, (int)((int64_t)j0 * ATT_KB * k_ts * 2), lds + (j0 & 1) * TILE, w);
+    stage_tile<D, TAIL>(rsV, vvo, (int)((int64_t)j0 * ATT_KB * v_ts * 2), lds + (2 + (j0 & 1)) * TILE, w);
+  } else {
+    stage_tile<D, TAIL>(rsK, kvo, 0, lds, w);
+    stage_tile<D, TAIL>(rsV, vvo, 0, lds + 2 * TILE, w);
+  }
   dma_wait_all();
   __syncthreads();
 
@@ -88,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
     __builtin_amdgcn_sched_barrier(0);                                                    \
   }
   MI_STAMP(-1)
-  for (int j = 0; j < ntiles; ++j) {
+  for (int j = j0; j < ntiles; ++j) {
     const char* kt = lds + (j & 1) * TILE;
     const char* vt = lds + (2 + (j & 1)) * TILE;
     const bool more = j + 1 < ntiles;
@@ -98,7 +125,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
     }
     const int key0 = j * ATT_KB;
     // wave-uniform: tiles entirely above the diagonal contribute nothing (TAIL: nor does a wave whose rows are all past S)
-    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31)) {
+    // (WIN: nor a tile entirely below the band of the wave's first row)
+    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31) && (!WIN || key0 + ATT_KB - 1 >= q_first - wm1)) {
       f16v sacc[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -127,6 +155,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
 #pragma unroll
           for (int i = 0; i < 16; ++i)
             if (key0 + 32 * kb + acc_row(i, h) > qrow) sacc[kb][i] = -INFINITY;
+      }
+      if (WIN && key0 < q_first + 31 - wm1) {  // tile touches the lower band edge of some row of the wave
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (key0 + 32 * kb + acc_row(i, h) < qrow - wm1) sacc[kb][i] = -INFINITY;
       }
       if (TAIL && !CAUSAL && key0 + ATT_KB > S) {  // keys at or past S were staged as zeros: a score of 0, not -inf
 #pragma unroll
@@ -224,13 +259,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
 // dQ pass: same walk as the forward (128 query rows per workgroup, 64-key tiles).  S^T and dP^T are recomputed with the
 // query on the lane (LSE and delta are lane constants), dS^T feeds  dQ^T += K^T . dS^T  straight from the accumulators.
 // Also writes delta[b, h, q] = sum_d dO * O for the dK/dV pass.
-template <int D, bool CAUSAL, bool TAIL = false>
+template <int D, bool CAUSAL, bool TAIL = false, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                              const uint16_t* __restrict__ v, const uint16_t* __restrict__ o,
                                                              const uint16_t* __restrict__ dout, const float* __restrict__ lse,
                                                              float* __restrict__ delta, uint16_t* __restrict__ dq, int S,
-                                                             int H, int G, int64_t q_ts, int64_t k_ts, int64_t v_ts,
+                                                             int H, int G, int window, int64_t q_ts, int64_t k_ts, int64_t v_ts,
                                                              int64_t o_ts, int64_t do_ts, int64_t dq_ts, float c, float scale) {
+  static_assert(!WIN || CAUSAL, "the window is a band below the causal diagonal");
   constexpr int TILE = ATT_KB * D * 2;
   constexpr int KT = D / 16, DB = D / 32;
   __shared__ __attribute__((aligned(16))) char lds[4 * TILE];
@@ -243,6 +279,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
     const int stiles = (S + ATT_KB - 1) / ATT_KB;
     ntiles = CAUSAL ? min(ntiles, stiles) : stiles;
   }
+  const int wm1 = WIN ? window - 1 : 0;
+  const int j0 = WIN ? max(0, qb * ATT_QB - wm1) / ATT_KB : 0;  // first tile any row of the workgroup sees (j0 < ntiles: the diagonal tile is later)
   const uint16_t* kbase = k + (int64_t)b * S * k_ts + (int64_t)g * D;
   const uint16_t* vbase = v + (int64_t)b * S * v_ts + (int64_t)g * D;
 
@@ -290,12 +328,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
   int kvo[D / 32], vvo[D / 32];
   dma_voffsets<D>(kvo, k_ts, tid);
   dma_voffsets<D>(vvo, v_ts, tid);
-  stage_tile<D, TAIL>(rsK, kvo, 0, lds, w);
-  stage_tile<D, TAIL>(rsV, vvo, 0, lds + 2 * TILE, w);
+  if (WIN) {
+    stage_tile<D, TAIL>(rsK, kvo, (int)((int64_t)j0 * ATT_KB * k_ts * 2), lds + (j0 & 1) * TILE, w);
+    stage_tile<D, TAIL>(rsV, vvo, (int)((int64_t)j0 * ATT_KB * v_ts * 2), lds + (2 + (j0 & 1)) * TILE, w);
+  } else {
+    stage_tile<D, TAIL>(rsK, kvo, 0, lds, w);
+    stage_tile<D, TAIL>(rsV, vvo, 0, lds + 2 * TILE, w);
+  }
   dma_wait_all();
   __syncthreads();
 
-  for (int j = 0; j < ntiles; ++j) {
+  for (int j = j0; j < ntiles; ++j) {
     const char* kt = lds + (j & 1) * TILE;
     const char* vt = lds + (2 + (j & 1)) * TILE;
     const bool more = j + 1 < ntiles;
@@ -329,10 +372,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
         __builtin_amdgcn_sched_barrier(0);
       }
       const bool diag = CAUSAL && key0 + 32 * kb + 31 > q_first;
+      const bool edge = WIN && key0 + 32 * kb < q_first + 31 - wm1;  // block holds a key below the band of the wave's last row
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[i], c, -my_lse));
         if (diag && key0 + 32 * kb + acc_row(i, h) > qrow) p = 0.0f;
+        if (edge && key0 + 32 * kb + acc_row(i, h) < qrow - wm1) p = 0.0f;  // a select: whatever exp2 gave for a key outside the band
         if (TAIL && !CAUSAL && key0 + 32 * kb + acc_row(i, h) >= S) p = 0.0f;  // keys staged as zeros
         sacc[i] = p * (pacc[i] - dl);
       }
@@ -353,8 +398,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
     };
     // (wave-uniform tests: blocks entirely above the diagonal contribute nothing)
     // (TAIL: nor does a wave whose rows are all past S, nor a block whose keys are)
-    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31)) block(0);
-    if ((!TAIL || (q_first < S && key0 + 32 < S)) && (!CAUSAL || key0 + 32 <= q_first + 31)) block(1);
+    // (WIN: nor a block entirely below the band of the wave's first row)
+    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31) && (!WIN || key0 + 31 >= q_first - wm1)) block(0);
+    if ((!TAIL || (q_first < S && key0 + 32 < S)) && (!CAUSAL || key0 + 32 <= q_first + 31) && (!WIN || key0 + 63 >= q_first - wm1)) block(1);
     dma_wait_all();  // the next tile has landed (this wave's share; the barrier covers the others')
     __syncthreads();
   }
@@ -366,13 +412,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
 // B operands (key on the lane) and dK^T, dV^T of those keys in accumulators while the workgroup sweeps the group's query
 // heads x 32-row query slices (Q and dO slices staged once for all four waves; row reads for S and dP, transposed reads
 // for the dV^T and dK^T products).
-template <int D, bool CAUSAL, bool TAIL = false>
+template <int D, bool CAUSAL, bool TAIL = false, bool WIN = false>
 __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                                const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                uint16_t* __restrict__ dk, uint16_t* __restrict__ dv, int S, int H,
                                                                int G, int B, int64_t q_ts, int64_t k_ts, int64_t v_ts,
-                                                               int64_t do_ts, int64_t dk_ts, int64_t dv_ts, float c, float scale) {
+                                                               int64_t do_ts, int64_t dk_ts, int64_t dv_ts, float c, float scale,
+                                                               int window = 0) {
+  static_assert(!WIN || CAUSAL, "the window is a band below the causal diagonal");
   constexpr int SL = 32 * D * 2;  // bytes of one 32-row slice image
   constexpr int KT = D / 16, DB = D / 32;
   constexpr int BUF = 2 * SL + 256;  // Q slice, dO slice, lse[32], delta[32]
@@ -409,7 +457,9 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
     for (int i = 0; i < 16; ++i) { dka[d][i] = 0.0f; dva[d][i] = 0.0f; }
 
   const int sl0 = CAUSAL ? (kbi * 128) / 32 : 0;  // first query slice that can see this key block
-  const int nsl = (TAIL ? (S + 31) / 32 : S / 32) - sl0;
+  const int wm1 = WIN ? window - 1 : 0;
+  // (WIN: the last key of the block is seen from query kbi * 128 + 127 + wm1 and no later: (128 + wm1 + 31) / 32 slices at most)
+  const int nsl = WIN ? min((TAIL ? (S + 31) / 32 : S / 32) - sl0, (128 + wm1 + 31) / 32) : (TAIL ? (S + 31) / 32 : S / 32) - sl0;
   const int nsteps = rep * nsl;
   // staging: thread -> 2 chunks of the Q slice and 2 of the dO slice; threads 0..31 lse, 32..63 delta
   v4i qreg[2], dreg[2];
@@ -457,7 +507,8 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
     if (more) load_step(step + 1);
     const int q0 = (sl0 + step % nsl) * 32;
     // wave-uniform: slices entirely before this wave's keys see none of them (TAIL: a wave whose keys are all past S has no sums)
-    if ((!TAIL || key_first < S) && (!CAUSAL || q0 + 31 >= key_first)) {
+    // (WIN: nor do the slices past the band of the wave's last key)
+    if ((!TAIL || key_first < S) && (!CAUSAL || q0 + 31 >= key_first) && (!WIN || q0 <= key_first + 31 + wm1)) {
       const char* qt = buf;
       const char* dt = buf + SL;
       const float* st = reinterpret_cast<const float*>(buf + 2 * SL);
@@ -470,6 +521,7 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
         pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<D>(dt, 0, t, lane), vf[t], pacc, 0, 0, 0);
       }
       const bool diag = CAUSAL && q0 < key_first + 31;
+      const bool edge = WIN && q0 + 31 > key_first + wm1;  // slice holds a query past the band of the wave's first key
       f16v dsacc;
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
@@ -480,6 +532,7 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
           const int i = 4 * a + e;
           float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[i], c, -ls[e]));
           if (diag && key > q0 + acc_row(i, h)) p = 0.0f;
+          if (edge && q0 + acc_row(i, h) > key + wm1) p = 0.0f;
           if (TAIL && q0 + acc_row(i, h) >= S) p = 0.0f;  // a select: p and dS of a row past S are 0 whatever exp2 gave
           sacc[i] = p;
           dsacc[i] = p * (pacc[i] - dl[e]);
@@ -514,38 +567,61 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
 
 }  // namespace mi
 
-extern "C" int mi_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G,
-                           int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
-                           void* stream) {
-  MI_CHECK_ARG(q && k && v && o && lse, "mi_attn_fwd: null pointer");
-  MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "mi_attn_fwd: bad B/H/G (%d, %d, %d)", B, H, G);
-  MI_CHECK_ARG(D == 128 || D == 64, "mi_attn_fwd: head_dim %d not supported (64, 128)", D);
-  MI_CHECK_ARG(S >= 128 && S % 16 == 0, "mi_attn_fwd: seq %d must be a multiple of 16 and at least 128", S);
-  MI_CHECK_ARG(q_ts % 8 == 0 && k_ts % 8 == 0 && v_ts % 8 == 0 && o_ts % 8 == 0, "mi_attn_fwd: token strides must be multiples of 8");
+// One host path for mi_attn_fwd (window = 0: no band) and mi_attn_fwd_win (window >= 1); `fn` names the entry point in every refusal.
+static int attn_fwd_launch(const char* fn, const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
+                           int G, int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
+                           int window, void* stream) {
+  MI_CHECK_ARG(q && k && v && o && lse, "%s: null pointer", fn);
+  MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "%s: bad B/H/G (%d, %d, %d)", fn, B, H, G);
+  MI_CHECK_ARG(D == 128 || D == 64, "%s: head_dim %d not supported (64, 128)", fn, D);
+  MI_CHECK_ARG(S >= 128 && S % 16 == 0, "%s: seq %d must be a multiple of 16 and at least 128", fn, S);
+  MI_CHECK_ARG(q_ts % 8 == 0 && k_ts % 8 == 0 && v_ts % 8 == 0 && o_ts % 8 == 0, "%s: token strides must be multiples of 8", fn);
   MI_CHECK_ARG((int64_t)S * k_ts * 2 < (1LL << 31) && (int64_t)S * v_ts * 2 < (1LL << 31) && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0,
-               "mi_attn_fwd: one batch of K / V must span < 2 GiB and be 16-byte aligned (32-bit buffer offsets of the LDS DMA)");
-  MI_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)o % 16) == 0, "mi_attn_fwd: q and o must be 16-byte aligned (16-byte row accesses)");
-  MI_CHECK_ARG(H <= 65535 && B <= 65535, "mi_attn_fwd: grid too large");
+               "%s: one batch of K / V must span < 2 GiB and be 16-byte aligned (32-bit buffer offsets of the LDS DMA)", fn);
+  MI_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)o % 16) == 0, "%s: q and o must be 16-byte aligned (16-byte row accesses)", fn);
+  MI_CHECK_ARG(H <= 65535 && B <= 65535, "%s: grid too large", fn);
   const float c = scale * 1.4426950408889634f;
   const bool tail = S % mi::ATT_QB != 0;  // a partial last block: the TAIL instantiations; full blocks launch the kernels as before
+  const bool win = window >= 1 && window < S;  // a window that covers every causal key is the plain causal mask: the kernels as before
   dim3 grid((S + mi::ATT_QB - 1) / mi::ATT_QB, H, B), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define MI_ATTN_FWD_T(DD, CC, TT)                                                                                      \
-  hipLaunchKernelGGL((mi::attn_fwd_kernel<DD, CC, false, TT>), grid, block, 0, st, (const uint16_t*)q, (const uint16_t*)k, \
-                     (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, q_ts, k_ts, v_ts, o_ts, c, (unsigned long long*)nullptr)
+#define MI_ATTN_FWD_T(DD, CC, TT, WW)                                                                                  \
+  hipLaunchKernelGGL((mi::attn_fwd_kernel<DD, CC, false, TT, WW>), grid, block, 0, st, (const uint16_t*)q, (const uint16_t*)k, \
+                     (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, window, q_ts, k_ts, v_ts, o_ts, c, (unsigned long long*)nullptr)
 #define MI_ATTN_FWD(DD, CC)                                                                                            \
   do {                                                                                                                 \
-    if (tail) MI_ATTN_FWD_T(DD, CC, true); else MI_ATTN_FWD_T(DD, CC, false);                                          \
+    if (tail) MI_ATTN_FWD_T(DD, CC, true, false); else MI_ATTN_FWD_T(DD, CC, false, false);                            \
   } while (0)
-  if (D == 128) {
+#define MI_ATTN_FWD_WIN(DD)                                                                                            \
+  do {                                                                                                                 \
+    if (tail) MI_ATTN_FWD_T(DD, true, true, true); else MI_ATTN_FWD_T(DD, true, false, true);                          \
+  } while (0)
+  if (win) {  // (causal: mi_attn_fwd_win refuses everything else)
+    if (D == 128) MI_ATTN_FWD_WIN(128); else MI_ATTN_FWD_WIN(64);
+  } else if (D == 128) {
     if (causal) MI_ATTN_FWD(128, true); else MI_ATTN_FWD(128, false);
   } else {
     if (causal) MI_ATTN_FWD(64, true); else MI_ATTN_FWD(64, false);
   }
 #undef MI_ATTN_FWD_T
 #undef MI_ATTN_FWD
-  MI_CHECK_LAUNCH("mi_attn_fwd launch");
+#undef MI_ATTN_FWD_WIN
+  MI_CHECK_LAUNCH(window ? "mi_attn_fwd_win launch" : "mi_attn_fwd launch");
   return MI_OK;
+}
+
+extern "C" int mi_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G,
+                           int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
+                           void* stream) {
+  return attn_fwd_launch("mi_attn_fwd", q, k, v, o, lse, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, scale, causal, 0, stream);
+}
+
+extern "C" int mi_attn_fwd_win(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G,
+                               int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
+                               int window, void* stream) {
+  MI_CHECK_ARG(window >= 1, "mi_attn_fwd_win: window %d must be at least 1 (the keys a query sees, itself included)", window);
+  MI_CHECK_ARG(causal != 0, "mi_attn_fwd_win: the window is a band below the causal diagonal: causal must be set");
+  return attn_fwd_launch("mi_attn_fwd_win", q, k, v, o, lse, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, scale, causal, window, stream);
 }
 
 #ifdef MI_DIAG
@@ -558,52 +634,79 @@ extern "C" int mi_attn_fwd_diag(const void* q, const void* k, const void* v, voi
   MI_CHECK_ARG(D == 128 && S % 128 == 0 && H % G == 0, "mi_attn_fwd_diag: unsupported shape");
   dim3 grid(S / mi::ATT_QB, H, B), block(256);
   hipLaunchKernelGGL((mi::attn_fwd_kernel<128, true, true>), grid, block, 0, (hipStream_t)stream, (const uint16_t*)q,
-                     (const uint16_t*)k, (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, q_ts, k_ts, v_ts, o_ts,
+                     (const uint16_t*)k, (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, 0, q_ts, k_ts, v_ts, o_ts,
                      scale * 1.4426950408889634f, dbg);
   MI_CHECK_LAUNCH("mi_attn_fwd_diag launch");
   return MI_OK;
 }
 #endif  // MI_DIAG
 
-extern "C" int mi_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                           float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
-                           int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
-                           int64_t dv_ts, float scale, int causal, void* stream) {
-  MI_CHECK_ARG(q && k && v && o && dout && lse && delta && dq && dk && dv, "mi_attn_bwd: null pointer");
-  MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "mi_attn_bwd: bad B/H/G (%d, %d, %d)", B, H, G);
-  MI_CHECK_ARG(D == 128 || D == 64, "mi_attn_bwd: head_dim %d not supported (64, 128)", D);
-  MI_CHECK_ARG(S >= 128 && S % 16 == 0, "mi_attn_bwd: seq %d must be a multiple of 16 and at least 128", S);
-  MI_CHECK_ARG((q_ts | k_ts | v_ts | o_ts | do_ts | dq_ts | dk_ts | dv_ts) % 8 == 0, "mi_attn_bwd: token strides must be multiples of 8");
+// One host path for mi_attn_bwd (window = 0) and mi_attn_bwd_win (window >= 1), as attn_fwd_launch.
+static int attn_bwd_launch(const char* fn, const void* q, const void* k, const void* v, const void* o, const void* dout,
+                           const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D,
+                           int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
+                           int64_t dv_ts, float scale, int causal, int window, void* stream) {
+  MI_CHECK_ARG(q && k && v && o && dout && lse && delta && dq && dk && dv, "%s: null pointer", fn);
+  MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "%s: bad B/H/G (%d, %d, %d)", fn, B, H, G);
+  MI_CHECK_ARG(D == 128 || D == 64, "%s: head_dim %d not supported (64, 128)", fn, D);
+  MI_CHECK_ARG(S >= 128 && S % 16 == 0, "%s: seq %d must be a multiple of 16 and at least 128", fn, S);
+  MI_CHECK_ARG((q_ts | k_ts | v_ts | o_ts | do_ts | dq_ts | dk_ts | dv_ts) % 8 == 0, "%s: token strides must be multiples of 8", fn);
   MI_CHECK_ARG((int64_t)S * k_ts * 2 < (1LL << 31) && (int64_t)S * v_ts * 2 < (1LL << 31) && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0,
-               "mi_attn_bwd: one batch of K / V must span < 2 GiB and be 16-byte aligned (32-bit buffer offsets of the LDS DMA)");
+               "%s: one batch of K / V must span < 2 GiB and be 16-byte aligned (32-bit buffer offsets of the LDS DMA)", fn);
   MI_CHECK_ARG((((uintptr_t)q | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16) == 0,
-               "mi_attn_bwd: q, o, dout, dq, dk and dv must be 16-byte aligned (16-byte row accesses)");
-  MI_CHECK_ARG(H <= 65535 && B <= 65535, "mi_attn_bwd: grid too large");
+               "%s: q, o, dout, dq, dk and dv must be 16-byte aligned (16-byte row accesses)", fn);
+  MI_CHECK_ARG(H <= 65535 && B <= 65535, "%s: grid too large", fn);
   const float c = scale * 1.4426950408889634f;
   hipStream_t st = (hipStream_t)stream;
   const bool tail = S % mi::ATT_QB != 0;  // a partial last block: the TAIL instantiations; full blocks launch the kernels as before
+  const bool win = window >= 1 && window < S;  // as in attn_fwd_launch
   const int nblk = (S + mi::ATT_QB - 1) / mi::ATT_QB;
   dim3 grid_q(nblk, H, B), grid_kv((unsigned)((int64_t)nblk * G * B)), block(256);
-#define MI_ATTN_BWD_T(DD, CC, TT)                                                                                      \
+#define MI_ATTN_BWD_T(DD, CC, TT, WW)                                                                                  \
   do {                                                                                                                 \
-    hipLaunchKernelGGL((mi::attn_bwd_dq_kernel<DD, CC, TT>), grid_q, block, 0, st, (const uint16_t*)q, (const uint16_t*)k, \
+    hipLaunchKernelGGL((mi::attn_bwd_dq_kernel<DD, CC, TT, WW>), grid_q, block, 0, st, (const uint16_t*)q, (const uint16_t*)k, \
                        (const uint16_t*)v, (const uint16_t*)o, (const uint16_t*)dout, lse, delta, (uint16_t*)dq, S, H,  \
-                       G, q_ts, k_ts, v_ts, o_ts, do_ts, dq_ts, c, scale);                                               \
-    hipLaunchKernelGGL((mi::attn_bwd_dkdv_kernel<DD, CC, TT>), grid_kv, block, 0, st, (const uint16_t*)q,                \
+                       G, window, q_ts, k_ts, v_ts, o_ts, do_ts, dq_ts, c, scale);                                       \
+    hipLaunchKernelGGL((mi::attn_bwd_dkdv_kernel<DD, CC, TT, WW>), grid_kv, block, 0, st, (const uint16_t*)q,            \
                        (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)dout, lse, delta, (uint16_t*)dk,        \
-                       (uint16_t*)dv, S, H, G, B, q_ts, k_ts, v_ts, do_ts, dk_ts, dv_ts, c, scale);                      \
+                       (uint16_t*)dv, S, H, G, B, q_ts, k_ts, v_ts, do_ts, dk_ts, dv_ts, c, scale, window);              \
   } while (0)
 #define MI_ATTN_BWD(DD, CC)                                                                                            \
   do {                                                                                                                 \
-    if (tail) MI_ATTN_BWD_T(DD, CC, true); else MI_ATTN_BWD_T(DD, CC, false);                                          \
+    if (tail) MI_ATTN_BWD_T(DD, CC, true, false); else MI_ATTN_BWD_T(DD, CC, false, false);                            \
   } while (0)
-  if (D == 128) {
+#define MI_ATTN_BWD_WIN(DD)                                                                                            \
+  do {                                                                                                                 \
+    if (tail) MI_ATTN_BWD_T(DD, true, true, true); else MI_ATTN_BWD_T(DD, true, false, true);                          \
+  } while (0)
+  if (win) {  // (causal: mi_attn_bwd_win refuses everything else)
+    if (D == 128) MI_ATTN_BWD_WIN(128); else MI_ATTN_BWD_WIN(64);
+  } else if (D == 128) {
     if (causal) MI_ATTN_BWD(128, true); else MI_ATTN_BWD(128, false);
   } else {
     if (causal) MI_ATTN_BWD(64, true); else MI_ATTN_BWD(64, false);
   }
 #undef MI_ATTN_BWD
+#undef MI_ATTN_BWD_WIN
 #undef MI_ATTN_BWD_T
-  MI_CHECK_LAUNCH("mi_attn_bwd launch");
+  MI_CHECK_LAUNCH(window ? "mi_attn_bwd_win launch" : "mi_attn_bwd launch");
   return MI_OK;
+}
+
+extern "C" int mi_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                           float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
+                           int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
+                           int64_t dv_ts, float scale, int causal, void* stream) {
+  return attn_bwd_launch("mi_attn_bwd", q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, do_ts,
+                         dq_ts, dk_ts, dv_ts, scale, causal, 0, stream);
+}
+
+extern "C" int mi_attn_bwd_win(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                               float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
+                               int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
+                               int64_t dv_ts, float scale, int causal, int window, void* stream) {
+  MI_CHECK_ARG(window >= 1, "mi_attn_bwd_win: window %d must be at least 1 (the keys a query sees, itself included)", window);
+  MI_CHECK_ARG(causal != 0, "mi_attn_bwd_win: the window is a band below the causal diagonal: causal must be set");
+  return attn_bwd_launch("mi_attn_bwd_win", q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, do_ts,
+                         dq_ts, dk_ts, dv_ts, scale, causal, window, stream);
 }

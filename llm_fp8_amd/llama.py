@@ -115,6 +115,9 @@ class TELlamaDecoderLayer(torch.nn.Module):
         super().__init__()
         dev = "cuda" if torch.cuda.is_available() else "cpu"
         self.attn_recipe, self.mlp_recipe = scenario_recipes(self.scenario)
+        if _attention_kwargs is None and getattr(config, "sliding_window", None):
+            # LlamaConfig has no such field: train.py --sliding_window puts it there (another family passes its own kwargs)
+            _attention_kwargs = dict(window_size=(int(config.sliding_window) - 1, 0))
         self.self_attention = te.MultiheadAttention(
             hidden_size=config.hidden_size,
             num_attention_heads=config.num_attention_heads,

@@ -7,12 +7,17 @@ reference's core is bf16 flash-attn through TE, README.md:27-28): the hand-writt
 csrc/mi_attn.hip for the shapes of the reference's configs and collator (causal, head_dim 64 / 128, seq >= 128 and
 seq % 16 == 0 -- the reference pads a batch to a multiple of 16 -- no dropout), the one-workgroup-per-(batch, kv head)
 kernels of csrc/mi_attn_short.hip for the same shapes at the lengths below 128 where they were measured faster (`_SHORT_MIN_S`;
-`LLM_FP8_AMD_NO_SHORT_ATTN=1` turns that route off), torch `scaled_dot_product_attention` otherwise."""
+`LLM_FP8_AMD_NO_SHORT_ATTN=1` turns that route off), torch `scaled_dot_product_attention` otherwise.
+
+Sliding-window causal attention (`window_size=(left, 0)`, TE's and flash-attn's argument; W = left + 1 keys per query, HF's
+`sliding_window`) runs on the band-limited instantiations of the same kernels (mi_attn_fwd_win / mi_attn_bwd_win: O(S * W) work)
+under the conditions of the full-causal route; every other windowed case -- S < 128 with a real band, CPU tensors, dropout,
+`LLM_FP8_AMD_NO_WINDOW_ATTN=1` -- takes `scaled_dot_product_attention` with a cached boolean band mask."""
 from __future__ import annotations
 
 import os
 import weakref
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -146,13 +151,14 @@ class _QKNormRoPESplitFn(torch.autograd.Function):
 
 
 class _FlashAttnFn(torch.autograd.Function):
-    """bshd attention core on mi_attn_fwd / mi_attn_bwd; saves q, k, v, o and the log-sum-exp, never the scores."""
+    """bshd attention core on mi_attn_fwd / mi_attn_bwd (`window` = W: mi_attn_fwd_win / mi_attn_bwd_win); saves q, k, v, o and
+    the log-sum-exp, never the scores."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal):
-        o, lse = ops.attn_fwd(q, k, v, scale, causal)
+    def forward(ctx, q, k, v, scale, causal, window=None):
+        o, lse = ops.attn_fwd(q, k, v, scale, causal, window=window)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.scale, ctx.causal = scale, causal
+        ctx.scale, ctx.causal, ctx.window = scale, causal, window
         return o
 
     @staticmethod
@@ -162,8 +168,11 @@ class _FlashAttnFn(torch.autograd.Function):
         ok = (do.stride(3) == 1 and do.stride(2) == do.shape[3] and do.stride(0) == do.shape[1] * do.stride(1)
               and do.stride(1) % 8 == 0 and do.data_ptr() % 16 == 0)
         do = do if ok else do.clone(memory_format=torch.contiguous_format)  # (a misaligned contiguous view's .contiguous() is itself)
-        dq, dk, dv = ops.attn_bwd(do, q, k, v, o, lse, ctx.scale, ctx.causal)
-        return dq, dk, dv, None, None
+        dq, dk, dv = ops.attn_bwd(do, q, k, v, o, lse, ctx.scale, ctx.causal, window=ctx.window)
+        return dq, dk, dv, None, None, None
+
+
+_WindowAttnFn = _FlashAttnFn  # the same Function: the window is its one further non-tensor argument
 
 
 class _ShortAttnFn(torch.autograd.Function):
@@ -215,20 +224,67 @@ def _short_ok(q, k, v, causal: bool, dropout: float) -> bool:
                and S * t.stride(1) * 2 < 2 ** 31 and t.data_ptr() % 16 == 0 for t in (q, k, v))
 
 
+_BAND_MASKS = {}
+
+
+def _band_mask(S: int, W: int, device) -> torch.Tensor:
+    """[S, S] bool, True = attend: key j of query i with i - W < j <= i.  Built once per (S, W, device)."""
+    key = (S, W, str(device))
+    hit = _BAND_MASKS.get(key)
+    if hit is None:
+        i = torch.arange(S, device=device)
+        d = i[:, None] - i[None, :]
+        hit = (d >= 0) & (d < W)
+        if len(_BAND_MASKS) > 16:
+            _BAND_MASKS.clear()
+        _BAND_MASKS[key] = hit
+    return hit
+
+
 class DotProductAttention(torch.nn.Module):
-    """bf16 attention core.  q [b,s,h,d], k/v [b,s,g,d] (bshd) -> [b,s,h*d]."""
+    """bf16 attention core.  q [b,s,h,d], k/v [b,s,g,d] (bshd) -> [b,s,h*d].
+    `window_size` = (left, right) as in TE: None or left < 0 is the full mask; with a causal mask type right is 0 or -1 and
+    (left, 0) lets a query see itself and the `left` keys before it (W = left + 1)."""
 
     def __init__(self, num_attention_heads: int, kv_channels: int, num_gqa_groups: Optional[int] = None,
-                 attention_dropout: float = 0.0, attn_mask_type: str = "causal", qkv_format: str = "bshd", **_ignored):
+                 attention_dropout: float = 0.0, attn_mask_type: str = "causal", qkv_format: str = "bshd",
+                 window_size: Optional[Tuple[int, int]] = None, **_ignored):
         super().__init__()
         self.h, self.d = num_attention_heads, kv_channels
         self.g = num_gqa_groups or num_attention_heads
         self.p, self.attn_mask_type, self.qkv_format = attention_dropout, attn_mask_type, qkv_format
+        if window_size is not None:
+            left, right = window_size
+            causal = attn_mask_type in ("causal", "padding_causal")
+            if causal and right not in (0, -1):
+                raise ValueError(f"window_size={tuple(window_size)}: with a causal mask type `right` must be 0 or -1")
+            if not causal and left >= 0 and right != 0:  # (left, 0) without a causal type is the same band; the rest is two-sided
+                raise NotImplementedError(f"window_size={tuple(window_size)} with attn_mask_type={attn_mask_type!r}: two-sided "
+                                          "windows are not implemented")
+            window_size = (int(left), int(right)) if left >= 0 else None
+        self.window_size = window_size  # None: the full mask
+
+    def _forward_window(self, q, k, v, W: int, dropout: float):
+        """Causal band of W keys (bshd in, bshd out): the HIP kernels where the full-causal route would take them, else SDPA with
+        the band mask (also under LLM_FP8_AMD_NO_WINDOW_ATTN=1: the route the kernels are tested and timed against)."""
+        causal = self.attn_mask_type in ("causal", "padding_causal")
+        if os.environ.get("LLM_FP8_AMD_NO_WINDOW_ATTN") != "1" and _flash_ok(q, k, v, causal, dropout):
+            return _WindowAttnFn.apply(q, k, v, self.d ** -0.5, True, W)
+        mask = _band_mask(q.shape[1], W, q.device)
+        o = F.scaled_dot_product_attention(*(t.transpose(1, 2) for t in (q, k, v)), attn_mask=mask, dropout_p=dropout,
+                                           enable_gqa=(self.g != self.h))
+        return o.transpose(1, 2)
 
     def forward(self, q, k, v, attention_mask=None):
         if self.qkv_format == "sbhd":
             q, k, v = (t.transpose(0, 1) for t in (q, k, v))
         causal = self.attn_mask_type in ("causal", "padding_causal")
+        # a window at least as long as the sequence is the plain causal mask: today's routes, bit for bit
+        if self.window_size is not None and self.window_size[0] + 1 < q.shape[1]:
+            o = self._forward_window(q, k, v, self.window_size[0] + 1, self.p if self.training else 0.0)
+            if self.qkv_format == "sbhd":
+                o = o.transpose(0, 1)
+            return o.reshape(*o.shape[:2], self.h * self.d)
         flash = _flash_ok(q, k, v, causal, self.p if self.training else 0.0)
         if flash or _short_ok(q, k, v, causal, self.p if self.training else 0.0):
             o = _FlashAttnFn.apply(q, k, v, self.d ** -0.5, True) if flash else _ShortAttnFn.apply(q, k, v, self.d ** -0.5)
@@ -260,7 +316,8 @@ class MultiheadAttention(torch.nn.Module):
                  input_layernorm: bool = False, attention_type: str = "self", fuse_qkv_params: bool = False,
                  zero_centered_gamma: bool = False, qkv_weight_interleaved: bool = True, bias: bool = True,
                  normalization: str = "LayerNorm", qkv_format: str = "sbhd", params_dtype=None, device="cuda",
-                 qk_norm_type: Optional[str] = None, qk_norm_eps: float = 1e-6, qk_norm_before_rope: bool = True, **_ignored):
+                 qk_norm_type: Optional[str] = None, qk_norm_eps: float = 1e-6, qk_norm_before_rope: bool = True,
+                 window_size: Optional[Tuple[int, int]] = None, **_ignored):
         super().__init__()
         assert attention_type == "self", "only self-attention is on the reference path"
         assert qkv_format in ("sbhd", "bshd")
@@ -287,7 +344,8 @@ class MultiheadAttention(torch.nn.Module):
         else:
             self.qkv = Linear(hidden_size, sum(self.split), bias=bias, params_dtype=params_dtype, device=device,
                               init_method=init_method)
-        self.core_attention = DotProductAttention(self.h, self.d, self.g, attention_dropout, attn_mask_type, qkv_format)
+        self.core_attention = DotProductAttention(self.h, self.d, self.g, attention_dropout, attn_mask_type, qkv_format,
+                                                  window_size=window_size)
         self.proj = Linear(q_out, hidden_size, bias=bias, params_dtype=params_dtype, device=device,
                            init_method=output_layer_init_method or init_method)
         if qk_norm_type == "RMSNorm":  # per-head norm over head_dim (HF Qwen3 `q_norm` / `k_norm`): one weight [d] each

@@ -912,9 +912,20 @@ def _bshd_ok(t: torch.Tensor, D: int):
     assert t.stride(0) == t.shape[1] * t.stride(1), "batch and sequence must collapse to one token stride"
 
 
-def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True, out=None):
+def attn_window_walk(S: int, window: int, block: int):
+    """What the band-limited kernels walk for 128-row block `block` at a window below S: (first 64-key tile of the forward / dQ
+    loop, tiles in it, 32-row query slices per head of the dK/dV sweep).  Full causal: (0, 2 * block + 2, (S - 128 * block) / 32)."""
+    wm1, first = window - 1, 128 * block
+    j0 = max(0, first - wm1) // 64
+    return j0, min(2 * block + 2, -(-S // 64)) - j0, min(-(-S // 32) - 4 * block, (128 + wm1 + 31) // 32)
+
+
+def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True, out=None,
+             window: Optional[int] = None):
     """Attention core.  q [B, S, H, D], k/v [B, S, G, D] bf16 (views with a token stride are fine) -> (o [B, S, H, D], lse [B, H, S]).
-    `out` = optional preallocated (o, lse): o may be a view with its own token stride, lse is contiguous fp32."""
+    `out` = optional preallocated (o, lse): o may be a view with its own token stride, lse is contiguous fp32.
+    `window` = W (causal only): query i sees the W keys i - W < j <= i and `lse` is the band's; the kernels walk only the band
+    (attn_window_walk), and W >= S is the plain causal call, bit for bit.  None takes mi_attn_fwd."""
     _dev(q, k, v)
     B, S, H, D = q.shape
     G = k.shape[2]
@@ -929,15 +940,21 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, ca
         _bshd_ok(o, D)
         assert o.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1),
-            v.stride(1), o.stride(1), float(scale), int(causal), _stream())
-    _launch(_lib.load().mi_attn_fwd, args, "mi_attn_fwd", "attn_fwd",
+            v.stride(1), o.stride(1), float(scale), int(causal))
+    if window is not None:
+        _launch(_lib.require("mi_attn_fwd_win", "sliding-window attention"), args + (int(window), _stream()), "mi_attn_fwd_win",
+                "attn_fwd_win", lambda: (f"{B}x{S}x{H}x{D}w{window}", 4.0 * B * H * S * min(window, S / 2) * D,
+                                         2.0 * (q.numel() * 2 + k.numel() * 2)))
+        return o, lse
+    _launch(_lib.load().mi_attn_fwd, args + (_stream(),), "mi_attn_fwd", "attn_fwd",
             lambda: (f"{B}x{S}x{H}x{D}", 4.0 * B * H * S * S * D * (0.5 if causal else 1.0), 2.0 * (q.numel() * 2 + k.numel() * 2)))
     return o, lse
 
 
 def attn_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor,
-             scale: float, causal: bool = True, out=None):
-    """Backward of attn_fwd -> (dq [B,S,H,D], dk, dv [B,S,G,D]).  `out` = optional preallocated (dq, dk, dv) views."""
+             scale: float, causal: bool = True, out=None, window: Optional[int] = None):
+    """Backward of attn_fwd -> (dq [B,S,H,D], dk, dv [B,S,G,D]).  `out` = optional preallocated (dq, dk, dv) views.
+    `window`: the value the forward was called with (None takes mi_attn_bwd)."""
     _dev(do, q, k, v, o, lse)
     B, S, H, D = q.shape
     G = k.shape[2]
@@ -957,8 +974,13 @@ def attn_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), delta.data_ptr(),
             dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1), v.stride(1), o.stride(1),
-            do.stride(1), dq.stride(1), dk.stride(1), dv.stride(1), float(scale), int(causal), _stream())
-    _launch(_lib.load().mi_attn_bwd, args, "mi_attn_bwd", "attn_bwd",   # 7 products: S, dP, dQ | S, dP, dV, dK
+            do.stride(1), dq.stride(1), dk.stride(1), dv.stride(1), float(scale), int(causal))
+    if window is not None:
+        _launch(_lib.require("mi_attn_bwd_win", "sliding-window attention"), args + (int(window), _stream()), "mi_attn_bwd_win",
+                "attn_bwd_win", lambda: (f"{B}x{S}x{H}x{D}w{window}", 14.0 * B * H * S * min(window, S / 2) * D,
+                                         2.0 * (3 * q.numel() + 4 * k.numel())))
+        return dq, dk, dv
+    _launch(_lib.load().mi_attn_bwd, args + (_stream(),), "mi_attn_bwd", "attn_bwd",   # 7 products: S, dP, dQ | S, dP, dV, dK
             lambda: (f"{B}x{S}x{H}x{D}", 14.0 * B * H * S * S * D * (0.5 if causal else 1.0), 2.0 * (3 * q.numel() + 4 * k.numel())))
     return dq, dk, dv
 

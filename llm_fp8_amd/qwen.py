@@ -75,18 +75,40 @@ def _rope_type(config) -> str:
     return "default"
 
 
+def sliding_layer(config, layer_idx: int) -> bool:
+    """Whether layer `layer_idx` of a `use_sliding_window` config attends a window: `layer_types` where transformers provides it,
+    else HF's rule `layer_idx >= max_window_layers`."""
+    types = getattr(config, "layer_types", None)
+    if types is not None:
+        return types[layer_idx] == "sliding_attention"
+    return layer_idx >= config.max_window_layers
+
+
 class TEQwen3DecoderLayer(TELlamaDecoderLayer):
-    """TELlamaDecoderLayer with the per-head QK RMSNorm and the config's rotary base; `forward` (both routes) is inherited."""
+    """TELlamaDecoderLayer with the per-head QK RMSNorm and the config's rotary base; `forward` (both routes) is inherited.
+    Under `config.use_sliding_window` a sliding layer (`sliding_layer`) attends the last `config.sliding_window` keys; a config that
+    sets the flag and selects no sliding layer (max_window_layers >= num_hidden_layers) is refused, not built with full attention."""
 
     def __init__(self, config, *args, **kwargs):
         if _rope_type(config) != "default":
             raise NotImplementedError(f"TEQwen3DecoderLayer: rope_type {_rope_type(config)!r} is not implemented (only 'default')")
-        if getattr(config, "use_sliding_window", False):
-            raise NotImplementedError("TEQwen3DecoderLayer: use_sliding_window=True is not implemented (full causal attention only)")
         if getattr(config, "attention_bias", False):
             raise NotImplementedError("TEQwen3DecoderLayer: attention_bias=True is not implemented")
-        super().__init__(config, *args, _attention_kwargs=dict(qk_norm_type="RMSNorm", qk_norm_eps=config.rms_norm_eps),
-                         _mlp_kwargs=dict(eps=config.rms_norm_eps), _rope_base=rope_base(config), **kwargs)
+        attn = dict(qk_norm_type="RMSNorm", qk_norm_eps=config.rms_norm_eps)
+        if getattr(config, "use_sliding_window", False):
+            layer_idx = args[0] if args else kwargs.get("layer_idx")  # HF: Qwen3DecoderLayer(config, layer_idx)
+            if layer_idx is None:
+                raise ValueError("TEQwen3DecoderLayer: use_sliding_window=True needs the layer_idx HF passes to its decoder layers")
+            if not any(sliding_layer(config, i) for i in range(config.num_hidden_layers)):
+                # HF builds such a model with full attention everywhere and says nothing: whoever set the flag trains another mask
+                raise NotImplementedError(
+                    f"TEQwen3DecoderLayer: use_sliding_window=True selects no sliding layer (max_window_layers="
+                    f"{getattr(config, 'max_window_layers', None)} with {config.num_hidden_layers} layers): lower max_window_layers, "
+                    "or set use_sliding_window=False for full causal attention")
+            if sliding_layer(config, layer_idx):
+                attn["window_size"] = (int(config.sliding_window) - 1, 0)
+        super().__init__(config, *args, _attention_kwargs=attn, _mlp_kwargs=dict(eps=config.rms_norm_eps),
+                         _rope_base=rope_base(config), **kwargs)
 
 
 def decoder_layer_cls(scenario: str):

@@ -49,6 +49,7 @@ class TrainingConfig:
     optimizer_state: Optional[str] = None  # "bf16" | "fp32" | "bf16_sr" (optim.ClippedAdamW); None: resolve_optimizer_state
     skip_nonfinite_steps: bool = True     # ClippedAdamW drops a step whose gradient norm is Inf / NaN (resolve_skip_nonfinite)
     grad_accum_dtype: Optional[str] = None  # "bf16" | "fp32" (grad_accum.GradAccumulator); None: resolve_grad_accum_dtype
+    sliding_window: Optional[int] = None  # every layer attends the last N keys (causal band; attention.DotProductAttention window_size)
 
 
 def create_model(cfg: TrainingConfig, device) -> torch.nn.Module:
@@ -60,6 +61,12 @@ def create_model(cfg: TrainingConfig, device) -> torch.nn.Module:
         over["vocab_size"] = cfg.vocab_size
     # the family follows the name: `qwen3...` / `qwen/qwen3...` is Qwen3 (qwen.py), everything else Llama
     from . import qwen
+    if cfg.sliding_window is not None:
+        if cfg.sliding_window < 1:
+            raise ValueError(f"sliding_window={cfg.sliding_window}: at least 1 (the keys a query sees, itself included)")
+        over["sliding_window"] = cfg.sliding_window  # Llama: an extra config field that TELlamaDecoderLayer turns into window_size
+        if qwen.is_qwen3_name(cfg.model_name):
+            over.update(use_sliding_window=True, max_window_layers=0)
     try:
         if qwen.is_qwen3_name(cfg.model_name):
             from transformers.models.qwen3.modeling_qwen3 import Qwen3ForCausalLM as hf_cls
@@ -433,6 +440,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--grad_accum_dtype", choices=GRAD_ACCUM_DTYPES, default=None,
                     help="what a window of --gradient_accumulation_steps micro-batches is summed in: bf16 (default; or "
                          "$LLM_FP8_AMD_GRAD_ACCUM; autograd's adds into .grad) | fp32 main_grad sums, rounded to bf16 once")
+    ap.add_argument("--sliding_window", type=int, default=None,
+                    help="sliding-window causal attention in every layer: a query sees itself and the N - 1 keys before it")
     ap.add_argument("--no_skip_nonfinite_steps", action="store_true",
                     help="let a step with an Inf / NaN gradient norm through (ClippedAdamW drops it on the device by default)")
     return ap
@@ -445,7 +454,7 @@ def config_from_args(a) -> TrainingConfig:
                          num_hidden_layers=a.num_hidden_layers, vocab_size=a.vocab_size, num_warmup_steps=a.num_warmup_steps,
                          gradient_accumulation_steps=a.gradient_accumulation_steps, output_dir=a.output_dir, load_dir=a.load_dir,
                          optimizer_state=a.optimizer_state, skip_nonfinite_steps=not a.no_skip_nonfinite_steps,
-                         grad_accum_dtype=a.grad_accum_dtype)
+                         grad_accum_dtype=a.grad_accum_dtype, sliding_window=a.sliding_window)
 
 
 def main(argv=None):
