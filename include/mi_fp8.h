@@ -77,9 +77,11 @@ extern "C" {
  *   8  mi_attn_short_fwd, mi_attn_short_bwd (the attention core at 16 <= S <= 112: one workgroup per (batch, kv head), one
  *      launch each way)
  *   9  mi_attn_fwd_win, mi_attn_bwd_win (sliding-window causal attention: band-limited forward, dQ and dK/dV kernels)
+ *  10  mi_attn_fwd_seg, mi_attn_bwd_seg (packed-sequence causal attention: several documents in a row, each token attends
+ *      inside its own; the same three kernels walk only the documents)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 9
+#define MI_ABI_REVISION 10
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -692,6 +694,27 @@ int mi_attn_bwd_win(const void* q, const void* k, const void* v, const void* o, 
                     float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
                     int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts, int64_t dv_ts,
                     float scale, int causal, int window, void* stream);
+
+/*
+ * Packed-sequence causal attention (revision 10): mi_attn_fwd / mi_attn_bwd with `seg_start, seg_end` in front of `stream`.  A row
+ * of S tokens holds several documents back to back; seg_start and seg_end are int32 [B, S] device arrays that give, for token t of
+ * row b, the index within the row of the first token of its document and one past its last.  Query i attends keys j with
+ * seg_start[i] <= j <= i.  Within a row both arrays are non-decreasing.  `lse` and `delta` keep their layout; `lse` is the
+ * log-sum-exp over the row's document.  The kernels walk only the documents: O(sum len^2) work.  One document per row
+ * (seg_start = 0, seg_end = S) gives the bits of mi_attn_fwd / mi_attn_bwd.
+ *   The launcher cannot inspect device arrays without a host synchronisation and does not: the kernels clamp every value they
+ * read, seg_start[t] to [0, t] and seg_end[t] to [t + 1, S].  Arrays with wrong contents may give wrong numbers; they never give an
+ * access outside the tensors nor a row without a key.  The forward and dQ kernels read seg_start, the dK/dV kernel seg_end.
+ *   Refused before any launch: a null segment pointer or one not 4-byte aligned, causal == 0, and everything mi_attn_fwd /
+ * mi_attn_bwd refuse.  No atomics and no sums across workgroups: results are bitwise reproducible.
+ */
+int mi_attn_fwd_seg(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G, int D,
+                    int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal, const int32_t* seg_start,
+                    const int32_t* seg_end, void* stream);
+int mi_attn_bwd_seg(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                    float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
+                    int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts, int64_t dv_ts,
+                    float scale, int causal, const int32_t* seg_start, const int32_t* seg_end, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,9 @@
 //
 // Sliding window (mi_attn_fwd_win / mi_attn_bwd_win, causal only): query i sees the `window` keys i - window < j <= i.  The WIN = true
 // instantiations walk only the band (see the WIN note below); WIN = false is the code without any of it.
+//
+// Packed sequences (mi_attn_fwd_seg / mi_attn_bwd_seg, causal only): a row holds several documents and query i sees the keys
+// seg_start[i] <= j <= i of its own.  The SEG = true instantiations walk only the documents (see the SEG note below): O(sum len^2).
 #include "mi_attn_dev.h"
 
 namespace mi {
@@ -46,14 +49,33 @@ constexpr int ATT_KB = 64;   // keys per tile
 //   dK / dV    the sweep over query slices ends at the last slice from which any key of the workgroup is seen (query
 //              kbi * 128 + 127 + wm1, clamped to S); a wave skips the slices past its own band (q0 > key_first + 31 + wm1), and
 //              on the slices that cross the band edge p and dS are 0 where query > key + wm1.
-// `window` sits in what was alignment padding of the argument block (fwd, dQ) or at its end (dK/dV), and only WIN reads it.
-template <int D, bool CAUSAL, bool DIAG = false, bool TAIL = false, bool WIN = false>
+// SEG (all three kernels, CAUSAL only, never with WIN): the band's lower edge is per row, the first token of the row's document.
+// seg_start / seg_end [B, S] int32 hold, for token t, the first token of its document and one past its last; both are non-decreasing
+// along a row.  Every value read goes through seg_lo / seg_hi (mi_attn_dev.h): start in [0, t], end in [t + 1, S].  Arrays with
+// wrong contents give wrong numbers, never an access outside the row and never a row without a key (the loops' bounds below stay
+// inside the causal walk, and the tile / slice that holds a token's own key is never skipped or masked for it).
+//   fwd / dQ   each lane keeps its row's start; the wave's first and last rows' starts come from lanes 0 and 31.  The tile loop
+//              starts at j0 = start of the workgroup's first row / 64, the smallest start in the block (same parity rule as WIN).
+//              A wave whose rows all start above a tile (key0 + 63 < start of q_first) stages and meets the barrier only; a tile
+//              with key0 < start of the wave's last row is masked per element (key < the lane's start), one compare + select;
+//              every other tile below the diagonal is the unmasked code.  A row whose first visited tile is all masked for it
+//              relies on the finite initial maximum, as under WIN.
+//   dK / dV    each lane keeps its key's end.  The sweep ends at the end of the workgroup's last key (clamped to S - 1), rounded up
+//              to a slice: the largest end in the block.  A wave skips slices with q0 >= end of its last key; on slices that hold a
+//              query at or past the end of its first key, p and dS are 0 where query >= the lane's end.  For key <= query that is
+//              the predicate seg_start[query] <= key, so the passes agree.
+// `window` sits in what was alignment padding of the argument block (fwd, dQ) or at its end (dK/dV), and only WIN reads it; the segment pointers follow
+// at the very end, and only SEG reads them.
+template <int D, bool CAUSAL, bool DIAG = false, bool TAIL = false, bool WIN = false, bool SEG = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                           const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                           float* __restrict__ lse, int S, int H, int G, int window,
                                                           int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float c,
-                                                          unsigned long long* __restrict__ dbg = nullptr) {
+                                                          unsigned long long* __restrict__ dbg = nullptr,
+                                                          const int32_t* __restrict__ seg_start = nullptr,
+                                                          const int32_t* __restrict__ seg_end = nullptr) {
   static_assert(!WIN || CAUSAL, "the window is a band below the causal diagonal");
+  static_assert(!SEG || (CAUSAL && !WIN), "documents are bands below the causal diagonal, and not combined with a window");
   constexpr int TILE = ATT_KB * D * 2;  // bytes of one K (or V) tile
   constexpr int KT = D / 16, DB = D / 32;
   __shared__ __attribute__((aligned(16))) char lds[4 * TILE];
@@ -67,7 +89,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
     ntiles = CAUSAL ? min(ntiles, stiles) : stiles;
   }
   const int wm1 = WIN ? window - 1 : 0;
-  const int j0 = WIN ? max(0, qb * ATT_QB - wm1) / ATT_KB : 0;  // first tile any row of the workgroup sees (j0 < ntiles: the diagonal tile is later)
+  // first tile any row of the workgroup sees (j0 < ntiles: the diagonal tile is later)
+  const int j0 = WIN ? max(0, qb * ATT_QB - wm1) / ATT_KB : SEG ? seg_lo(seg_start + (int64_t)b * S, qb * ATT_QB) / ATT_KB : 0;
+  // (SEG) first key of this lane's row, and of the wave's first and last rows (rows at or past S take row S - 1's; nothing of theirs is stored)
+  const int ss = SEG ? seg_lo(seg_start + (int64_t)b * S, TAIL ? min(qrow, S - 1) : qrow) : 0;
+  const int ss_first = SEG ? __builtin_amdgcn_readlane(ss, 0) : 0, ss_last = SEG ? __builtin_amdgcn_readlane(ss, 31) : 0;
   const uint16_t* kbase = k + (int64_t)b * S * k_ts + (int64_t)g * D;
   const uint16_t* vbase = v + (int64_t)b * S * v_ts + (int64_t)g * D;
 
@@ -94,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
   int kvo[D / 32], vvo[D / 32];
   dma_voffsets<D>(kvo, k_ts, tid);
   dma_voffsets<D>(vvo, v_ts, tid);
-  if (WIN) {
+  if (WIN || SEG) {
     stage_tile<D, TAIL>(rsK, kvo, (int)((int64_t)j0 * ATT_KB * k_ts * 2), lds + (j0 & 1) * TILE, w);
     stage_tile<D, TAIL>(rsV, vvo, (int)((int64_t)j0 * ATT_KB * v_ts * 2), lds + (2 + (j0 & 1)) * TILE, w);
   } else {
@@ -125,8 +151,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
     }
     const int key0 = j * ATT_KB;
     // wave-uniform: tiles entirely above the diagonal contribute nothing (TAIL: nor does a wave whose rows are all past S)
-    // (WIN: nor a tile entirely below the band of the wave's first row)
-    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31) && (!WIN || key0 + ATT_KB - 1 >= q_first - wm1)) {
+    // (WIN: nor a tile entirely below the band of the wave's first row; SEG: nor one entirely before that row's document)
+    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31) && (!WIN || key0 + ATT_KB - 1 >= q_first - wm1) &&
+        (!SEG || key0 + ATT_KB - 1 >= ss_first)) {
       f16v sacc[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -162,6 +189,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
 #pragma unroll
           for (int i = 0; i < 16; ++i)
             if (key0 + 32 * kb + acc_row(i, h) < qrow - wm1) sacc[kb][i] = -INFINITY;
+      }
+      if (SEG && key0 < ss_last) {  // tile holds a key in front of the document of some row of the wave
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (key0 + 32 * kb + acc_row(i, h) < ss) sacc[kb][i] = -INFINITY;
       }
       if (TAIL && !CAUSAL && key0 + ATT_KB > S) {  // keys at or past S were staged as zeros: a score of 0, not -inf
 #pragma unroll
@@ -259,14 +293,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
 // dQ pass: same walk as the forward (128 query rows per workgroup, 64-key tiles).  S^T and dP^T are recomputed with the
 // query on the lane (LSE and delta are lane constants), dS^T feeds  dQ^T += K^T . dS^T  straight from the accumulators.
 // Also writes delta[b, h, q] = sum_d dO * O for the dK/dV pass.
-template <int D, bool CAUSAL, bool TAIL = false, bool WIN = false>
+template <int D, bool CAUSAL, bool TAIL = false, bool WIN = false, bool SEG = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                              const uint16_t* __restrict__ v, const uint16_t* __restrict__ o,
                                                              const uint16_t* __restrict__ dout, const float* __restrict__ lse,
                                                              float* __restrict__ delta, uint16_t* __restrict__ dq, int S,
                                                              int H, int G, int window, int64_t q_ts, int64_t k_ts, int64_t v_ts,
-                                                             int64_t o_ts, int64_t do_ts, int64_t dq_ts, float c, float scale) {
+                                                             int64_t o_ts, int64_t do_ts, int64_t dq_ts, float c, float scale,
+                                                             const int32_t* __restrict__ seg_start = nullptr,
+                                                             const int32_t* __restrict__ seg_end = nullptr) {
   static_assert(!WIN || CAUSAL, "the window is a band below the causal diagonal");
+  static_assert(!SEG || (CAUSAL && !WIN), "documents are bands below the causal diagonal, and not combined with a window");
   constexpr int TILE = ATT_KB * D * 2;
   constexpr int KT = D / 16, DB = D / 32;
   __shared__ __attribute__((aligned(16))) char lds[4 * TILE];
@@ -280,7 +317,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
     ntiles = CAUSAL ? min(ntiles, stiles) : stiles;
   }
   const int wm1 = WIN ? window - 1 : 0;
-  const int j0 = WIN ? max(0, qb * ATT_QB - wm1) / ATT_KB : 0;  // first tile any row of the workgroup sees (j0 < ntiles: the diagonal tile is later)
+  // first tile any row of the workgroup sees (j0 < ntiles: the diagonal tile is later)
+  const int j0 = WIN ? max(0, qb * ATT_QB - wm1) / ATT_KB : SEG ? seg_lo(seg_start + (int64_t)b * S, qb * ATT_QB) / ATT_KB : 0;
+  // (SEG) first key of this lane's row, and of the wave's first and last rows (rows at or past S take row S - 1's; nothing of theirs is stored)
+  const int ss = SEG ? seg_lo(seg_start + (int64_t)b * S, TAIL ? min(qrow, S - 1) : qrow) : 0;
+  const int ss_first = SEG ? __builtin_amdgcn_readlane(ss, 0) : 0, ss_last = SEG ? __builtin_amdgcn_readlane(ss, 31) : 0;
   const uint16_t* kbase = k + (int64_t)b * S * k_ts + (int64_t)g * D;
   const uint16_t* vbase = v + (int64_t)b * S * v_ts + (int64_t)g * D;
 
@@ -328,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
   int kvo[D / 32], vvo[D / 32];
   dma_voffsets<D>(kvo, k_ts, tid);
   dma_voffsets<D>(vvo, v_ts, tid);
-  if (WIN) {
+  if (WIN || SEG) {
     stage_tile<D, TAIL>(rsK, kvo, (int)((int64_t)j0 * ATT_KB * k_ts * 2), lds + (j0 & 1) * TILE, w);
     stage_tile<D, TAIL>(rsV, vvo, (int)((int64_t)j0 * ATT_KB * v_ts * 2), lds + (2 + (j0 & 1)) * TILE, w);
   } else {
@@ -373,11 +414,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
       }
       const bool diag = CAUSAL && key0 + 32 * kb + 31 > q_first;
       const bool edge = WIN && key0 + 32 * kb < q_first + 31 - wm1;  // block holds a key below the band of the wave's last row
+      const bool sedge = SEG && key0 + 32 * kb < ss_last;            // block holds a key in front of the document of the wave's last row
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[i], c, -my_lse));
         if (diag && key0 + 32 * kb + acc_row(i, h) > qrow) p = 0.0f;
         if (edge && key0 + 32 * kb + acc_row(i, h) < qrow - wm1) p = 0.0f;  // a select: whatever exp2 gave for a key outside the band
+        if (sedge && key0 + 32 * kb + acc_row(i, h) < ss) p = 0.0f;
         if (TAIL && !CAUSAL && key0 + 32 * kb + acc_row(i, h) >= S) p = 0.0f;  // keys staged as zeros
         sacc[i] = p * (pacc[i] - dl);
       }
@@ -398,9 +441,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
     };
     // (wave-uniform tests: blocks entirely above the diagonal contribute nothing)
     // (TAIL: nor does a wave whose rows are all past S, nor a block whose keys are)
-    // (WIN: nor a block entirely below the band of the wave's first row)
-    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31) && (!WIN || key0 + 31 >= q_first - wm1)) block(0);
-    if ((!TAIL || (q_first < S && key0 + 32 < S)) && (!CAUSAL || key0 + 32 <= q_first + 31) && (!WIN || key0 + 63 >= q_first - wm1)) block(1);
+    // (WIN: nor a block entirely below the band of the wave's first row; SEG: nor one entirely before that row's document)
+    if ((!TAIL || q_first < S) && (!CAUSAL || key0 <= q_first + 31) && (!WIN || key0 + 31 >= q_first - wm1) && (!SEG || key0 + 31 >= ss_first)) block(0);
+    if ((!TAIL || (q_first < S && key0 + 32 < S)) && (!CAUSAL || key0 + 32 <= q_first + 31) && (!WIN || key0 + 63 >= q_first - wm1) &&
+        (!SEG || key0 + 63 >= ss_first)) block(1);
     dma_wait_all();  // the next tile has landed (this wave's share; the barrier covers the others')
     __syncthreads();
   }
@@ -412,15 +456,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
 // B operands (key on the lane) and dK^T, dV^T of those keys in accumulators while the workgroup sweeps the group's query
 // heads x 32-row query slices (Q and dO slices staged once for all four waves; row reads for S and dP, transposed reads
 // for the dV^T and dK^T products).
-template <int D, bool CAUSAL, bool TAIL = false, bool WIN = false>
+template <int D, bool CAUSAL, bool TAIL = false, bool WIN = false, bool SEG = false>
 __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                                const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                uint16_t* __restrict__ dk, uint16_t* __restrict__ dv, int S, int H,
                                                                int G, int B, int64_t q_ts, int64_t k_ts, int64_t v_ts,
                                                                int64_t do_ts, int64_t dk_ts, int64_t dv_ts, float c, float scale,
-                                                               int window = 0) {
+                                                               int window = 0, const int32_t* __restrict__ seg_start = nullptr,
+                                                               const int32_t* __restrict__ seg_end = nullptr) {
   static_assert(!WIN || CAUSAL, "the window is a band below the causal diagonal");
+  static_assert(!SEG || (CAUSAL && !WIN), "documents are bands below the causal diagonal, and not combined with a window");
   constexpr int SL = 32 * D * 2;  // bytes of one 32-row slice image
   constexpr int KT = D / 16, DB = D / 32;
   constexpr int BUF = 2 * SL + 256;  // Q slice, dO slice, lse[32], delta[32]
@@ -459,7 +505,13 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
   const int sl0 = CAUSAL ? (kbi * 128) / 32 : 0;  // first query slice that can see this key block
   const int wm1 = WIN ? window - 1 : 0;
   // (WIN: the last key of the block is seen from query kbi * 128 + 127 + wm1 and no later: (128 + wm1 + 31) / 32 slices at most)
-  const int nsl = WIN ? min((TAIL ? (S + 31) / 32 : S / 32) - sl0, (128 + wm1 + 31) / 32) : (TAIL ? (S + 31) / 32 : S / 32) - sl0;
+  // (SEG: the last key of the block is seen up to the end of its document and no later; that end is past the key, so nsl >= 1)
+  const int nsl = WIN   ? min((TAIL ? (S + 31) / 32 : S / 32) - sl0, (128 + wm1 + 31) / 32)
+                  : SEG ? min((TAIL ? (S + 31) / 32 : S / 32), (seg_hi(seg_end + (int64_t)b * S, TAIL ? min(kbi * 128 + 127, S - 1) : kbi * 128 + 127, S) + 31) / 32) - sl0
+                        : (TAIL ? (S + 31) / 32 : S / 32) - sl0;
+  // (SEG) one past the last query that sees this lane's key, and the wave's first and last keys' (keys at or past S take key S - 1's)
+  const int se = SEG ? seg_hi(seg_end + (int64_t)b * S, TAIL ? min(key, S - 1) : key, S) : 0;
+  const int se_first = SEG ? __builtin_amdgcn_readlane(se, 0) : 0, se_last = SEG ? __builtin_amdgcn_readlane(se, 31) : 0;
   const int nsteps = rep * nsl;
   // staging: thread -> 2 chunks of the Q slice and 2 of the dO slice; threads 0..31 lse, 32..63 delta
   v4i qreg[2], dreg[2];
@@ -507,8 +559,8 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
     if (more) load_step(step + 1);
     const int q0 = (sl0 + step % nsl) * 32;
     // wave-uniform: slices entirely before this wave's keys see none of them (TAIL: a wave whose keys are all past S has no sums)
-    // (WIN: nor do the slices past the band of the wave's last key)
-    if ((!TAIL || key_first < S) && (!CAUSAL || q0 + 31 >= key_first) && (!WIN || q0 <= key_first + 31 + wm1)) {
+    // (WIN: nor do the slices past the band of the wave's last key; SEG: nor those past the document of that key)
+    if ((!TAIL || key_first < S) && (!CAUSAL || q0 + 31 >= key_first) && (!WIN || q0 <= key_first + 31 + wm1) && (!SEG || q0 < se_last)) {
       const char* qt = buf;
       const char* dt = buf + SL;
       const float* st = reinterpret_cast<const float*>(buf + 2 * SL);
@@ -522,6 +574,7 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
       }
       const bool diag = CAUSAL && q0 < key_first + 31;
       const bool edge = WIN && q0 + 31 > key_first + wm1;  // slice holds a query past the band of the wave's first key
+      const bool sedge = SEG && q0 + 31 >= se_first;       // slice holds a query past the document of the wave's first key
       f16v dsacc;
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
@@ -533,6 +586,7 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
           float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[i], c, -ls[e]));
           if (diag && key > q0 + acc_row(i, h)) p = 0.0f;
           if (edge && q0 + acc_row(i, h) > key + wm1) p = 0.0f;
+          if (sedge && q0 + acc_row(i, h) >= se) p = 0.0f;
           if (TAIL && q0 + acc_row(i, h) >= S) p = 0.0f;  // a select: p and dS of a row past S are 0 whatever exp2 gave
           sacc[i] = p;
           dsacc[i] = p * (pacc[i] - dl[e]);
@@ -567,10 +621,11 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
 
 }  // namespace mi
 
-// One host path for mi_attn_fwd (window = 0: no band) and mi_attn_fwd_win (window >= 1); `fn` names the entry point in every refusal.
+// One host path for mi_attn_fwd (window = 0: no band), mi_attn_fwd_win (window >= 1) and mi_attn_fwd_seg (seg_start, seg_end set:
+// documents); `fn` names the entry point in every refusal.
 static int attn_fwd_launch(const char* fn, const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
                            int G, int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
-                           int window, void* stream) {
+                           int window, const int32_t* seg_start, const int32_t* seg_end, void* stream) {
   MI_CHECK_ARG(q && k && v && o && lse, "%s: null pointer", fn);
   MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "%s: bad B/H/G (%d, %d, %d)", fn, B, H, G);
   MI_CHECK_ARG(D == 128 || D == 64, "%s: head_dim %d not supported (64, 128)", fn, D);
@@ -585,18 +640,25 @@ static int attn_fwd_launch(const char* fn, const void* q, const void* k, const v
   const bool win = window >= 1 && window < S;  // a window that covers every causal key is the plain causal mask: the kernels as before
   dim3 grid((S + mi::ATT_QB - 1) / mi::ATT_QB, H, B), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define MI_ATTN_FWD_T(DD, CC, TT, WW)                                                                                  \
-  hipLaunchKernelGGL((mi::attn_fwd_kernel<DD, CC, false, TT, WW>), grid, block, 0, st, (const uint16_t*)q, (const uint16_t*)k, \
-                     (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, window, q_ts, k_ts, v_ts, o_ts, c, (unsigned long long*)nullptr)
+#define MI_ATTN_FWD_T(DD, CC, TT, WW, SS)                                                                              \
+  hipLaunchKernelGGL((mi::attn_fwd_kernel<DD, CC, false, TT, WW, SS>), grid, block, 0, st, (const uint16_t*)q,         \
+                     (const uint16_t*)k, (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, window, q_ts, k_ts, v_ts, o_ts, c, \
+                     (unsigned long long*)nullptr, seg_start, seg_end)
 #define MI_ATTN_FWD(DD, CC)                                                                                            \
   do {                                                                                                                 \
-    if (tail) MI_ATTN_FWD_T(DD, CC, true, false); else MI_ATTN_FWD_T(DD, CC, false, false);                            \
+    if (tail) MI_ATTN_FWD_T(DD, CC, true, false, false); else MI_ATTN_FWD_T(DD, CC, false, false, false);              \
   } while (0)
 #define MI_ATTN_FWD_WIN(DD)                                                                                            \
   do {                                                                                                                 \
-    if (tail) MI_ATTN_FWD_T(DD, true, true, true); else MI_ATTN_FWD_T(DD, true, false, true);                          \
+    if (tail) MI_ATTN_FWD_T(DD, true, true, true, false); else MI_ATTN_FWD_T(DD, true, false, true, false);            \
   } while (0)
-  if (win) {  // (causal: mi_attn_fwd_win refuses everything else)
+#define MI_ATTN_FWD_SEG(DD)                                                                                            \
+  do {                                                                                                                 \
+    if (tail) MI_ATTN_FWD_T(DD, true, true, false, true); else MI_ATTN_FWD_T(DD, true, false, false, true);            \
+  } while (0)
+  if (seg_start) {  // (causal, no window, both arrays: mi_attn_fwd_seg refuses everything else)
+    if (D == 128) MI_ATTN_FWD_SEG(128); else MI_ATTN_FWD_SEG(64);
+  } else if (win) {  // (causal: mi_attn_fwd_win refuses everything else)
     if (D == 128) MI_ATTN_FWD_WIN(128); else MI_ATTN_FWD_WIN(64);
   } else if (D == 128) {
     if (causal) MI_ATTN_FWD(128, true); else MI_ATTN_FWD(128, false);
@@ -606,14 +668,15 @@ static int attn_fwd_launch(const char* fn, const void* q, const void* k, const v
 #undef MI_ATTN_FWD_T
 #undef MI_ATTN_FWD
 #undef MI_ATTN_FWD_WIN
-  MI_CHECK_LAUNCH(window ? "mi_attn_fwd_win launch" : "mi_attn_fwd launch");
+#undef MI_ATTN_FWD_SEG
+  MI_CHECK_LAUNCH(seg_start ? "mi_attn_fwd_seg launch" : window ? "mi_attn_fwd_win launch" : "mi_attn_fwd launch");
   return MI_OK;
 }
 
 extern "C" int mi_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G,
                            int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
                            void* stream) {
-  return attn_fwd_launch("mi_attn_fwd", q, k, v, o, lse, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, scale, causal, 0, stream);
+  return attn_fwd_launch("mi_attn_fwd", q, k, v, o, lse, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, scale, causal, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int mi_attn_fwd_win(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G,
@@ -621,7 +684,22 @@ extern "C" int mi_attn_fwd_win(const void* q, const void* k, const void* v, void
                                int window, void* stream) {
   MI_CHECK_ARG(window >= 1, "mi_attn_fwd_win: window %d must be at least 1 (the keys a query sees, itself included)", window);
   MI_CHECK_ARG(causal != 0, "mi_attn_fwd_win: the window is a band below the causal diagonal: causal must be set");
-  return attn_fwd_launch("mi_attn_fwd_win", q, k, v, o, lse, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, scale, causal, window, stream);
+  return attn_fwd_launch("mi_attn_fwd_win", q, k, v, o, lse, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, scale, causal, window, nullptr, nullptr, stream);
+}
+
+// (the arrays live on the device: their contents cannot be checked here without a host synchronisation, so the kernels clamp them)
+#define MI_CHECK_SEG(fn)                                                                                               \
+  do {                                                                                                                 \
+    MI_CHECK_ARG(seg_start && seg_end, fn ": null segment pointer");                                                   \
+    MI_CHECK_ARG(((uintptr_t)seg_start % 4) == 0 && ((uintptr_t)seg_end % 4) == 0, fn ": seg_start and seg_end must be 4-byte aligned"); \
+    MI_CHECK_ARG(causal != 0, fn ": documents are bands below the causal diagonal: causal must be set");                \
+  } while (0)
+
+extern "C" int mi_attn_fwd_seg(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G,
+                               int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
+                               const int32_t* seg_start, const int32_t* seg_end, void* stream) {
+  MI_CHECK_SEG("mi_attn_fwd_seg");
+  return attn_fwd_launch("mi_attn_fwd_seg", q, k, v, o, lse, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, scale, causal, 0, seg_start, seg_end, stream);
 }
 
 #ifdef MI_DIAG
@@ -641,11 +719,12 @@ extern "C" int mi_attn_fwd_diag(const void* q, const void* k, const void* v, voi
 }
 #endif  // MI_DIAG
 
-// One host path for mi_attn_bwd (window = 0) and mi_attn_bwd_win (window >= 1), as attn_fwd_launch.
+// One host path for mi_attn_bwd (window = 0), mi_attn_bwd_win (window >= 1) and mi_attn_bwd_seg (seg_start, seg_end set), as attn_fwd_launch.
 static int attn_bwd_launch(const char* fn, const void* q, const void* k, const void* v, const void* o, const void* dout,
                            const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D,
                            int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
-                           int64_t dv_ts, float scale, int causal, int window, void* stream) {
+                           int64_t dv_ts, float scale, int causal, int window, const int32_t* seg_start, const int32_t* seg_end,
+                           void* stream) {
   MI_CHECK_ARG(q && k && v && o && dout && lse && delta && dq && dk && dv, "%s: null pointer", fn);
   MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "%s: bad B/H/G (%d, %d, %d)", fn, B, H, G);
   MI_CHECK_ARG(D == 128 || D == 64, "%s: head_dim %d not supported (64, 128)", fn, D);
@@ -662,24 +741,31 @@ static int attn_bwd_launch(const char* fn, const void* q, const void* k, const v
   const bool win = window >= 1 && window < S;  // as in attn_fwd_launch
   const int nblk = (S + mi::ATT_QB - 1) / mi::ATT_QB;
   dim3 grid_q(nblk, H, B), grid_kv((unsigned)((int64_t)nblk * G * B)), block(256);
-#define MI_ATTN_BWD_T(DD, CC, TT, WW)                                                                                  \
+#define MI_ATTN_BWD_T(DD, CC, TT, WW, SS)                                                                              \
   do {                                                                                                                 \
-    hipLaunchKernelGGL((mi::attn_bwd_dq_kernel<DD, CC, TT, WW>), grid_q, block, 0, st, (const uint16_t*)q, (const uint16_t*)k, \
-                       (const uint16_t*)v, (const uint16_t*)o, (const uint16_t*)dout, lse, delta, (uint16_t*)dq, S, H,  \
-                       G, window, q_ts, k_ts, v_ts, o_ts, do_ts, dq_ts, c, scale);                                       \
-    hipLaunchKernelGGL((mi::attn_bwd_dkdv_kernel<DD, CC, TT, WW>), grid_kv, block, 0, st, (const uint16_t*)q,            \
+    hipLaunchKernelGGL((mi::attn_bwd_dq_kernel<DD, CC, TT, WW, SS>), grid_q, block, 0, st, (const uint16_t*)q,         \
+                       (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)o, (const uint16_t*)dout, lse, delta,   \
+                       (uint16_t*)dq, S, H, G, window, q_ts, k_ts, v_ts, o_ts, do_ts, dq_ts, c, scale, seg_start, seg_end); \
+    hipLaunchKernelGGL((mi::attn_bwd_dkdv_kernel<DD, CC, TT, WW, SS>), grid_kv, block, 0, st, (const uint16_t*)q,      \
                        (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)dout, lse, delta, (uint16_t*)dk,        \
-                       (uint16_t*)dv, S, H, G, B, q_ts, k_ts, v_ts, do_ts, dk_ts, dv_ts, c, scale, window);              \
+                       (uint16_t*)dv, S, H, G, B, q_ts, k_ts, v_ts, do_ts, dk_ts, dv_ts, c, scale, window, seg_start,   \
+                       seg_end);                                                                                        \
   } while (0)
 #define MI_ATTN_BWD(DD, CC)                                                                                            \
   do {                                                                                                                 \
-    if (tail) MI_ATTN_BWD_T(DD, CC, true, false); else MI_ATTN_BWD_T(DD, CC, false, false);                            \
+    if (tail) MI_ATTN_BWD_T(DD, CC, true, false, false); else MI_ATTN_BWD_T(DD, CC, false, false, false);              \
   } while (0)
 #define MI_ATTN_BWD_WIN(DD)                                                                                            \
   do {                                                                                                                 \
-    if (tail) MI_ATTN_BWD_T(DD, true, true, true); else MI_ATTN_BWD_T(DD, true, false, true);                          \
+    if (tail) MI_ATTN_BWD_T(DD, true, true, true, false); else MI_ATTN_BWD_T(DD, true, false, true, false);            \
   } while (0)
-  if (win) {  // (causal: mi_attn_bwd_win refuses everything else)
+#define MI_ATTN_BWD_SEG(DD)                                                                                            \
+  do {                                                                                                                 \
+    if (tail) MI_ATTN_BWD_T(DD, true, true, false, true); else MI_ATTN_BWD_T(DD, true, false, false, true);            \
+  } while (0)
+  if (seg_start) {  // (causal, no window, both arrays: mi_attn_bwd_seg refuses everything else)
+    if (D == 128) MI_ATTN_BWD_SEG(128); else MI_ATTN_BWD_SEG(64);
+  } else if (win) {  // (causal: mi_attn_bwd_win refuses everything else)
     if (D == 128) MI_ATTN_BWD_WIN(128); else MI_ATTN_BWD_WIN(64);
   } else if (D == 128) {
     if (causal) MI_ATTN_BWD(128, true); else MI_ATTN_BWD(128, false);
@@ -688,8 +774,9 @@ static int attn_bwd_launch(const char* fn, const void* q, const void* k, const v
   }
 #undef MI_ATTN_BWD
 #undef MI_ATTN_BWD_WIN
+#undef MI_ATTN_BWD_SEG
 #undef MI_ATTN_BWD_T
-  MI_CHECK_LAUNCH(window ? "mi_attn_bwd_win launch" : "mi_attn_bwd launch");
+  MI_CHECK_LAUNCH(seg_start ? "mi_attn_bwd_seg launch" : window ? "mi_attn_bwd_win launch" : "mi_attn_bwd launch");
   return MI_OK;
 }
 
@@ -698,7 +785,7 @@ extern "C" int mi_attn_bwd(const void* q, const void* k, const void* v, const vo
                            int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
                            int64_t dv_ts, float scale, int causal, void* stream) {
   return attn_bwd_launch("mi_attn_bwd", q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, do_ts,
-                         dq_ts, dk_ts, dv_ts, scale, causal, 0, stream);
+                         dq_ts, dk_ts, dv_ts, scale, causal, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int mi_attn_bwd_win(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
@@ -708,5 +795,16 @@ extern "C" int mi_attn_bwd_win(const void* q, const void* k, const void* v, cons
   MI_CHECK_ARG(window >= 1, "mi_attn_bwd_win: window %d must be at least 1 (the keys a query sees, itself included)", window);
   MI_CHECK_ARG(causal != 0, "mi_attn_bwd_win: the window is a band below the causal diagonal: causal must be set");
   return attn_bwd_launch("mi_attn_bwd_win", q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, do_ts,
-                         dq_ts, dk_ts, dv_ts, scale, causal, window, stream);
+                         dq_ts, dk_ts, dv_ts, scale, causal, window, nullptr, nullptr, stream);
 }
+
+extern "C" int mi_attn_bwd_seg(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                               float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
+                               int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
+                               int64_t dv_ts, float scale, int causal, const int32_t* seg_start, const int32_t* seg_end,
+                               void* stream) {
+  MI_CHECK_SEG("mi_attn_bwd_seg");
+  return attn_bwd_launch("mi_attn_bwd_seg", q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, do_ts,
+                         dq_ts, dk_ts, dv_ts, scale, causal, 0, seg_start, seg_end, stream);
+}
+#undef MI_CHECK_SEG

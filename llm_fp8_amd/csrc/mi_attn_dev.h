@@ -53,6 +53,11 @@ __device__ __forceinline__ bf8 acc_frag(const f16v& a, int s) {
 
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
+// Packed sequences (SEG in mi_attn.hip): token t's document as the kernels use it.  Whatever the arrays hold, the document starts
+// in [0, t] and ends in [t + 1, S]: a token always sees itself, and nothing derived from these values leaves the row.
+__device__ __forceinline__ int seg_lo(const int32_t* __restrict__ seg_start, int t) { return min(max(seg_start[t], 0), t); }
+__device__ __forceinline__ int seg_hi(const int32_t* __restrict__ seg_end, int t, int S) { return min(max(seg_end[t], t + 1), S); }
+
 // Make a prologue load complete HERE (a use the compiler cannot move): left alone, such loads sink towards their first use
 // inside the tile loop, and the s_waitcnt vmcnt placed there also waits -- the counter is in-order -- for the NEXT tile's
 // just-issued prefetch loads, every tile.

@@ -156,10 +156,24 @@ class TELlamaDecoderLayer(torch.nn.Module):
         if attention_mask is not None and not isinstance(attention_mask, torch.Tensor):
             raise TypeError("attention_mask must be a torch.Tensor")
         fp8 = hidden_states.is_cuda  # FP8 is unconditionally on in the reference layer (te_llama.py:76,79)
+        # packed sequences: transformers hands its FlashAttentionKwargs through LlamaModel.forward(**kwargs) to every layer; the
+        # documents of the row are cu_seq_lens_q (int32 or int64: ops.attn_segments reads either, and the SAME tensor goes to every
+        # layer, so the segment arrays are built once per model forward).  The rotary table keeps running through the row: RoPE
+        # scores depend on i - j only, so every document gets the scores of positions restarted at its first token.
+        cu = kwargs.get("cu_seq_lens_q", None)
+        if cu is not None:
+            cu_k = kwargs.get("cu_seq_lens_k", None)
+            # (q and k of this layer are projections of the same tokens; the values of the two tensors, which a trainer moves to
+            # the device one by one, cannot be compared without a host synchronisation, so only the shapes are)
+            if cu_k is not None and cu_k.shape != cu.shape:
+                raise NotImplementedError("cu_seq_lens_k must equal cu_seq_lens_q: packed sequences are implemented for self-attention only")
+            if hidden_states.shape[0] != 1:
+                raise ValueError(f"cu_seq_lens_q with a batch of {hidden_states.shape[0]}: a packed row is [1, T], as transformers' "
+                                 "flattening collator produces it")
         if self.route == "reference":
             with te.fp8_autocast(enabled=fp8, fp8_recipe=self.attn_recipe):
                 hidden_states = hidden_states + self.self_attention(hidden_states, attention_mask=attention_mask,
-                                                                    rotary_pos_emb=self.te_rope_emb)
+                                                                    rotary_pos_emb=self.te_rope_emb, cu_seqlens_q=cu)
             with te.fp8_autocast(enabled=fp8, fp8_recipe=self.mlp_recipe):
                 hidden_states = hidden_states + self.layernorm_mlp(hidden_states)
             return hidden_states
@@ -169,7 +183,7 @@ class TELlamaDecoderLayer(torch.nn.Module):
         # -- handed over on the tensor -- the next layer's input norm), saving that norm's own pass over the activations.
         with te.fp8_autocast(enabled=fp8, fp8_recipe=self.attn_recipe):
             attn_out, skip = self.self_attention(hidden_states, attention_mask=attention_mask, rotary_pos_emb=self.te_rope_emb,
-                                                 _with_skip=True, _rstd=_handed_rstd(hidden_states))
+                                                 _with_skip=True, _rstd=_handed_rstd(hidden_states), cu_seqlens_q=cu)
         eps_mlp = self.layernorm_mlp.eps
         hidden_states, rstd = residual_add_stats(skip, attn_out, eps_mlp)
         # `_defer_bias`: the fc2 bias (TE's default bias=True on LayerNormMLP, te_llama.py:58-63) joins the residual add below

@@ -12,7 +12,13 @@ kernels of csrc/mi_attn_short.hip for the same shapes at the lengths below 128 w
 Sliding-window causal attention (`window_size=(left, 0)`, TE's and flash-attn's argument; W = left + 1 keys per query, HF's
 `sliding_window`) runs on the band-limited instantiations of the same kernels (mi_attn_fwd_win / mi_attn_bwd_win: O(S * W) work)
 under the conditions of the full-causal route; every other windowed case -- S < 128 with a real band, CPU tensors, dropout,
-`LLM_FP8_AMD_NO_WINDOW_ATTN=1` -- takes `scaled_dot_product_attention` with a cached boolean band mask."""
+`LLM_FP8_AMD_NO_WINDOW_ATTN=1` -- takes `scaled_dot_product_attention` with a cached boolean band mask.
+
+Packed sequences (`cu_seqlens_q`, TE's argument; HF's `cu_seq_lens_q`): one row of tokens holds several documents and a token
+attends only inside its own.  The same kernels walk only the documents (mi_attn_fwd_seg / mi_attn_bwd_seg: O(sum len^2) work) under
+the conditions of the full-causal route; every other packed case -- T < 128, CPU tensors, dropout, a window as well,
+`LLM_FP8_AMD_NO_PACKED_ATTN=1` -- takes `scaled_dot_product_attention` with the boolean document mask.  RoPE needs nothing: its
+scores depend on i - j only, so positions that run through the row give every document the scores of restarted ones."""
 from __future__ import annotations
 
 import os
@@ -151,14 +157,14 @@ class _QKNormRoPESplitFn(torch.autograd.Function):
 
 
 class _FlashAttnFn(torch.autograd.Function):
-    """bshd attention core on mi_attn_fwd / mi_attn_bwd (`window` = W: mi_attn_fwd_win / mi_attn_bwd_win); saves q, k, v, o and
-    the log-sum-exp, never the scores."""
+    """bshd attention core on mi_attn_fwd / mi_attn_bwd (`window` = W: mi_attn_fwd_win / mi_attn_bwd_win; `segments` =
+    ops.attn_segments' pair: mi_attn_fwd_seg / mi_attn_bwd_seg); saves q, k, v, o and the log-sum-exp, never the scores."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal, window=None):
-        o, lse = ops.attn_fwd(q, k, v, scale, causal, window=window)
+    def forward(ctx, q, k, v, scale, causal, window=None, segments=None):
+        o, lse = ops.attn_fwd(q, k, v, scale, causal, window=window, segments=segments)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.scale, ctx.causal, ctx.window = scale, causal, window
+        ctx.scale, ctx.causal, ctx.window, ctx.segments = scale, causal, window, segments
         return o
 
     @staticmethod
@@ -168,8 +174,8 @@ class _FlashAttnFn(torch.autograd.Function):
         ok = (do.stride(3) == 1 and do.stride(2) == do.shape[3] and do.stride(0) == do.shape[1] * do.stride(1)
               and do.stride(1) % 8 == 0 and do.data_ptr() % 16 == 0)
         do = do if ok else do.clone(memory_format=torch.contiguous_format)  # (a misaligned contiguous view's .contiguous() is itself)
-        dq, dk, dv = ops.attn_bwd(do, q, k, v, o, lse, ctx.scale, ctx.causal, window=ctx.window)
-        return dq, dk, dv, None, None, None
+        dq, dk, dv = ops.attn_bwd(do, q, k, v, o, lse, ctx.scale, ctx.causal, window=ctx.window, segments=ctx.segments)
+        return dq, dk, dv, None, None, None, None
 
 
 _WindowAttnFn = _FlashAttnFn  # the same Function: the window is its one further non-tensor argument
@@ -241,8 +247,25 @@ def _band_mask(S: int, W: int, device) -> torch.Tensor:
     return hit
 
 
+_SEGMENTS = {}
+
+
+def _segments(cu_seqlens: torch.Tensor, T: int):
+    """ops.attn_segments(cu_seqlens, 1, T), built once per model forward and not once per layer: cached on the identity and the
+    version of the `cu_seqlens` tensor (an in-place write to it bumps the version)."""
+    key = (id(cu_seqlens), cu_seqlens._version, T)
+    hit = _SEGMENTS.get(key)
+    if hit is None or hit[0]() is not cu_seqlens:  # (the weak reference: an id can be reused by a later tensor)
+        if len(_SEGMENTS) > 16:
+            _SEGMENTS.clear()
+        hit = _SEGMENTS[key] = (weakref.ref(cu_seqlens), ops.attn_segments(cu_seqlens, 1, T))
+    return hit[1]
+
+
 class DotProductAttention(torch.nn.Module):
     """bf16 attention core.  q [b,s,h,d], k/v [b,s,g,d] (bshd) -> [b,s,h*d].
+    Packed sequences: `cu_seqlens_q` (int32 or int64 [n + 1], TE's cumulative document lengths) with a batch of 1, or with
+    qkv_format="thd" (q [t,h,d], k/v [t,g,d] -> [t,h*d]); `cu_seqlens_kv` is None or the same tensor (self-attention).
     `window_size` = (left, right) as in TE: None or left < 0 is the full mask; with a causal mask type right is 0 or -1 and
     (left, 0) lets a query see itself and the `left` keys before it (W = left + 1)."""
 
@@ -275,7 +298,44 @@ class DotProductAttention(torch.nn.Module):
                                            enable_gqa=(self.g != self.h))
         return o.transpose(1, 2)
 
-    def forward(self, q, k, v, attention_mask=None):
+    def _forward_packed(self, q, k, v, cu_seqlens, dropout: float):
+        """Causal attention inside the documents of one packed row (bshd with b = 1 in, bshd out): the HIP kernels where the
+        full-causal route would take them and no window is set, else SDPA with the document mask (also under
+        LLM_FP8_AMD_NO_PACKED_ATTN=1: the route the kernels are tested and timed against)."""
+        T = q.shape[1]
+        seg_start, seg_end = _segments(cu_seqlens, T)
+        W = self.window_size[0] + 1 if self.window_size is not None else T
+        if W >= T and os.environ.get("LLM_FP8_AMD_NO_PACKED_ATTN") != "1" and _flash_ok(q, k, v, True, dropout):
+            return _FlashAttnFn.apply(q, k, v, self.d ** -0.5, True, None, (seg_start, seg_end))
+        j = torch.arange(T, device=q.device)
+        mask = (seg_start[0, :, None] <= j[None, :]) & (j[None, :] <= j[:, None])
+        if W < T:
+            mask = mask & _band_mask(T, W, q.device)
+        o = F.scaled_dot_product_attention(*(t.transpose(1, 2) for t in (q, k, v)), attn_mask=mask, dropout_p=dropout,
+                                           enable_gqa=(self.g != self.h))
+        return o.transpose(1, 2)
+
+    def forward(self, q, k, v, attention_mask=None, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None):
+        if cu_seqlens_q is not None or cu_seqlens_kv is not None or self.qkv_format == "thd":
+            if cu_seqlens_q is None:
+                raise ValueError("packed sequences (qkv_format='thd' or cu_seqlens_kv) need cu_seqlens_q")
+            if cu_seqlens_kv is not None and cu_seqlens_kv is not cu_seqlens_q:
+                raise NotImplementedError("cu_seqlens_kv must be None or the tensor passed as cu_seqlens_q: packed sequences are "
+                                          "implemented for self-attention only")
+            if self.attn_mask_type not in ("causal", "padding_causal"):
+                raise NotImplementedError(f"cu_seqlens_q with attn_mask_type={self.attn_mask_type!r}: packed sequences are causal")
+            if self.qkv_format == "thd":
+                q, k, v = (t.unsqueeze(0) for t in (q, k, v))
+            elif self.qkv_format == "sbhd":
+                q, k, v = (t.transpose(0, 1) for t in (q, k, v))
+            if q.shape[0] != 1:
+                raise ValueError(f"cu_seqlens_q with a batch of {q.shape[0]}: a packed row is [1, T] (or qkv_format='thd')")
+            o = self._forward_packed(q, k, v, cu_seqlens_q, self.p if self.training else 0.0)
+            if self.qkv_format == "thd":
+                return o.reshape(o.shape[1], self.h * self.d)
+            if self.qkv_format == "sbhd":
+                o = o.transpose(0, 1)
+            return o.reshape(*o.shape[:2], self.h * self.d)
         if self.qkv_format == "sbhd":
             q, k, v = (t.transpose(0, 1) for t in (q, k, v))
         causal = self.attn_mask_type in ("causal", "padding_causal")
@@ -353,21 +413,23 @@ class MultiheadAttention(torch.nn.Module):
             self.k_norm = RMSNorm(self.d, eps=qk_norm_eps, params_dtype=params_dtype, device=device)
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                rotary_pos_emb=None, _with_skip: bool = False, _rstd=None, **_ignored):
-        """`_with_skip` (extension): returns (out, skip); `_rstd`: statistics hand-off, see LayerNormLinear.forward."""
+                rotary_pos_emb=None, _with_skip: bool = False, _rstd=None, cu_seqlens_q=None, **_ignored):
+        """`_with_skip` (extension): returns (out, skip); `_rstd`: statistics hand-off, see LayerNormLinear.forward.
+        `cu_seqlens_q`: packed sequences, see DotProductAttention (a batch of 1)."""
+        cu = cu_seqlens_q
         if _with_skip:
             if not self.input_layernorm:
-                return self._attend(self.qkv(hidden_states), attention_mask, rotary_pos_emb), hidden_states
+                return self._attend(self.qkv(hidden_states), attention_mask, rotary_pos_emb, cu_seqlens_q=cu), hidden_states
             # the rotary split's backward hands the projection its grad_output already in FP8 (module.DyHandoff): only
             # when the two are wired back to back right here
             handoff = DyHandoff() if (rotary_pos_emb is not None and hidden_states.is_cuda and torch.is_grad_enabled()
                                       and os.environ.get("LLM_FP8_AMD_NO_DY_HANDOFF") != "1") else None
             qkv, skip = self.layernorm_qkv(hidden_states, _with_skip=True, _rstd=_rstd, _dy_handoff=handoff)
-            return self._attend(qkv, attention_mask, rotary_pos_emb, handoff), skip
+            return self._attend(qkv, attention_mask, rotary_pos_emb, handoff, cu_seqlens_q=cu), skip
         qkv = self.layernorm_qkv(hidden_states) if self.input_layernorm else self.qkv(hidden_states)
-        return self._attend(qkv, attention_mask, rotary_pos_emb)
+        return self._attend(qkv, attention_mask, rotary_pos_emb, cu_seqlens_q=cu)
 
-    def _attend_qk_norm(self, qkv: torch.Tensor, attention_mask, rotary_pos_emb, handoff) -> torch.Tensor:
+    def _attend_qk_norm(self, qkv: torch.Tensor, attention_mask, rotary_pos_emb, handoff, cu_seqlens_q=None) -> torch.Tensor:
         """`_attend` with the per-head RMSNorm of q and k in front of RoPE.  Neither route has an FP8-emitting backward, so the
         q|k|v projection quantises its own grad_output: the hand-off is withdrawn on both."""
         if handoff is not None:
@@ -379,7 +441,7 @@ class MultiheadAttention(torch.nn.Module):
                 and os.environ.get("LLM_FP8_AMD_NO_QK_NORM_FUSION") != "1"):
             cos, sin = _cos_sin_tables(rotary_pos_emb, qkv.shape[1])
             q, k, v = _QKNormRoPESplitFn.apply(qkv, gq, gk, cos, sin, self.h, self.g, self.d, float(self.qk_norm_eps))
-            return self.proj(self.core_attention(q, k, v, attention_mask))
+            return self.proj(self.core_attention(q, k, v, attention_mask, cu_seqlens_q=cu_seqlens_q))
         # the torch route (and the CPU route): split, norm on the [.., h, d] views, rotate
         q, k, v = torch.split(qkv, self.split, dim=-1)
         a, b = qkv.shape[0], qkv.shape[1]
@@ -390,17 +452,17 @@ class MultiheadAttention(torch.nn.Module):
             fq, fk = rotary_pos_emb if isinstance(rotary_pos_emb, (tuple, list)) else (rotary_pos_emb, rotary_pos_emb)
             q = apply_rotary_pos_emb(q, fq, self.qkv_format)
             k = apply_rotary_pos_emb(k, fk, self.qkv_format)
-        return self.proj(self.core_attention(q, k, v, attention_mask))
+        return self.proj(self.core_attention(q, k, v, attention_mask, cu_seqlens_q=cu_seqlens_q))
 
-    def _attend(self, qkv: torch.Tensor, attention_mask, rotary_pos_emb, handoff=None) -> torch.Tensor:
+    def _attend(self, qkv: torch.Tensor, attention_mask, rotary_pos_emb, handoff=None, cu_seqlens_q=None) -> torch.Tensor:
         if self.qk_norm_type is not None:
-            return self._attend_qk_norm(qkv, attention_mask, rotary_pos_emb, handoff)
+            return self._attend_qk_norm(qkv, attention_mask, rotary_pos_emb, handoff, cu_seqlens_q)
         if (rotary_pos_emb is not None and not isinstance(rotary_pos_emb, (tuple, list)) and qkv.is_cuda
                 and qkv.dtype == torch.bfloat16 and self.qkv_format == "bshd" and self.d % 16 == 0
                 and rotary_pos_emb.shape[-1] == self.d):
             cos, sin = _cos_sin_tables(rotary_pos_emb, qkv.shape[1])
             q, k, v = _RoPESplitFn.apply(qkv, cos, sin, self.h, self.g, self.d, handoff)
-            return self.proj(self.core_attention(q, k, v, attention_mask))
+            return self.proj(self.core_attention(q, k, v, attention_mask, cu_seqlens_q=cu_seqlens_q))
         if handoff is not None:
             handoff.withdraw()  # not the fused rotary path: the projection quantises its own grad_output
         q, k, v = torch.split(qkv, self.split, dim=-1)
@@ -412,5 +474,5 @@ class MultiheadAttention(torch.nn.Module):
             fq, fk = rotary_pos_emb if isinstance(rotary_pos_emb, (tuple, list)) else (rotary_pos_emb, rotary_pos_emb)
             q = apply_rotary_pos_emb(q, fq, self.qkv_format)
             k = apply_rotary_pos_emb(k, fk, self.qkv_format)
-        ctx = self.core_attention(q, k, v, attention_mask)
+        ctx = self.core_attention(q, k, v, attention_mask, cu_seqlens_q=cu_seqlens_q)
         return self.proj(ctx)

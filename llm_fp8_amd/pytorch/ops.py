@@ -920,14 +920,44 @@ def attn_window_walk(S: int, window: int, block: int):
     return j0, min(2 * block + 2, -(-S // 64)) - j0, min(-(-S // 32) - 4 * block, (128 + wm1 + 31) // 32)
 
 
+def attn_segments(cu_seqlens: torch.Tensor, B: int, S: int):
+    """(seg_start, seg_end), int32 [B, S] on cu_seqlens' device, for `segments=` of attn_fwd / attn_bwd: for every token of the
+    B * S tokens that `cu_seqlens` ([0, l0, l0 + l1, ...], TE's and flash-attn's cumulative lengths) cuts into documents, the index
+    within its row of its document's first token and one past its last.  A document ends at its row's end at the latest, and the
+    tokens at or past cu_seqlens[-1] form one trailing document: a padded tail stays finite and sees only itself.  Built on the
+    device, without a host synchronisation."""
+    cu = cu_seqlens.reshape(-1).to(torch.int64)
+    t = torch.arange(B * S, device=cu.device)
+    # boundaries = the document starts, every row start, and B * S as the end of whatever comes last
+    cuts = torch.cat((cu.clamp(0, B * S), torch.arange(0, B * S + 1, S, device=cu.device))).sort().values
+    hi = torch.bucketize(t, cuts, right=True)  # first boundary above t; the one in front of it is at or below t
+    row0 = t - t % S
+    start, end = cuts[hi - 1] - row0, cuts[hi] - row0  # (hi is in range: B * S is a boundary above every token)
+    return start.to(torch.int32).view(B, S), end.to(torch.int32).view(B, S)
+
+
+def _segments_ok(segments, B: int, S: int, device):
+    seg_start, seg_end = segments
+    for t in (seg_start, seg_end):
+        assert t.dtype == torch.int32 and t.shape == (B, S) and t.is_contiguous() and t.device == device, \
+            "segments = (seg_start, seg_end): int32 [B, S], contiguous, on the operands' device"
+    return seg_start, seg_end
+
+
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True, out=None,
-             window: Optional[int] = None):
+             window: Optional[int] = None, segments=None):
     """Attention core.  q [B, S, H, D], k/v [B, S, G, D] bf16 (views with a token stride are fine) -> (o [B, S, H, D], lse [B, H, S]).
     `out` = optional preallocated (o, lse): o may be a view with its own token stride, lse is contiguous fp32.
     `window` = W (causal only): query i sees the W keys i - W < j <= i and `lse` is the band's; the kernels walk only the band
-    (attn_window_walk), and W >= S is the plain causal call, bit for bit.  None takes mi_attn_fwd."""
+    (attn_window_walk), and W >= S is the plain causal call, bit for bit.  None takes mi_attn_fwd.
+    `segments` = (seg_start, seg_end) of attn_segments (causal only, not with `window`): a row holds several documents, query i
+    sees the keys seg_start[i] <= j <= i, `lse` is the document's, and the kernels walk only the documents (mi_attn_fwd_seg)."""
+    if segments is not None and window is not None:
+        raise ValueError("segments together with window: packed sequences with a sliding window are not implemented")
     _dev(q, k, v)
     B, S, H, D = q.shape
+    if segments is not None:
+        segments = _segments_ok(segments, B, S, q.device)
     G = k.shape[2]
     for t in (q, k, v):
         _bshd_ok(t, D)
@@ -941,6 +971,12 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, ca
         assert o.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1),
             v.stride(1), o.stride(1), float(scale), int(causal))
+    if segments is not None:
+        # the plain causal flop figure: the true one is 4 D sum len^2 and needs the lengths on the host
+        _launch(_lib.require("mi_attn_fwd_seg", "packed-sequence attention"),
+                args + (segments[0].data_ptr(), segments[1].data_ptr(), _stream()), "mi_attn_fwd_seg", "attn_fwd_seg",
+                lambda: (f"{B}x{S}x{H}x{D}seg", 4.0 * B * H * S * S * D * 0.5, 2.0 * (q.numel() * 2 + k.numel() * 2)))
+        return o, lse
     if window is not None:
         _launch(_lib.require("mi_attn_fwd_win", "sliding-window attention"), args + (int(window), _stream()), "mi_attn_fwd_win",
                 "attn_fwd_win", lambda: (f"{B}x{S}x{H}x{D}w{window}", 4.0 * B * H * S * min(window, S / 2) * D,
@@ -952,11 +988,15 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, ca
 
 
 def attn_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor,
-             scale: float, causal: bool = True, out=None, window: Optional[int] = None):
+             scale: float, causal: bool = True, out=None, window: Optional[int] = None, segments=None):
     """Backward of attn_fwd -> (dq [B,S,H,D], dk, dv [B,S,G,D]).  `out` = optional preallocated (dq, dk, dv) views.
-    `window`: the value the forward was called with (None takes mi_attn_bwd)."""
+    `window`, `segments`: the values the forward was called with (None, None takes mi_attn_bwd)."""
+    if segments is not None and window is not None:
+        raise ValueError("segments together with window: packed sequences with a sliding window are not implemented")
     _dev(do, q, k, v, o, lse)
     B, S, H, D = q.shape
+    if segments is not None:
+        segments = _segments_ok(segments, B, S, q.device)
     G = k.shape[2]
     for t in (q, k, v, o, do):
         _bshd_ok(t, D)
@@ -975,6 +1015,12 @@ def attn_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), delta.data_ptr(),
             dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1), v.stride(1), o.stride(1),
             do.stride(1), dq.stride(1), dk.stride(1), dv.stride(1), float(scale), int(causal))
+    if segments is not None:
+        # (the plain causal flop figure, as in attn_fwd: the true one needs the lengths on the host)
+        _launch(_lib.require("mi_attn_bwd_seg", "packed-sequence attention"),
+                args + (segments[0].data_ptr(), segments[1].data_ptr(), _stream()), "mi_attn_bwd_seg", "attn_bwd_seg",
+                lambda: (f"{B}x{S}x{H}x{D}seg", 14.0 * B * H * S * S * D * 0.5, 2.0 * (3 * q.numel() + 4 * k.numel())))
+        return dq, dk, dv
     if window is not None:
         _launch(_lib.require("mi_attn_bwd_win", "sliding-window attention"), args + (int(window), _stream()), "mi_attn_bwd_win",
                 "attn_bwd_win", lambda: (f"{B}x{S}x{H}x{D}w{window}", 14.0 * B * H * S * min(window, S / 2) * D,

@@ -50,6 +50,7 @@ class TrainingConfig:
     skip_nonfinite_steps: bool = True     # ClippedAdamW drops a step whose gradient norm is Inf / NaN (resolve_skip_nonfinite)
     grad_accum_dtype: Optional[str] = None  # "bf16" | "fp32" (grad_accum.GradAccumulator); None: resolve_grad_accum_dtype
     sliding_window: Optional[int] = None  # every layer attends the last N keys (causal band; attention.DotProductAttention window_size)
+    packed_docs: int = 0                  # N > 0: the batch is one row of batch_size * max_seq_length tokens cut into N documents
 
 
 def create_model(cfg: TrainingConfig, device) -> torch.nn.Module:
@@ -330,7 +331,31 @@ def create_optimizer(model, cfg: TrainingConfig):
 def synthetic_batch(cfg: TrainingConfig, vocab_size: int, device, generator=None):
     """What DataCollatorForLanguageModeling(mlm=False) yields without padding (data.py:59-63): labels = input_ids."""
     ids = torch.randint(0, vocab_size, (cfg.batch_size, cfg.max_seq_length), device=device, generator=generator)
+    if cfg.packed_docs:
+        return pack_batch(ids, cfg.packed_docs, generator)
     return {"input_ids": ids, "attention_mask": torch.ones_like(ids), "labels": ids.clone()}
+
+
+def pack_batch(ids: torch.Tensor, n_docs: int, generator=None):
+    """Sample packing as transformers' DataCollatorWithFlattening yields it: the [B, S] tokens become one row [1, B * S] of
+    `n_docs` documents of seeded random lengths (each >= 1), with the cumulative lengths as `cu_seq_lens_q` / `cu_seq_lens_k`
+    (int32), `position_ids` restarted at every document and label -100 at every document's first token, so that no document
+    predicts across a boundary.  No attention mask: a token attends inside its own document.  Built without a host
+    synchronisation."""
+    T = ids.numel()
+    if not 1 <= n_docs <= T:
+        raise ValueError(f"packed_docs={n_docs}: between 1 and the {T} tokens of a batch")
+    dev = ids.device
+    # n_docs - 1 distinct cut points in 1 .. T - 1: every document keeps at least one token
+    cuts = torch.randperm(T - 1, device=dev, generator=generator)[:n_docs - 1].sort().values + 1
+    cu = torch.cat((cuts.new_zeros(1), cuts, cuts.new_full((1,), T))).to(torch.int32)
+    t = torch.arange(T, device=dev)
+    start = cu.long()[torch.bucketize(t, cu[1:].long(), right=True)]
+    row = ids.reshape(1, T)
+    labels = row.clone()
+    labels[0, cu[:-1].long()] = -100
+    return {"input_ids": row, "labels": labels, "position_ids": (t - start).unsqueeze(0), "cu_seq_lens_q": cu, "cu_seq_lens_k": cu,
+            "max_length_q": T, "max_length_k": T}
 
 
 def _set_first_microbatch(model, value):
@@ -442,6 +467,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
                          "$LLM_FP8_AMD_GRAD_ACCUM; autograd's adds into .grad) | fp32 main_grad sums, rounded to bf16 once")
     ap.add_argument("--sliding_window", type=int, default=None,
                     help="sliding-window causal attention in every layer: a query sees itself and the N - 1 keys before it")
+    ap.add_argument("--packed_docs", type=int, default=0,
+                    help="sample packing: flatten the batch to one row of batch_size * max_seq_length tokens cut into N documents of "
+                         "random lengths; every token attends inside its own document (0 = off)")
     ap.add_argument("--no_skip_nonfinite_steps", action="store_true",
                     help="let a step with an Inf / NaN gradient norm through (ClippedAdamW drops it on the device by default)")
     return ap
@@ -454,7 +482,7 @@ def config_from_args(a) -> TrainingConfig:
                          num_hidden_layers=a.num_hidden_layers, vocab_size=a.vocab_size, num_warmup_steps=a.num_warmup_steps,
                          gradient_accumulation_steps=a.gradient_accumulation_steps, output_dir=a.output_dir, load_dir=a.load_dir,
                          optimizer_state=a.optimizer_state, skip_nonfinite_steps=not a.no_skip_nonfinite_steps,
-                         grad_accum_dtype=a.grad_accum_dtype, sliding_window=a.sliding_window)
+                         grad_accum_dtype=a.grad_accum_dtype, sliding_window=a.sliding_window, packed_docs=a.packed_docs)
 
 
 def main(argv=None):
