@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from llm_fp8_amd.pytorch.attention import _SHORT_MIN_S
 from oracle import fp8_oracle as O
 from tests.util import bf16_bits
 
@@ -49,7 +50,10 @@ def _check_bwd(got, ref, name):
 # ------------------------------------------------------------------------------------------------ 1. float64
 @pytest.mark.parametrize("H,G", [(2, 2), (6, 2), (4, 1)])  # groups of 1, 3 and 4 query heads
 @pytest.mark.parametrize("D", [64, 128])
-@pytest.mark.parametrize("S", [16, 48, 64, 112])  # three idle key waves; a partial second slice; two full; four, the last partial
+# S -> 32-row slices (nsl): 16 -> 1 (three idle key waves), 32 -> 1 (one full slice), 48 -> 2 (a partial second slice), 64 -> 2 (two
+# full), 80 -> 3 (a partial third), 96 -> 3 (three full), 112 -> 4 (the last partial).  80 and 96 are the `nsl == 3` deal of the
+# (head, slice) items over the waves, the one case that does not rotate the slice by item / 4
+@pytest.mark.parametrize("S", [16, 32, 48, 64, 80, 96, 112])
 def test_short_vs_float64(ops, dev, S, D, H, G):
     B, scale = 2, D ** -0.5
     q, k, v, do = _rand(B, S, H, G, D, seed=S + D + H)
@@ -69,11 +73,12 @@ CANARY = 0x7FC1  # a bf16 quiet NaN: whatever reads it into a sum poisons the re
 
 
 @pytest.mark.parametrize("D", [64, 128])
-def test_strided_views_canaries_batches_and_reproducibility(ops, dev, D):
+@pytest.mark.parametrize("S", [48, 80])  # 80: a partial third slice and an idle fourth key wave
+def test_strided_views_canaries_batches_and_reproducibility(ops, dev, S, D):
     """q, k, v column slices of one fused [B, S, (H + 2G) D] buffer; o, dO, dq, dk, dv views with token strides of their own
     inside NaN-canary buffers; lse between NaN guards.  Bitwise the contiguous call, nothing else written, batch 0 independent
     of batch 1, and a second call gives the same bits (the dQ reduction has a fixed order)."""
-    B, S, H, G, scale = 2, 48, 6, 2, D ** -0.5
+    B, H, G, scale = 2, 6, 2, D ** -0.5
     q, k, v, do = (t.to(dev) for t in _rand(B, S, H, G, D, seed=D))
     fused = torch.cat([t.reshape(B, S, -1) for t in (q, k, v)], dim=-1).contiguous()
     fused0 = fused.clone()
@@ -118,13 +123,17 @@ def test_strided_views_canaries_batches_and_reproducibility(ops, dev, D):
 
 
 # ------------------------------------------------------------------------------------------------ 3. module route
-@pytest.mark.parametrize("S", [64, 112])
-def test_dot_product_attention_short_route_matches_sdpa(dev, monkeypatch, S):
+# every (S, D) the module sends to the short kernels, from the table itself: D = 128 with S in 64 .. 112, D = 64 with S in 80 .. 112
+ADMITTED = [(S, D) for D, lo in sorted(_SHORT_MIN_S.items()) for S in range(lo, 128, 16)]
+
+
+@pytest.mark.parametrize("S,D", ADMITTED)
+def test_dot_product_attention_short_route_matches_sdpa(dev, monkeypatch, S, D):
     """The construction and the bound of test_dot_product_attention_flash_path_matches_sdpa; the other side is the same module
     with the short route switched off."""
     from llm_fp8_amd.pytorch import attention as A
     from llm_fp8_amd.pytorch.profiler import KernelTimer
-    B, H, G, D = 2, 6, 2, 128
+    B, H, G = 2, 6, 2
     core = A.DotProductAttention(H, D, G, attention_dropout=0.0, attn_mask_type="causal", qkv_format="bshd")
     torch.manual_seed(3)
     q, k, v = (torch.randn(B, S, n, D, device=dev, dtype=torch.bfloat16, requires_grad=True) for n in (H, G, G))
@@ -145,6 +154,26 @@ def test_dot_product_attention_short_route_matches_sdpa(dev, monkeypatch, S):
     for a, b, name in zip(got, (o2.detach(), q.grad, k.grad, v.grad), ("o", "dq", "dk", "dv")):
         rel = ((a.float() - b.float()).norm() / b.float().norm()).item()
         assert rel < 1e-2, f"{name}: {rel:.4g}"
+
+
+@pytest.mark.parametrize("D", sorted(_SHORT_MIN_S))
+def test_below_the_table_the_module_stays_off_the_short_kernels(dev, monkeypatch, D):
+    """At the largest multiple of 16 below _SHORT_MIN_S[D] (a length the kernels take, test 1) the module keeps the SDPA route."""
+    from llm_fp8_amd.pytorch import attention as A
+    from llm_fp8_amd.pytorch.profiler import KernelTimer
+    monkeypatch.delenv("LLM_FP8_AMD_NO_SHORT_ATTN", raising=False)
+    B, S, H, G = 2, _SHORT_MIN_S[D] - 16, 6, 2
+    assert S >= 16 and S % 16 == 0
+    core = A.DotProductAttention(H, D, G, attention_dropout=0.0, attn_mask_type="causal", qkv_format="bshd")
+    torch.manual_seed(5)
+    q, k, v = (torch.randn(B, S, n, D, device=dev, dtype=torch.bfloat16, requires_grad=True) for n in (H, G, G))
+    assert not A._short_ok(q, k, v, True, 0.0) and not A._flash_ok(q, k, v, True, 0.0)
+    with KernelTimer().install() as timer:
+        o = core(q, k, v)
+        o.backward(torch.randn_like(o) / 4)
+    torch.cuda.synchronize()
+    assert not [n for n in timer.summarize() if n.startswith("attn")], sorted(timer.summarize())
+    assert all(torch.isfinite(t).all() for t in (o, q.grad, k.grad, v.grad))
 
 
 # ------------------------------------------------------------------------------------------------ 4. refusals

@@ -1,6 +1,6 @@
 """CPU: the sliding-window attention surface.  Header, library and binding agree on revision 9 and the two `_win` entry points;
 what they refuse is refused on the host, before a launch, under the entry point's name (fake pointers: nothing is dereferenced);
-DotProductAttention's `window_size` follows TE's (left, right) on the SDPA route against a float64 band softmax; the Qwen3 layers
+ops.attn_window_walk against counts read off the band mask; DotProductAttention's `window_size` follows TE's (left, right) on the SDPA route against a float64 band softmax; the Qwen3 layers
 and train.TrainingConfig carry the window where the config says so."""
 import os
 import re
@@ -76,6 +76,25 @@ def test_host_refusals(call, ptrs, who):
     refused(call(q_ts=516), "strides")
     refused(call(k_ts=1 << 23), "2 GiB")
     refused(call(H=65536, G=1), "grid")
+
+
+@pytest.mark.parametrize("S", [128, 256, 400, 1024, 1040])
+def test_attn_window_walk_against_the_band_mask(S):
+    """ops.attn_window_walk for every 128-row block against counts read off the boolean band mask itself."""
+    from llm_fp8_amd.pytorch import ops
+    i = np.arange(S)
+    windows = {1, 2, 17, 32, 33, 63, 64, 65, 70, 96, 100, 127, 128, 129, 192, 193, 300, 513, 1000, S - 129, S - 1}
+    for W in sorted(w for w in windows if 0 < w < S):  # (a window of S or more is the plain causal call)
+        mask = (i[None, :] <= i[:, None]) & (i[None, :] > i[:, None] - W)  # [query, key]
+        for block in range(-(-S // 128)):
+            rows = slice(128 * block, min(128 * block + 128, S))
+            keys = np.flatnonzero(mask[rows].any(0))          # keys some query row of the block sees
+            j0 = int(keys[0]) // 64                           # first 64-key tile with a visible key
+            diag = min(128 * block + 127, S - 1) // 64        # the diagonal tile, clamped to the row
+            queries = np.flatnonzero(mask[:, rows].any(1))    # queries that see some key of the block
+            slices = int(queries[-1]) // 32 - 4 * block + 1   # from the key block's first slice through the last one that sees it
+            assert int(queries[0]) // 32 == 4 * block
+            assert ops.attn_window_walk(S, W, block) == (j0, diag - j0 + 1, slices), (S, W, block)
 
 
 def _band_f64(q, k, v, W):
