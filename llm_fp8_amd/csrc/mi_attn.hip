@@ -18,24 +18,29 @@
 // the kernels with TAIL = false, which is the code without any of the guards.  Otherwise the grids are ceil(S / 128) blocks
 // and the TAIL = true instantiations guard the one partial block / tile / slice at the end (see attn_fwd_kernel).
 //
-// Sliding window (mi_attn_fwd_win / mi_attn_bwd_win, causal only): query i sees the `window` keys i - window < j <= i.  The WIN = true
-// instantiations walk only the band (see the WIN note below); WIN = false is the code without any of it.
+// Sliding window (mi_attn_fwd_win / mi_attn_bwd_win, causal only): query i sees the `window` keys i - window < j <= i.  The
+// Mask::window instantiations walk only the band (see the WIN note below); every other mask is the code without any of it.
 //
 // Packed sequences (mi_attn_fwd_seg / mi_attn_bwd_seg, causal only): a row holds several documents and query i sees the keys
-// seg_start[i] <= j <= i of its own.  The SEG = true instantiations walk only the documents (see the SEG note below): O(sum len^2).
+// seg_start[i] <= j <= i of its own.  The Mask::packed instantiations walk only the documents (see the SEG note below): O(sum len^2).
 #include "mi_attn_dev.h"
+#include "mi_attn_host.h"
 
 namespace mi {
 
 constexpr int ATT_QB = 128;  // query rows per workgroup (4 waves x 32)
 constexpr int ATT_KB = 64;   // keys per tile
 
+// What a query sees, the one mask parameter of the three kernels: every key; the keys up to its own; the `window` keys up to its
+// own; the keys of its document up to its own.  Each kernel derives CAUSAL (every mask but none), WIN and SEG from it.
+enum class Mask { none, causal, window, packed };
+
 // TAIL (all three kernels): S is a multiple of 16 but not of 128, so the last 128-row block (and the last 64-key tile, the
 // last 32-row slice) is partial.  Rows at or past S belong to the next batch / head or lie outside the tensor: their loads
 // are clamped to row S - 1 or replaced by zeros, their stores are predicated, and a wave whose 32 rows are all past S keeps
 // staging its share of every tile and meeting every barrier but skips the arithmetic.  TAIL = false is the code as it was.
 //
-// WIN (all three kernels, CAUSAL only): the causal mask gets a second, lower edge, key > query - window.  With wm1 = window - 1:
+// WIN (all three kernels, Mask::window): the causal mask gets a second, lower edge, key > query - window.  With wm1 = window - 1:
 //   fwd / dQ   the tile loop starts at the first tile that ANY row of the workgroup sees, j0 = max(0, first row - wm1) / 64 (the
 //              staging is shared, so the start is the workgroup's; the double-buffer parity stays that of j).  A wave whose 32 rows
 //              all have their band above a tile (key0 + 63 < q_first - wm1) stages and meets the barrier but does no arithmetic,
@@ -49,7 +54,7 @@ constexpr int ATT_KB = 64;   // keys per tile
 //   dK / dV    the sweep over query slices ends at the last slice from which any key of the workgroup is seen (query
 //              kbi * 128 + 127 + wm1, clamped to S); a wave skips the slices past its own band (q0 > key_first + 31 + wm1), and
 //              on the slices that cross the band edge p and dS are 0 where query > key + wm1.
-// SEG (all three kernels, CAUSAL only, never with WIN): the band's lower edge is per row, the first token of the row's document.
+// SEG (all three kernels, Mask::packed): the band's lower edge is per row, the first token of the row's document.
 // seg_start / seg_end [B, S] int32 hold, for token t, the first token of its document and one past its last; both are non-decreasing
 // along a row.  Every value read goes through seg_lo / seg_hi (mi_attn_dev.h): start in [0, t], end in [t + 1, S].  Arrays with
 // wrong contents give wrong numbers, never an access outside the row and never a row without a key (the loops' bounds below stay
@@ -66,7 +71,7 @@ constexpr int ATT_KB = 64;   // keys per tile
 //              the predicate seg_start[query] <= key, so the passes agree.
 // `window` sits in what was alignment padding of the argument block (fwd, dQ) or at its end (dK/dV), and only WIN reads it; the segment pointers follow
 // at the very end, and only SEG reads them.
-template <int D, bool CAUSAL, bool DIAG = false, bool TAIL = false, bool WIN = false, bool SEG = false>
+template <int D, Mask MASK, bool DIAG = false, bool TAIL = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                           const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
                                                           float* __restrict__ lse, int S, int H, int G, int window,
@@ -74,8 +79,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
                                                           unsigned long long* __restrict__ dbg = nullptr,
                                                           const int32_t* __restrict__ seg_start = nullptr,
                                                           const int32_t* __restrict__ seg_end = nullptr) {
-  static_assert(!WIN || CAUSAL, "the window is a band below the causal diagonal");
-  static_assert(!SEG || (CAUSAL && !WIN), "documents are bands below the causal diagonal, and not combined with a window");
+  constexpr bool CAUSAL = MASK != Mask::none, WIN = MASK == Mask::window, SEG = MASK == Mask::packed;
   constexpr int TILE = ATT_KB * D * 2;  // bytes of one K (or V) tile
   constexpr int KT = D / 16, DB = D / 32;
   __shared__ __attribute__((aligned(16))) char lds[4 * TILE];
@@ -293,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const uint16_t* __rest
 // dQ pass: same walk as the forward (128 query rows per workgroup, 64-key tiles).  S^T and dP^T are recomputed with the
 // query on the lane (LSE and delta are lane constants), dS^T feeds  dQ^T += K^T . dS^T  straight from the accumulators.
 // Also writes delta[b, h, q] = sum_d dO * O for the dK/dV pass.
-template <int D, bool CAUSAL, bool TAIL = false, bool WIN = false, bool SEG = false>
+template <int D, Mask MASK, bool TAIL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                              const uint16_t* __restrict__ v, const uint16_t* __restrict__ o,
                                                              const uint16_t* __restrict__ dout, const float* __restrict__ lse,
@@ -302,8 +306,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
                                                              int64_t o_ts, int64_t do_ts, int64_t dq_ts, float c, float scale,
                                                              const int32_t* __restrict__ seg_start = nullptr,
                                                              const int32_t* __restrict__ seg_end = nullptr) {
-  static_assert(!WIN || CAUSAL, "the window is a band below the causal diagonal");
-  static_assert(!SEG || (CAUSAL && !WIN), "documents are bands below the causal diagonal, and not combined with a window");
+  constexpr bool CAUSAL = MASK != Mask::none, WIN = MASK == Mask::window, SEG = MASK == Mask::packed;
   constexpr int TILE = ATT_KB * D * 2;
   constexpr int KT = D / 16, DB = D / 32;
   __shared__ __attribute__((aligned(16))) char lds[4 * TILE];
@@ -456,7 +459,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
 // B operands (key on the lane) and dK^T, dV^T of those keys in accumulators while the workgroup sweeps the group's query
 // heads x 32-row query slices (Q and dO slices staged once for all four waves; row reads for S and dP, transposed reads
 // for the dV^T and dK^T products).
-template <int D, bool CAUSAL, bool TAIL = false, bool WIN = false, bool SEG = false>
+template <int D, Mask MASK, bool TAIL = false>
 __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                                const uint16_t* __restrict__ v, const uint16_t* __restrict__ dout,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
@@ -465,8 +468,7 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
                                                                int64_t do_ts, int64_t dk_ts, int64_t dv_ts, float c, float scale,
                                                                int window = 0, const int32_t* __restrict__ seg_start = nullptr,
                                                                const int32_t* __restrict__ seg_end = nullptr) {
-  static_assert(!WIN || CAUSAL, "the window is a band below the causal diagonal");
-  static_assert(!SEG || (CAUSAL && !WIN), "documents are bands below the causal diagonal, and not combined with a window");
+  constexpr bool CAUSAL = MASK != Mask::none, WIN = MASK == Mask::window, SEG = MASK == Mask::packed;
   constexpr int SL = 32 * D * 2;  // bytes of one 32-row slice image
   constexpr int KT = D / 16, DB = D / 32;
   constexpr int BUF = 2 * SL + 256;  // Q slice, dO slice, lse[32], delta[32]
@@ -619,57 +621,110 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd_dkdv_kernel(co
   store_rows_from_accT<D, TAIL>(dva, 1.0f, slice, dv + ((int64_t)b * S + key_first) * dv_ts + (int64_t)g * D, dv_ts, lane, S - key_first);
 }
 
+// The instantiations of the three kernels, listed once: head_dim {64, 128} x the four masks x {full blocks, TAIL}.  attn_select
+// hands the one that (D, mask, tail) name to `launch`, a generic lambda, as an AttnVariant.
+template <int D_, Mask MASK_, bool TAIL_>
+struct AttnVariant {
+  static constexpr int D = D_;
+  static constexpr Mask MASK = MASK_;
+  static constexpr bool TAIL = TAIL_;
+};
+
+template <int D, Mask MASK, class F>
+void attn_select_tail(bool tail, F& launch) {
+  if (tail) launch(AttnVariant<D, MASK, true>{}); else launch(AttnVariant<D, MASK, false>{});
+}
+
+template <int D, class F>
+void attn_select_mask(Mask mask, bool tail, F& launch) {
+  switch (mask) {
+    case Mask::none: return attn_select_tail<D, Mask::none>(tail, launch);
+    case Mask::causal: return attn_select_tail<D, Mask::causal>(tail, launch);
+    case Mask::window: return attn_select_tail<D, Mask::window>(tail, launch);
+    case Mask::packed: return attn_select_tail<D, Mask::packed>(tail, launch);
+  }
+}
+
+template <class F>
+void attn_select(int D, Mask mask, bool tail, F launch) {
+  if (D == 128) attn_select_mask<128>(mask, tail, launch); else attn_select_mask<64>(mask, tail, launch);
+}
+
 }  // namespace mi
 
-// One host path for mi_attn_fwd (window = 0: no band), mi_attn_fwd_win (window >= 1) and mi_attn_fwd_seg (seg_start, seg_end set:
-// documents); `fn` names the entry point in every refusal.
+// The mask of a call: mi_attn_fwd / mi_attn_bwd pass window = 0 and no arrays, the _win entry points window >= 1, the _seg entry
+// points both arrays (and both have refused everything but causal).  A window that covers every causal key is the plain causal
+// mask: the kernels as before.
+static mi::Mask attn_mask(int S, int causal, int window, const int32_t* seg_start) {
+  if (seg_start) return mi::Mask::packed;
+  if (window >= 1 && window < S) return mi::Mask::window;
+  return causal ? mi::Mask::causal : mi::Mask::none;
+}
+
+// One host path for mi_attn_fwd, mi_attn_fwd_win and mi_attn_fwd_seg; `fn` names the entry point in every refusal.
 static int attn_fwd_launch(const char* fn, const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
                            int G, int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
                            int window, const int32_t* seg_start, const int32_t* seg_end, void* stream) {
-  MI_CHECK_ARG(q && k && v && o && lse, "%s: null pointer", fn);
-  MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "%s: bad B/H/G (%d, %d, %d)", fn, B, H, G);
-  MI_CHECK_ARG(D == 128 || D == 64, "%s: head_dim %d not supported (64, 128)", fn, D);
-  MI_CHECK_ARG(S >= 128 && S % 16 == 0, "%s: seq %d must be a multiple of 16 and at least 128", fn, S);
-  MI_CHECK_ARG(q_ts % 8 == 0 && k_ts % 8 == 0 && v_ts % 8 == 0 && o_ts % 8 == 0, "%s: token strides must be multiples of 8", fn);
-  MI_CHECK_ARG((int64_t)S * k_ts * 2 < (1LL << 31) && (int64_t)S * v_ts * 2 < (1LL << 31) && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0,
-               "%s: one batch of K / V must span < 2 GiB and be 16-byte aligned (32-bit buffer offsets of the LDS DMA)", fn);
-  MI_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)o % 16) == 0, "%s: q and o must be 16-byte aligned (16-byte row accesses)", fn);
-  MI_CHECK_ARG(H <= 65535 && B <= 65535, "%s: grid too large", fn);
+  if (const int rc = mi::attn_check_operands(fn, {{"q", q, q_ts, mi::ATT_ROWS}, {"k", k, k_ts, mi::ATT_KV}, {"v", v, v_ts, mi::ATT_KV},
+                                                  {"o", o, o_ts, mi::ATT_ROWS}, {"lse", lse, 0, mi::ATT_F32}},
+                                             B, S, H, G, D, mi::ATT_QB, INT_MAX, H))
+    return rc;
   const float c = scale * 1.4426950408889634f;
-  const bool tail = S % mi::ATT_QB != 0;  // a partial last block: the TAIL instantiations; full blocks launch the kernels as before
-  const bool win = window >= 1 && window < S;  // a window that covers every causal key is the plain causal mask: the kernels as before
   dim3 grid((S + mi::ATT_QB - 1) / mi::ATT_QB, H, B), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define MI_ATTN_FWD_T(DD, CC, TT, WW, SS)                                                                              \
-  hipLaunchKernelGGL((mi::attn_fwd_kernel<DD, CC, false, TT, WW, SS>), grid, block, 0, st, (const uint16_t*)q,         \
-                     (const uint16_t*)k, (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, window, q_ts, k_ts, v_ts, o_ts, c, \
-                     (unsigned long long*)nullptr, seg_start, seg_end)
-#define MI_ATTN_FWD(DD, CC)                                                                                            \
-  do {                                                                                                                 \
-    if (tail) MI_ATTN_FWD_T(DD, CC, true, false, false); else MI_ATTN_FWD_T(DD, CC, false, false, false);              \
-  } while (0)
-#define MI_ATTN_FWD_WIN(DD)                                                                                            \
-  do {                                                                                                                 \
-    if (tail) MI_ATTN_FWD_T(DD, true, true, true, false); else MI_ATTN_FWD_T(DD, true, false, true, false);            \
-  } while (0)
-#define MI_ATTN_FWD_SEG(DD)                                                                                            \
-  do {                                                                                                                 \
-    if (tail) MI_ATTN_FWD_T(DD, true, true, false, true); else MI_ATTN_FWD_T(DD, true, false, false, true);            \
-  } while (0)
-  if (seg_start) {  // (causal, no window, both arrays: mi_attn_fwd_seg refuses everything else)
-    if (D == 128) MI_ATTN_FWD_SEG(128); else MI_ATTN_FWD_SEG(64);
-  } else if (win) {  // (causal: mi_attn_fwd_win refuses everything else)
-    if (D == 128) MI_ATTN_FWD_WIN(128); else MI_ATTN_FWD_WIN(64);
-  } else if (D == 128) {
-    if (causal) MI_ATTN_FWD(128, true); else MI_ATTN_FWD(128, false);
-  } else {
-    if (causal) MI_ATTN_FWD(64, true); else MI_ATTN_FWD(64, false);
-  }
-#undef MI_ATTN_FWD_T
-#undef MI_ATTN_FWD
-#undef MI_ATTN_FWD_WIN
-#undef MI_ATTN_FWD_SEG
+  // (a partial last block: the TAIL instantiations; full blocks launch the kernels as before)
+  mi::attn_select(D, attn_mask(S, causal, window, seg_start), S % mi::ATT_QB != 0, [&](auto var) {
+    using V = decltype(var);
+    hipLaunchKernelGGL((mi::attn_fwd_kernel<V::D, V::MASK, false, V::TAIL>), grid, block, 0, st, (const uint16_t*)q,
+                       (const uint16_t*)k, (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, window, q_ts, k_ts, v_ts, o_ts, c,
+                       (unsigned long long*)nullptr, seg_start, seg_end);
+  });
   MI_CHECK_LAUNCH(seg_start ? "mi_attn_fwd_seg launch" : window ? "mi_attn_fwd_win launch" : "mi_attn_fwd launch");
+  return MI_OK;
+}
+
+// One host path for mi_attn_bwd, mi_attn_bwd_win and mi_attn_bwd_seg, as attn_fwd_launch.
+static int attn_bwd_launch(const char* fn, const void* q, const void* k, const void* v, const void* o, const void* dout,
+                           const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D,
+                           int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
+                           int64_t dv_ts, float scale, int causal, int window, const int32_t* seg_start, const int32_t* seg_end,
+                           void* stream) {
+  if (const int rc = mi::attn_check_operands(
+          fn, {{"q", q, q_ts, mi::ATT_ROWS}, {"k", k, k_ts, mi::ATT_KV}, {"v", v, v_ts, mi::ATT_KV}, {"o", o, o_ts, mi::ATT_ROWS},
+               {"dout", dout, do_ts, mi::ATT_ROWS}, {"lse", lse, 0, mi::ATT_F32}, {"delta", delta, 0, mi::ATT_PTR},
+               {"dq", dq, dq_ts, mi::ATT_ROWS}, {"dk", dk, dk_ts, mi::ATT_ROWS}, {"dv", dv, dv_ts, mi::ATT_ROWS}},
+          B, S, H, G, D, mi::ATT_QB, INT_MAX, H))
+    return rc;
+  const float c = scale * 1.4426950408889634f;
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = (S + mi::ATT_QB - 1) / mi::ATT_QB;
+  dim3 grid_q(nblk, H, B), grid_kv((unsigned)((int64_t)nblk * G * B)), block(256);
+  mi::attn_select(D, attn_mask(S, causal, window, seg_start), S % mi::ATT_QB != 0, [&](auto var) {
+    using V = decltype(var);
+    hipLaunchKernelGGL((mi::attn_bwd_dq_kernel<V::D, V::MASK, V::TAIL>), grid_q, block, 0, st, (const uint16_t*)q,
+                       (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)o, (const uint16_t*)dout, lse, delta,
+                       (uint16_t*)dq, S, H, G, window, q_ts, k_ts, v_ts, o_ts, do_ts, dq_ts, c, scale, seg_start, seg_end);
+    hipLaunchKernelGGL((mi::attn_bwd_dkdv_kernel<V::D, V::MASK, V::TAIL>), grid_kv, block, 0, st, (const uint16_t*)q,
+                       (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)dout, lse, delta, (uint16_t*)dk, (uint16_t*)dv,
+                       S, H, G, B, q_ts, k_ts, v_ts, do_ts, dk_ts, dv_ts, c, scale, window, seg_start, seg_end);
+  });
+  MI_CHECK_LAUNCH(seg_start ? "mi_attn_bwd_seg launch" : window ? "mi_attn_bwd_win launch" : "mi_attn_bwd launch");
+  return MI_OK;
+}
+
+// what only the _win entry points ask
+static int attn_check_window(const char* fn, int window, int causal) {
+  MI_CHECK_ARG(window >= 1, "%s: window %d must be at least 1 (the keys a query sees, itself included)", fn, window);
+  MI_CHECK_ARG(causal != 0, "%s: the window is a band below the causal diagonal: causal must be set", fn);
+  return MI_OK;
+}
+
+// what only the _seg entry points ask (the arrays live on the device: their contents cannot be checked here without a host
+// synchronisation, so the kernels clamp them)
+static int attn_check_segments(const char* fn, const int32_t* seg_start, const int32_t* seg_end, int causal) {
+  MI_CHECK_ARG(seg_start && seg_end, "%s: null segment pointer", fn);
+  MI_CHECK_ARG(((uintptr_t)seg_start % 4) == 0 && ((uintptr_t)seg_end % 4) == 0, "%s: seg_start and seg_end must be 4-byte aligned", fn);
+  MI_CHECK_ARG(causal != 0, "%s: documents are bands below the causal diagonal: causal must be set", fn);
   return MI_OK;
 }
 
@@ -682,23 +737,14 @@ extern "C" int mi_attn_fwd(const void* q, const void* k, const void* v, void* o,
 extern "C" int mi_attn_fwd_win(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G,
                                int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
                                int window, void* stream) {
-  MI_CHECK_ARG(window >= 1, "mi_attn_fwd_win: window %d must be at least 1 (the keys a query sees, itself included)", window);
-  MI_CHECK_ARG(causal != 0, "mi_attn_fwd_win: the window is a band below the causal diagonal: causal must be set");
+  if (const int rc = attn_check_window("mi_attn_fwd_win", window, causal)) return rc;
   return attn_fwd_launch("mi_attn_fwd_win", q, k, v, o, lse, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, scale, causal, window, nullptr, nullptr, stream);
 }
-
-// (the arrays live on the device: their contents cannot be checked here without a host synchronisation, so the kernels clamp them)
-#define MI_CHECK_SEG(fn)                                                                                               \
-  do {                                                                                                                 \
-    MI_CHECK_ARG(seg_start && seg_end, fn ": null segment pointer");                                                   \
-    MI_CHECK_ARG(((uintptr_t)seg_start % 4) == 0 && ((uintptr_t)seg_end % 4) == 0, fn ": seg_start and seg_end must be 4-byte aligned"); \
-    MI_CHECK_ARG(causal != 0, fn ": documents are bands below the causal diagonal: causal must be set");                \
-  } while (0)
 
 extern "C" int mi_attn_fwd_seg(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G,
                                int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
                                const int32_t* seg_start, const int32_t* seg_end, void* stream) {
-  MI_CHECK_SEG("mi_attn_fwd_seg");
+  if (const int rc = attn_check_segments("mi_attn_fwd_seg", seg_start, seg_end, causal)) return rc;
   return attn_fwd_launch("mi_attn_fwd_seg", q, k, v, o, lse, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, scale, causal, 0, seg_start, seg_end, stream);
 }
 
@@ -711,74 +757,13 @@ extern "C" int mi_attn_fwd_diag(const void* q, const void* k, const void* v, voi
   MI_CHECK_ARG(q && k && v && o && lse && dbg, "mi_attn_fwd_diag: null pointer");
   MI_CHECK_ARG(D == 128 && S % 128 == 0 && H % G == 0, "mi_attn_fwd_diag: unsupported shape");
   dim3 grid(S / mi::ATT_QB, H, B), block(256);
-  hipLaunchKernelGGL((mi::attn_fwd_kernel<128, true, true>), grid, block, 0, (hipStream_t)stream, (const uint16_t*)q,
+  hipLaunchKernelGGL((mi::attn_fwd_kernel<128, mi::Mask::causal, true>), grid, block, 0, (hipStream_t)stream, (const uint16_t*)q,
                      (const uint16_t*)k, (const uint16_t*)v, (uint16_t*)o, lse, S, H, G, 0, q_ts, k_ts, v_ts, o_ts,
                      scale * 1.4426950408889634f, dbg);
   MI_CHECK_LAUNCH("mi_attn_fwd_diag launch");
   return MI_OK;
 }
 #endif  // MI_DIAG
-
-// One host path for mi_attn_bwd (window = 0), mi_attn_bwd_win (window >= 1) and mi_attn_bwd_seg (seg_start, seg_end set), as attn_fwd_launch.
-static int attn_bwd_launch(const char* fn, const void* q, const void* k, const void* v, const void* o, const void* dout,
-                           const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D,
-                           int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
-                           int64_t dv_ts, float scale, int causal, int window, const int32_t* seg_start, const int32_t* seg_end,
-                           void* stream) {
-  MI_CHECK_ARG(q && k && v && o && dout && lse && delta && dq && dk && dv, "%s: null pointer", fn);
-  MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, "%s: bad B/H/G (%d, %d, %d)", fn, B, H, G);
-  MI_CHECK_ARG(D == 128 || D == 64, "%s: head_dim %d not supported (64, 128)", fn, D);
-  MI_CHECK_ARG(S >= 128 && S % 16 == 0, "%s: seq %d must be a multiple of 16 and at least 128", fn, S);
-  MI_CHECK_ARG((q_ts | k_ts | v_ts | o_ts | do_ts | dq_ts | dk_ts | dv_ts) % 8 == 0, "%s: token strides must be multiples of 8", fn);
-  MI_CHECK_ARG((int64_t)S * k_ts * 2 < (1LL << 31) && (int64_t)S * v_ts * 2 < (1LL << 31) && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0,
-               "%s: one batch of K / V must span < 2 GiB and be 16-byte aligned (32-bit buffer offsets of the LDS DMA)", fn);
-  MI_CHECK_ARG((((uintptr_t)q | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16) == 0,
-               "%s: q, o, dout, dq, dk and dv must be 16-byte aligned (16-byte row accesses)", fn);
-  MI_CHECK_ARG(H <= 65535 && B <= 65535, "%s: grid too large", fn);
-  const float c = scale * 1.4426950408889634f;
-  hipStream_t st = (hipStream_t)stream;
-  const bool tail = S % mi::ATT_QB != 0;  // a partial last block: the TAIL instantiations; full blocks launch the kernels as before
-  const bool win = window >= 1 && window < S;  // as in attn_fwd_launch
-  const int nblk = (S + mi::ATT_QB - 1) / mi::ATT_QB;
-  dim3 grid_q(nblk, H, B), grid_kv((unsigned)((int64_t)nblk * G * B)), block(256);
-#define MI_ATTN_BWD_T(DD, CC, TT, WW, SS)                                                                              \
-  do {                                                                                                                 \
-    hipLaunchKernelGGL((mi::attn_bwd_dq_kernel<DD, CC, TT, WW, SS>), grid_q, block, 0, st, (const uint16_t*)q,         \
-                       (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)o, (const uint16_t*)dout, lse, delta,   \
-                       (uint16_t*)dq, S, H, G, window, q_ts, k_ts, v_ts, o_ts, do_ts, dq_ts, c, scale, seg_start, seg_end); \
-    hipLaunchKernelGGL((mi::attn_bwd_dkdv_kernel<DD, CC, TT, WW, SS>), grid_kv, block, 0, st, (const uint16_t*)q,      \
-                       (const uint16_t*)k, (const uint16_t*)v, (const uint16_t*)dout, lse, delta, (uint16_t*)dk,        \
-                       (uint16_t*)dv, S, H, G, B, q_ts, k_ts, v_ts, do_ts, dk_ts, dv_ts, c, scale, window, seg_start,   \
-                       seg_end);                                                                                        \
-  } while (0)
-#define MI_ATTN_BWD(DD, CC)                                                                                            \
-  do {                                                                                                                 \
-    if (tail) MI_ATTN_BWD_T(DD, CC, true, false, false); else MI_ATTN_BWD_T(DD, CC, false, false, false);              \
-  } while (0)
-#define MI_ATTN_BWD_WIN(DD)                                                                                            \
-  do {                                                                                                                 \
-    if (tail) MI_ATTN_BWD_T(DD, true, true, true, false); else MI_ATTN_BWD_T(DD, true, false, true, false);            \
-  } while (0)
-#define MI_ATTN_BWD_SEG(DD)                                                                                            \
-  do {                                                                                                                 \
-    if (tail) MI_ATTN_BWD_T(DD, true, true, false, true); else MI_ATTN_BWD_T(DD, true, false, false, true);            \
-  } while (0)
-  if (seg_start) {  // (causal, no window, both arrays: mi_attn_bwd_seg refuses everything else)
-    if (D == 128) MI_ATTN_BWD_SEG(128); else MI_ATTN_BWD_SEG(64);
-  } else if (win) {  // (causal: mi_attn_bwd_win refuses everything else)
-    if (D == 128) MI_ATTN_BWD_WIN(128); else MI_ATTN_BWD_WIN(64);
-  } else if (D == 128) {
-    if (causal) MI_ATTN_BWD(128, true); else MI_ATTN_BWD(128, false);
-  } else {
-    if (causal) MI_ATTN_BWD(64, true); else MI_ATTN_BWD(64, false);
-  }
-#undef MI_ATTN_BWD
-#undef MI_ATTN_BWD_WIN
-#undef MI_ATTN_BWD_SEG
-#undef MI_ATTN_BWD_T
-  MI_CHECK_LAUNCH(seg_start ? "mi_attn_bwd_seg launch" : window ? "mi_attn_bwd_win launch" : "mi_attn_bwd launch");
-  return MI_OK;
-}
 
 extern "C" int mi_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                            float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
@@ -792,8 +777,7 @@ extern "C" int mi_attn_bwd_win(const void* q, const void* k, const void* v, cons
                                float* delta, void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts,
                                int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
                                int64_t dv_ts, float scale, int causal, int window, void* stream) {
-  MI_CHECK_ARG(window >= 1, "mi_attn_bwd_win: window %d must be at least 1 (the keys a query sees, itself included)", window);
-  MI_CHECK_ARG(causal != 0, "mi_attn_bwd_win: the window is a band below the causal diagonal: causal must be set");
+  if (const int rc = attn_check_window("mi_attn_bwd_win", window, causal)) return rc;
   return attn_bwd_launch("mi_attn_bwd_win", q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, do_ts,
                          dq_ts, dk_ts, dv_ts, scale, causal, window, nullptr, nullptr, stream);
 }
@@ -803,8 +787,7 @@ extern "C" int mi_attn_bwd_seg(const void* q, const void* k, const void* v, cons
                                int64_t k_ts, int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts,
                                int64_t dv_ts, float scale, int causal, const int32_t* seg_start, const int32_t* seg_end,
                                void* stream) {
-  MI_CHECK_SEG("mi_attn_bwd_seg");
+  if (const int rc = attn_check_segments("mi_attn_bwd_seg", seg_start, seg_end, causal)) return rc;
   return attn_bwd_launch("mi_attn_bwd_seg", q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, H, G, D, q_ts, k_ts, v_ts, o_ts, do_ts,
                          dq_ts, dk_ts, dv_ts, scale, causal, 0, seg_start, seg_end, stream);
 }
-#undef MI_CHECK_SEG

@@ -18,6 +18,7 @@
 //                     through LDS in wave order 0, 1, 2, 3 and the slice is stored as bf16 rows: no atomics, no sum across
 //                     workgroups, bitwise reproducible.
 #include "mi_attn_dev.h"
+#include "mi_attn_host.h"
 
 namespace mi {
 
@@ -335,24 +336,15 @@ __global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_short_bwd_kernel(
 
 }  // namespace mi
 
-// the refusals both entry points share (everything is refused here, on the host, before any launch)
-#define MI_ATTN_SHORT_CHECKS(name)                                                                                              \
-  MI_CHECK_ARG(B >= 1 && H >= 1 && G >= 1 && H % G == 0, name ": bad B/H/G (%d, %d, %d)", B, H, G);                             \
-  MI_CHECK_ARG(D == 128 || D == 64, name ": head_dim %d not supported (64, 128)", D);                                           \
-  MI_CHECK_ARG(S >= 16 && S <= 112 && S % 16 == 0, name ": seq %d must be a multiple of 16 from 16 to 112", S);                 \
-  MI_CHECK_ARG(causal != 0, name ": only the causal mask is implemented");                                                      \
-  MI_CHECK_ARG((int64_t)S * k_ts * 2 < (1LL << 31) && (int64_t)S * v_ts * 2 < (1LL << 31),                                      \
-               name ": one batch of K / V must span < 2 GiB (32-bit buffer offsets of the LDS DMA)");                           \
-  MI_CHECK_ARG(G <= 65535 && B <= 65535, name ": grid too large")
-
 extern "C" int mi_attn_short_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int G,
                                  int D, int64_t q_ts, int64_t k_ts, int64_t v_ts, int64_t o_ts, float scale, int causal,
                                  void* stream) {
-  MI_CHECK_ARG(q && k && v && o && lse, "mi_attn_short_fwd: null pointer");
-  MI_ATTN_SHORT_CHECKS("mi_attn_short_fwd");
-  MI_CHECK_ARG(q_ts % 8 == 0 && k_ts % 8 == 0 && v_ts % 8 == 0 && o_ts % 8 == 0, "mi_attn_short_fwd: token strides must be multiples of 8");
-  MI_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16) == 0 && ((uintptr_t)lse % 4) == 0,
-               "mi_attn_short_fwd: q, k, v and o must be 16-byte aligned (16-byte row accesses), lse 4-byte");
+  const char* fn = "mi_attn_short_fwd";
+  if (const int rc = mi::attn_check_operands(fn, {{"q", q, q_ts, mi::ATT_ROWS}, {"k", k, k_ts, mi::ATT_KV}, {"v", v, v_ts, mi::ATT_KV},
+                                                  {"o", o, o_ts, mi::ATT_ROWS}, {"lse", lse, 0, mi::ATT_F32}},
+                                             B, S, H, G, D, 16, 112, G))  // (the grid is G x B)
+    return rc;
+  MI_CHECK_ARG(causal != 0, "%s: only the causal mask is implemented", fn);
   const float c = scale * 1.4426950408889634f;
   dim3 grid(G, B), block(256);
   hipStream_t st = (hipStream_t)stream;
@@ -369,12 +361,14 @@ extern "C" int mi_attn_short_bwd(const void* q, const void* k, const void* v, co
                                  void* dq, void* dk, void* dv, int B, int S, int H, int G, int D, int64_t q_ts, int64_t k_ts,
                                  int64_t v_ts, int64_t o_ts, int64_t do_ts, int64_t dq_ts, int64_t dk_ts, int64_t dv_ts,
                                  float scale, int causal, void* stream) {
-  MI_CHECK_ARG(q && k && v && o && dout && lse && dq && dk && dv, "mi_attn_short_bwd: null pointer");
-  MI_ATTN_SHORT_CHECKS("mi_attn_short_bwd");
-  MI_CHECK_ARG((q_ts | k_ts | v_ts | o_ts | do_ts | dq_ts | dk_ts | dv_ts) % 8 == 0, "mi_attn_short_bwd: token strides must be multiples of 8");
-  MI_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16) == 0 &&
-                   ((uintptr_t)lse % 4) == 0,
-               "mi_attn_short_bwd: q, k, v, o, dout, dq, dk and dv must be 16-byte aligned (16-byte row accesses), lse 4-byte");
+  const char* fn = "mi_attn_short_bwd";
+  if (const int rc = mi::attn_check_operands(
+          fn, {{"q", q, q_ts, mi::ATT_ROWS}, {"k", k, k_ts, mi::ATT_KV}, {"v", v, v_ts, mi::ATT_KV}, {"o", o, o_ts, mi::ATT_ROWS},
+               {"dout", dout, do_ts, mi::ATT_ROWS}, {"lse", lse, 0, mi::ATT_F32}, {"dq", dq, dq_ts, mi::ATT_ROWS},
+               {"dk", dk, dk_ts, mi::ATT_ROWS}, {"dv", dv, dv_ts, mi::ATT_ROWS}},
+          B, S, H, G, D, 16, 112, G))  // (the grid is G x B)
+    return rc;
+  MI_CHECK_ARG(causal != 0, "%s: only the causal mask is implemented", fn);
   const float c = scale * 1.4426950408889634f;
   dim3 grid(G, B), block(256);
   hipStream_t st = (hipStream_t)stream;
@@ -387,4 +381,3 @@ extern "C" int mi_attn_short_bwd(const void* q, const void* k, const void* v, co
   MI_CHECK_LAUNCH("mi_attn_short_bwd launch");
   return MI_OK;
 }
-#undef MI_ATTN_SHORT_CHECKS

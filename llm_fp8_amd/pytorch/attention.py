@@ -18,7 +18,11 @@ Packed sequences (`cu_seqlens_q`, TE's argument; HF's `cu_seq_lens_q`): one row 
 attends only inside its own.  The same kernels walk only the documents (mi_attn_fwd_seg / mi_attn_bwd_seg: O(sum len^2) work) under
 the conditions of the full-causal route; every other packed case -- T < 128, CPU tensors, dropout, a window as well,
 `LLM_FP8_AMD_NO_PACKED_ATTN=1` -- takes `scaled_dot_product_attention` with the boolean document mask.  RoPE needs nothing: its
-scores depend on i - j only, so positions that run through the row give every document the scores of restarted ones."""
+scores depend on i - j only, so positions that run through the row give every document the scores of restarted ones.
+
+`DotProductAttention.forward` is the one place that decides: it brings q, k, v to bshd, reduces the request to (band W or None,
+documents or None, dropout), takes the kernels where `_flash_ok` / `_short_ok` admit the call, else one SDPA call whose mask
+`_sdpa_mask` builds from the band and / or the documents, and restores the caller's layout."""
 from __future__ import annotations
 
 import os
@@ -156,6 +160,19 @@ class _QKNormRoPESplitFn(torch.autograd.Function):
         return g.view(B, S, -1), dgq, dgk, None, None, None, None, None, None
 
 
+def _rows_ok(t: torch.Tensor, S: int, D: int) -> bool:
+    """What the launchers ask of a bshd operand of S tokens per batch: rows of D-wide heads behind one token stride, a multiple of
+    8, at a 16-byte aligned address."""
+    return (t.stride(3) == 1 and t.stride(2) == D and t.stride(0) == S * t.stride(1) and t.stride(1) % 8 == 0
+            and t.data_ptr() % 16 == 0)
+
+
+def _launcher_dout(do: torch.Tensor) -> torch.Tensor:
+    """dO as the backward launchers take it: itself where _rows_ok, else a copy (a misaligned contiguous view's .contiguous() is
+    itself, so the copy is a clone)."""
+    return do if _rows_ok(do, do.shape[1], do.shape[3]) else do.clone(memory_format=torch.contiguous_format)
+
+
 class _FlashAttnFn(torch.autograd.Function):
     """bshd attention core on mi_attn_fwd / mi_attn_bwd (`window` = W: mi_attn_fwd_win / mi_attn_bwd_win; `segments` =
     ops.attn_segments' pair: mi_attn_fwd_seg / mi_attn_bwd_seg); saves q, k, v, o and the log-sum-exp, never the scores."""
@@ -170,15 +187,8 @@ class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
-        # the launcher takes dO only as a bshd view with a token stride of a multiple of 8 at a 16-byte aligned address
-        ok = (do.stride(3) == 1 and do.stride(2) == do.shape[3] and do.stride(0) == do.shape[1] * do.stride(1)
-              and do.stride(1) % 8 == 0 and do.data_ptr() % 16 == 0)
-        do = do if ok else do.clone(memory_format=torch.contiguous_format)  # (a misaligned contiguous view's .contiguous() is itself)
-        dq, dk, dv = ops.attn_bwd(do, q, k, v, o, lse, ctx.scale, ctx.causal, window=ctx.window, segments=ctx.segments)
+        dq, dk, dv = ops.attn_bwd(_launcher_dout(do), q, k, v, o, lse, ctx.scale, ctx.causal, window=ctx.window, segments=ctx.segments)
         return dq, dk, dv, None, None, None, None
-
-
-_WindowAttnFn = _FlashAttnFn  # the same Function: the window is its one further non-tensor argument
 
 
 class _ShortAttnFn(torch.autograd.Function):
@@ -194,21 +204,23 @@ class _ShortAttnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
-        ok = (do.stride(3) == 1 and do.stride(2) == do.shape[3] and do.stride(0) == do.shape[1] * do.stride(1)
-              and do.stride(1) % 8 == 0 and do.data_ptr() % 16 == 0)  # the rule of _FlashAttnFn.backward
-        do = do if ok else do.clone(memory_format=torch.contiguous_format)
-        dq, dk, dv = ops.attn_short_bwd(do, q, k, v, o, lse, ctx.scale, True)
+        dq, dk, dv = ops.attn_short_bwd(_launcher_dout(do), q, k, v, o, lse, ctx.scale, True)
         return dq, dk, dv, None
 
 
-def _flash_ok(q, k, v, causal: bool, dropout: float) -> bool:
+def _kernels_ok(q, k, v, causal: bool, dropout: float) -> bool:
+    """What both kernel families ask of a call, the sequence length aside: bf16 on the device, causal, no dropout, head_dim 64 /
+    128, S % 16 == 0, whole GQA groups, and operands the launchers take (one batch of each below 2 GiB)."""
     if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and dropout == 0.0 and causal):
         return False
     B, S, H, D = q.shape
-    if D not in (64, 128) or S % 16 or S < 128 or H % k.shape[2]:
+    if D not in (64, 128) or S % 16 or H % k.shape[2]:
         return False
-    return all(t.stride(3) == 1 and t.stride(2) == D and t.stride(0) == S * t.stride(1) and t.stride(1) % 8 == 0
-               and S * t.stride(1) * 2 < 2 ** 31 and t.data_ptr() % 16 == 0 for t in (q, k, v))
+    return all(_rows_ok(t, S, D) and S * t.stride(1) * 2 < 2 ** 31 for t in (q, k, v))
+
+
+def _flash_ok(q, k, v, causal: bool, dropout: float) -> bool:
+    return _kernels_ok(q, k, v, causal, dropout) and q.shape[1] >= 128
 
 
 # The kernels take every S in 16 .. 112; the module sends them only the lengths at which forward + backward was measured faster
@@ -219,15 +231,8 @@ _SHORT_MIN_S = {128: 64, 64: 80}
 
 def _short_ok(q, k, v, causal: bool, dropout: float) -> bool:
     """_flash_ok's conditions at the lengths below one 128-row block: 16 <= S < 128, S % 16 == 0 (from _SHORT_MIN_S up)."""
-    if os.environ.get("LLM_FP8_AMD_NO_SHORT_ATTN") == "1":
-        return False
-    if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and dropout == 0.0 and causal):
-        return False
-    B, S, H, D = q.shape
-    if D not in (64, 128) or S % 16 or not _SHORT_MIN_S[D] <= S < 128 or H % k.shape[2]:
-        return False
-    return all(t.stride(3) == 1 and t.stride(2) == D and t.stride(0) == S * t.stride(1) and t.stride(1) % 8 == 0
-               and S * t.stride(1) * 2 < 2 ** 31 and t.data_ptr() % 16 == 0 for t in (q, k, v))
+    return (os.environ.get("LLM_FP8_AMD_NO_SHORT_ATTN") != "1" and _kernels_ok(q, k, v, causal, dropout)
+            and _SHORT_MIN_S[q.shape[3]] <= q.shape[1] < 128)
 
 
 _BAND_MASKS = {}
@@ -262,6 +267,17 @@ def _segments(cu_seqlens: torch.Tensor, T: int):
     return hit[1]
 
 
+def _sdpa_mask(S: int, W: Optional[int], segments, device) -> Optional[torch.Tensor]:
+    """[S, S] bool, True = attend, for the SDPA route: the causal band of W keys and / or the documents of `segments` (_segments'
+    pair for one packed row); None where there is neither."""
+    mask = None if W is None else _band_mask(S, W, device)
+    if segments is not None:
+        j = torch.arange(S, device=device)
+        docs = (segments[0][0, :, None] <= j[None, :]) & (j[None, :] <= j[:, None])
+        mask = docs if mask is None else docs & mask
+    return mask
+
+
 class DotProductAttention(torch.nn.Module):
     """bf16 attention core.  q [b,s,h,d], k/v [b,s,g,d] (bshd) -> [b,s,h*d].
     Packed sequences: `cu_seqlens_q` (int32 or int64 [n + 1], TE's cumulative document lengths) with a batch of 1, or with
@@ -287,77 +303,48 @@ class DotProductAttention(torch.nn.Module):
             window_size = (int(left), int(right)) if left >= 0 else None
         self.window_size = window_size  # None: the full mask
 
-    def _forward_window(self, q, k, v, W: int, dropout: float):
-        """Causal band of W keys (bshd in, bshd out): the HIP kernels where the full-causal route would take them, else SDPA with
-        the band mask (also under LLM_FP8_AMD_NO_WINDOW_ATTN=1: the route the kernels are tested and timed against)."""
-        causal = self.attn_mask_type in ("causal", "padding_causal")
-        if os.environ.get("LLM_FP8_AMD_NO_WINDOW_ATTN") != "1" and _flash_ok(q, k, v, causal, dropout):
-            return _WindowAttnFn.apply(q, k, v, self.d ** -0.5, True, W)
-        mask = _band_mask(q.shape[1], W, q.device)
-        o = F.scaled_dot_product_attention(*(t.transpose(1, 2) for t in (q, k, v)), attn_mask=mask, dropout_p=dropout,
-                                           enable_gqa=(self.g != self.h))
-        return o.transpose(1, 2)
-
-    def _forward_packed(self, q, k, v, cu_seqlens, dropout: float):
-        """Causal attention inside the documents of one packed row (bshd with b = 1 in, bshd out): the HIP kernels where the
-        full-causal route would take them and no window is set, else SDPA with the document mask (also under
-        LLM_FP8_AMD_NO_PACKED_ATTN=1: the route the kernels are tested and timed against)."""
-        T = q.shape[1]
-        seg_start, seg_end = _segments(cu_seqlens, T)
-        W = self.window_size[0] + 1 if self.window_size is not None else T
-        if W >= T and os.environ.get("LLM_FP8_AMD_NO_PACKED_ATTN") != "1" and _flash_ok(q, k, v, True, dropout):
-            return _FlashAttnFn.apply(q, k, v, self.d ** -0.5, True, None, (seg_start, seg_end))
-        j = torch.arange(T, device=q.device)
-        mask = (seg_start[0, :, None] <= j[None, :]) & (j[None, :] <= j[:, None])
-        if W < T:
-            mask = mask & _band_mask(T, W, q.device)
-        o = F.scaled_dot_product_attention(*(t.transpose(1, 2) for t in (q, k, v)), attn_mask=mask, dropout_p=dropout,
-                                           enable_gqa=(self.g != self.h))
-        return o.transpose(1, 2)
-
     def forward(self, q, k, v, attention_mask=None, cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None):
-        if cu_seqlens_q is not None or cu_seqlens_kv is not None or self.qkv_format == "thd":
+        causal = self.attn_mask_type in ("causal", "padding_causal")
+        packed = cu_seqlens_q is not None or cu_seqlens_kv is not None or self.qkv_format == "thd"
+        if packed:
             if cu_seqlens_q is None:
                 raise ValueError("packed sequences (qkv_format='thd' or cu_seqlens_kv) need cu_seqlens_q")
             if cu_seqlens_kv is not None and cu_seqlens_kv is not cu_seqlens_q:
                 raise NotImplementedError("cu_seqlens_kv must be None or the tensor passed as cu_seqlens_q: packed sequences are "
                                           "implemented for self-attention only")
-            if self.attn_mask_type not in ("causal", "padding_causal"):
+            if not causal:
                 raise NotImplementedError(f"cu_seqlens_q with attn_mask_type={self.attn_mask_type!r}: packed sequences are causal")
-            if self.qkv_format == "thd":
-                q, k, v = (t.unsqueeze(0) for t in (q, k, v))
-            elif self.qkv_format == "sbhd":
-                q, k, v = (t.transpose(0, 1) for t in (q, k, v))
-            if q.shape[0] != 1:
-                raise ValueError(f"cu_seqlens_q with a batch of {q.shape[0]}: a packed row is [1, T] (or qkv_format='thd')")
-            o = self._forward_packed(q, k, v, cu_seqlens_q, self.p if self.training else 0.0)
-            if self.qkv_format == "thd":
-                return o.reshape(o.shape[1], self.h * self.d)
-            if self.qkv_format == "sbhd":
-                o = o.transpose(0, 1)
-            return o.reshape(*o.shape[:2], self.h * self.d)
-        if self.qkv_format == "sbhd":
+        # the caller's layout -> bshd
+        if self.qkv_format == "thd":
+            q, k, v = (t.unsqueeze(0) for t in (q, k, v))
+        elif self.qkv_format == "sbhd":
             q, k, v = (t.transpose(0, 1) for t in (q, k, v))
-        causal = self.attn_mask_type in ("causal", "padding_causal")
-        # a window at least as long as the sequence is the plain causal mask: today's routes, bit for bit
-        if self.window_size is not None and self.window_size[0] + 1 < q.shape[1]:
-            o = self._forward_window(q, k, v, self.window_size[0] + 1, self.p if self.training else 0.0)
-            if self.qkv_format == "sbhd":
-                o = o.transpose(0, 1)
-            return o.reshape(*o.shape[:2], self.h * self.d)
-        flash = _flash_ok(q, k, v, causal, self.p if self.training else 0.0)
-        if flash or _short_ok(q, k, v, causal, self.p if self.training else 0.0):
-            o = _FlashAttnFn.apply(q, k, v, self.d ** -0.5, True) if flash else _ShortAttnFn.apply(q, k, v, self.d ** -0.5)
-            if self.qkv_format == "sbhd":
-                o = o.transpose(0, 1)
-            return o.reshape(*o.shape[:2], self.h * self.d)
-        q, k, v = (t.transpose(1, 2) for t in (q, k, v))  # [b, h, s, d]
-        mask = None
-        if not causal and attention_mask is not None:
-            mask = ~attention_mask if attention_mask.dtype == torch.bool else attention_mask  # TE: True = masked out
-        o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=self.p if self.training else 0.0,
-                                           is_causal=causal, enable_gqa=(self.g != self.h))
-        o = o.transpose(1, 2)  # [b, s, h, d]
+        if packed and q.shape[0] != 1:
+            raise ValueError(f"cu_seqlens_q with a batch of {q.shape[0]}: a packed row is [1, T] (or qkv_format='thd')")
+        # the request: a band of W keys (a window at least as long as the sequence is the plain causal mask: None), the documents
+        # of a packed row, dropout
+        S = q.shape[1]
+        W = self.window_size[0] + 1 if self.window_size is not None and self.window_size[0] + 1 < S else None
+        segments = _segments(cu_seqlens_q, S) if packed else None
+        dropout = self.p if self.training else 0.0
+        # the route.  The kernels of mi_attn.hip take a band or the documents, not both, where _flash_ok takes the call; the switch
+        # of a mask selects the SDPA route that its kernels are tested and timed against.  mi_attn_short.hip has the plain causal mask.
+        switch = "LLM_FP8_AMD_NO_PACKED_ATTN" if packed else "LLM_FP8_AMD_NO_WINDOW_ATTN"
+        plain, both = W is None and not packed, W is not None and packed
+        if not both and (plain or os.environ.get(switch) != "1") and _flash_ok(q, k, v, causal, dropout):
+            o = _FlashAttnFn.apply(q, k, v, self.d ** -0.5, True, W, segments)
+        elif plain and _short_ok(q, k, v, causal, dropout):
+            o = _ShortAttnFn.apply(q, k, v, self.d ** -0.5)
+        else:
+            mask = _sdpa_mask(S, W, segments, q.device)
+            is_causal = causal and mask is None  # (a band or document mask holds the diagonal itself)
+            if mask is None and not causal and attention_mask is not None:
+                mask = ~attention_mask if attention_mask.dtype == torch.bool else attention_mask  # TE: True = masked out
+            o = F.scaled_dot_product_attention(*(t.transpose(1, 2) for t in (q, k, v)), attn_mask=mask, dropout_p=dropout,
+                                               is_causal=is_causal, enable_gqa=(self.g != self.h)).transpose(1, 2)
+        # bshd -> the caller's layout
+        if self.qkv_format == "thd":
+            return o.reshape(o.shape[1], self.h * self.d)
         if self.qkv_format == "sbhd":
             o = o.transpose(0, 1)
         return o.reshape(*o.shape[:2], self.h * self.d)

@@ -908,8 +908,9 @@ def blockfp8_dswiglu_quantize(h: torch.Tensor, dact: torch.Tensor, fmt: int = E4
 
 
 def _bshd_ok(t: torch.Tensor, D: int):
-    assert t.dtype == torch.bfloat16 and t.dim() == 4 and t.shape[3] == D and t.stride(3) == 1 and t.stride(2) == D
-    assert t.stride(0) == t.shape[1] * t.stride(1), "batch and sequence must collapse to one token stride"
+    st = t.stride()  # (one call: this runs for every operand of every attention launch)
+    assert t.dtype == torch.bfloat16 and len(st) == 4 and t.shape[3] == D and st[3] == 1 and st[2] == D
+    assert st[0] == t.shape[1] * st[1], "batch and sequence must collapse to one token stride"
 
 
 def attn_window_walk(S: int, window: int, block: int):
@@ -944,6 +945,94 @@ def _segments_ok(segments, B: int, S: int, device):
     return seg_start, seg_end
 
 
+# The attention routes by mask kind: the profiler kinds forward and backward (the entry point is "mi_" + kind), what _lib.require
+# says needs them, (span-tag suffix, keys a query meets in the work figure), and the products of one (query, key) pair in the
+# backward (7: S, dP, dQ | S, dP, dV, dK; short 5: S, dP, dV, dK, dQ; the forward has 2).  "packed" carries the plain causal
+# figure: the true one is 4 D sum len^2 and needs the lengths on the host.
+_ATTN_ROUTES = {
+    "full": ("attn_fwd", "attn_bwd", "attention", lambda S, causal, window: ("", S * (0.5 if causal else 1.0)), 7),
+    "window": ("attn_fwd_win", "attn_bwd_win", "sliding-window attention",
+               lambda S, causal, window: (f"w{window}", min(window, S / 2)), 7),
+    "packed": ("attn_fwd_seg", "attn_bwd_seg", "packed-sequence attention", lambda S, causal, window: ("seg", S * 0.5), 7),
+    "short": ("attn_short_fwd", "attn_short_bwd", "short-sequence attention", lambda S, causal, window: ("", S * 0.5), 5),
+}
+
+
+def _attn_mask_kind(window, segments) -> str:
+    if segments is not None and window is not None:
+        raise ValueError("segments together with window: packed sequences with a sliding window are not implemented")
+    return "packed" if segments is not None else "window" if window is not None else "full"
+
+
+def _attn_layout_ok(mask: str, D: int, rows) -> None:
+    for t in rows:
+        if mask != "short" or t.numel():  # (an empty operand has no layout to check: the short launchers refuse S = 0 by name)
+            _bshd_ok(t, D)
+
+
+def _attn_operands(mask: str, rows, stats, window, segments):
+    """The checks every attention wrapper makes of the operands it is given: `rows` = the bshd tensors (q, k, v, ...), `stats` = lse
+    where it is an input.  -> B, S, H, G, D, the launcher arguments of the mask itself."""
+    _dev(*rows, *stats)
+    B, S, H, D = rows[0].shape
+    if mask == "packed":
+        extra = tuple(t.data_ptr() for t in _segments_ok(segments, B, S, rows[0].device))
+    else:
+        extra = (int(window),) if mask == "window" else ()
+    _attn_layout_ok(mask, D, rows)
+    return B, S, H, rows[1].shape[2], D, extra
+
+
+def _attn_launch(mask: str, bwd: bool, args, q, k, causal, window) -> None:
+    route = _ATTN_ROUTES[mask]
+    kind = route[bwd]
+
+    def span():
+        B, S, H, D = q.shape
+        suffix, keys = route[3](S, causal, window)
+        return (f"{B}x{S}x{H}x{D}{suffix}", 2.0 * (route[4] if bwd else 2) * B * H * S * keys * D,
+                2.0 * (3 * q.numel() + 4 * k.numel() if bwd else q.numel() * 2 + k.numel() * 2))
+    _launch(_lib.require("mi_" + kind, route[2]), args, "mi_" + kind, kind, span)
+
+
+def _attn_fwd(mask: str, q, k, v, scale, causal, out, window=None, segments=None):
+    B, S, H, G, D, extra = _attn_operands(mask, (q, k, v), (), window, segments)
+    if out is None:
+        o = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
+        lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    else:
+        o, lse = out
+        _dev(o, lse)
+        _attn_layout_ok(mask, D, (o,))
+        assert o.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1),
+            v.stride(1), o.stride(1), float(scale), int(causal), *extra, _stream())
+    _attn_launch(mask, False, args, q, k, causal, window)
+    return o, lse
+
+
+def _attn_bwd(mask: str, do, q, k, v, o, lse, scale, causal, out, window=None, segments=None):
+    B, S, H, G, D, extra = _attn_operands(mask, (q, k, v, o, do), (lse,), window, segments)
+    assert o.shape == do.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
+    if out is None:
+        dq = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
+        dk = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
+        dv = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
+    else:
+        dq, dk, dv = out
+        _dev(dq, dk, dv)
+        _attn_layout_ok(mask, D, out)
+        assert dq.shape == q.shape and dk.shape == dv.shape == k.shape
+    # (the long kernels' dK/dV pass reads delta = rowsum(dO * O) from a workspace that their dQ pass writes; short keeps it in LDS)
+    delta = None if mask == "short" else torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(),
+            *(() if delta is None else (delta.data_ptr(),)), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S, H, G, D, q.stride(1),
+            k.stride(1), v.stride(1), o.stride(1), do.stride(1), dq.stride(1), dk.stride(1), dv.stride(1), float(scale), int(causal),
+            *extra, _stream())
+    _attn_launch(mask, True, args, q, k, causal, window)
+    return dq, dk, dv
+
+
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True, out=None,
              window: Optional[int] = None, segments=None):
     """Attention core.  q [B, S, H, D], k/v [B, S, G, D] bf16 (views with a token stride are fine) -> (o [B, S, H, D], lse [B, H, S]).
@@ -952,135 +1041,23 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, ca
     (attn_window_walk), and W >= S is the plain causal call, bit for bit.  None takes mi_attn_fwd.
     `segments` = (seg_start, seg_end) of attn_segments (causal only, not with `window`): a row holds several documents, query i
     sees the keys seg_start[i] <= j <= i, `lse` is the document's, and the kernels walk only the documents (mi_attn_fwd_seg)."""
-    if segments is not None and window is not None:
-        raise ValueError("segments together with window: packed sequences with a sliding window are not implemented")
-    _dev(q, k, v)
-    B, S, H, D = q.shape
-    if segments is not None:
-        segments = _segments_ok(segments, B, S, q.device)
-    G = k.shape[2]
-    for t in (q, k, v):
-        _bshd_ok(t, D)
-    if out is None:
-        o = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
-        lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-    else:
-        o, lse = out
-        _dev(o, lse)
-        _bshd_ok(o, D)
-        assert o.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
-    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1),
-            v.stride(1), o.stride(1), float(scale), int(causal))
-    if segments is not None:
-        # the plain causal flop figure: the true one is 4 D sum len^2 and needs the lengths on the host
-        _launch(_lib.require("mi_attn_fwd_seg", "packed-sequence attention"),
-                args + (segments[0].data_ptr(), segments[1].data_ptr(), _stream()), "mi_attn_fwd_seg", "attn_fwd_seg",
-                lambda: (f"{B}x{S}x{H}x{D}seg", 4.0 * B * H * S * S * D * 0.5, 2.0 * (q.numel() * 2 + k.numel() * 2)))
-        return o, lse
-    if window is not None:
-        _launch(_lib.require("mi_attn_fwd_win", "sliding-window attention"), args + (int(window), _stream()), "mi_attn_fwd_win",
-                "attn_fwd_win", lambda: (f"{B}x{S}x{H}x{D}w{window}", 4.0 * B * H * S * min(window, S / 2) * D,
-                                         2.0 * (q.numel() * 2 + k.numel() * 2)))
-        return o, lse
-    _launch(_lib.load().mi_attn_fwd, args + (_stream(),), "mi_attn_fwd", "attn_fwd",
-            lambda: (f"{B}x{S}x{H}x{D}", 4.0 * B * H * S * S * D * (0.5 if causal else 1.0), 2.0 * (q.numel() * 2 + k.numel() * 2)))
-    return o, lse
+    return _attn_fwd(_attn_mask_kind(window, segments), q, k, v, scale, causal, out, window, segments)
 
 
 def attn_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor,
              scale: float, causal: bool = True, out=None, window: Optional[int] = None, segments=None):
     """Backward of attn_fwd -> (dq [B,S,H,D], dk, dv [B,S,G,D]).  `out` = optional preallocated (dq, dk, dv) views.
     `window`, `segments`: the values the forward was called with (None, None takes mi_attn_bwd)."""
-    if segments is not None and window is not None:
-        raise ValueError("segments together with window: packed sequences with a sliding window are not implemented")
-    _dev(do, q, k, v, o, lse)
-    B, S, H, D = q.shape
-    if segments is not None:
-        segments = _segments_ok(segments, B, S, q.device)
-    G = k.shape[2]
-    for t in (q, k, v, o, do):
-        _bshd_ok(t, D)
-    assert o.shape == do.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
-    if out is None:
-        dq = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
-        dk = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
-        dv = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
-    else:
-        dq, dk, dv = out
-        _dev(dq, dk, dv)
-        for t in out:
-            _bshd_ok(t, D)
-        assert dq.shape == q.shape and dk.shape == dv.shape == k.shape
-    delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-            dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1), v.stride(1), o.stride(1),
-            do.stride(1), dq.stride(1), dk.stride(1), dv.stride(1), float(scale), int(causal))
-    if segments is not None:
-        # (the plain causal flop figure, as in attn_fwd: the true one needs the lengths on the host)
-        _launch(_lib.require("mi_attn_bwd_seg", "packed-sequence attention"),
-                args + (segments[0].data_ptr(), segments[1].data_ptr(), _stream()), "mi_attn_bwd_seg", "attn_bwd_seg",
-                lambda: (f"{B}x{S}x{H}x{D}seg", 14.0 * B * H * S * S * D * 0.5, 2.0 * (3 * q.numel() + 4 * k.numel())))
-        return dq, dk, dv
-    if window is not None:
-        _launch(_lib.require("mi_attn_bwd_win", "sliding-window attention"), args + (int(window), _stream()), "mi_attn_bwd_win",
-                "attn_bwd_win", lambda: (f"{B}x{S}x{H}x{D}w{window}", 14.0 * B * H * S * min(window, S / 2) * D,
-                                         2.0 * (3 * q.numel() + 4 * k.numel())))
-        return dq, dk, dv
-    _launch(_lib.load().mi_attn_bwd, args + (_stream(),), "mi_attn_bwd", "attn_bwd",   # 7 products: S, dP, dQ | S, dP, dV, dK
-            lambda: (f"{B}x{S}x{H}x{D}", 14.0 * B * H * S * S * D * (0.5 if causal else 1.0), 2.0 * (3 * q.numel() + 4 * k.numel())))
-    return dq, dk, dv
-
-
-def _bshd_ok_short(t: torch.Tensor, D: int):
-    if t.numel():  # (an empty operand has no layout to check: the launcher refuses S = 0 by name)
-        _bshd_ok(t, D)
+    return _attn_bwd(_attn_mask_kind(window, segments), do, q, k, v, o, lse, scale, causal, out, window, segments)
 
 
 def attn_short_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True, out=None):
     """attn_fwd at 16 <= S <= 112 (S % 16 == 0, causal only): one launch, one workgroup per (batch, kv head).  Same operands,
     returns and `out` as attn_fwd."""
-    _dev(q, k, v)
-    B, S, H, D = q.shape
-    G = k.shape[2]
-    for t in (q, k, v):
-        _bshd_ok_short(t, D)
-    if out is None:
-        o = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
-        lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-    else:
-        o, lse = out
-        _dev(o, lse)
-        _bshd_ok_short(o, D)
-        assert o.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
-    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1),
-            v.stride(1), o.stride(1), float(scale), int(causal), _stream())
-    _launch(_lib.require("mi_attn_short_fwd", "short-sequence attention"), args, "mi_attn_short_fwd", "attn_short_fwd",
-            lambda: (f"{B}x{S}x{H}x{D}", 2.0 * B * H * S * S * D, 2.0 * (q.numel() * 2 + k.numel() * 2)))
-    return o, lse
+    return _attn_fwd("short", q, k, v, scale, causal, out)
 
 
 def attn_short_bwd(do: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor,
                    scale: float, causal: bool = True, out=None):
     """Backward of attn_short_fwd -> (dq, dk, dv), one launch and no workspace.  Same operands and `out` as attn_bwd."""
-    _dev(do, q, k, v, o, lse)
-    B, S, H, D = q.shape
-    G = k.shape[2]
-    for t in (q, k, v, o, do):
-        _bshd_ok_short(t, D)
-    assert o.shape == do.shape == q.shape and lse.shape == (B, H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
-    if out is None:
-        dq = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
-        dk = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
-        dv = torch.empty((B, S, G, D), dtype=torch.bfloat16, device=q.device)
-    else:
-        dq, dk, dv = out
-        _dev(dq, dk, dv)
-        for t in out:
-            _bshd_ok_short(t, D)
-        assert dq.shape == q.shape and dk.shape == dv.shape == k.shape
-    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-            dv.data_ptr(), B, S, H, G, D, q.stride(1), k.stride(1), v.stride(1), o.stride(1), do.stride(1), dq.stride(1),
-            dk.stride(1), dv.stride(1), float(scale), int(causal), _stream())
-    _launch(_lib.require("mi_attn_short_bwd", "short-sequence attention"), args, "mi_attn_short_bwd", "attn_short_bwd",
-            lambda: (f"{B}x{S}x{H}x{D}", 5.0 * B * H * S * S * D, 2.0 * (3 * q.numel() + 4 * k.numel())))  # 5 products: S, dP, dV, dK, dQ
-    return dq, dk, dv
+    return _attn_bwd("short", do, q, k, v, o, lse, scale, causal, out)

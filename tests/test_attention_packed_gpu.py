@@ -333,3 +333,74 @@ def test_train_step_on_a_packed_batch(dev, monkeypatch):
     # the bound of the model tests between two routes of one mask: attention outputs rounded to bf16 (2^-8) twice
     assert abs(loss_hip - loss_sdpa) <= 2 ** -7 * abs(loss_hip), (loss_hip, loss_sdpa)
     assert abs(loss_plain - loss_hip) > abs(loss_sdpa - loss_hip), (loss_plain, loss_hip, loss_sdpa)
+
+
+SHORT, LONG, WIN, SEG = ({f"attn{m}_fwd{s}", f"attn{m}_bwd{s}"} for m, s in (("_short", ""), ("", ""), ("", "_win"), ("", "_seg")))
+SWITCHES = ("LLM_FP8_AMD_NO_SHORT_ATTN", "LLM_FP8_AMD_NO_WINDOW_ATTN", "LLM_FP8_AMD_NO_PACKED_ATTN")
+# (S or T, module arguments, cu_seqlens or None, the switch that is set or None, the attn_* kinds launched at head_dim 128, at 64).
+# 144 is the smallest length with a partial last block, 128 the smallest with full blocks only, 80 the smallest the short route takes
+# at both head dims, 64 splits them (attention._SHORT_MIN_S), 48 is below both.
+ROUTES = {
+    "causal-48": (48, {}, None, None, set(), set()),
+    "causal-64": (64, {}, None, None, SHORT, set()),
+    "causal-80": (80, {}, None, None, SHORT, SHORT),
+    "causal-112": (112, {}, None, None, SHORT, SHORT),
+    "causal-128": (128, {}, None, None, LONG, LONG),
+    "causal-144": (144, {}, None, None, LONG, LONG),
+    "causal-80-no-short": (80, {}, None, SWITCHES[0], set(), set()),
+    "window32-80": (80, dict(window_size=(31, 0)), None, None, set(), set()),  # a real band below 128: SDPA, not the short kernels
+    "window32-128": (128, dict(window_size=(31, 0)), None, None, WIN, WIN),
+    "window32-144": (144, dict(window_size=(31, 0)), None, None, WIN, WIN),
+    "window144-144": (144, dict(window_size=(143, 0)), None, None, LONG, LONG),  # a window of S or more is the plain causal call
+    "window80-80": (80, dict(window_size=(79, 0)), None, None, SHORT, SHORT),
+    "window32-144-no-window": (144, dict(window_size=(31, 0)), None, SWITCHES[1], set(), set()),
+    "packed-144": (144, {}, [0, 48, 144], None, SEG, SEG),
+    "packed-80": (80, {}, [0, 32, 80], None, set(), set()),  # not the short kernels
+    "packed-window32-144": (144, dict(window_size=(31, 0)), [0, 48, 144], None, set(), set()),
+    "packed-window144-144": (144, dict(window_size=(143, 0)), [0, 48, 144], None, SEG, SEG),
+    "packed-144-no-packed": (144, {}, [0, 48, 144], SWITCHES[2], set(), set()),
+    "packed-144-thd": (144, dict(qkv_format="thd"), [0, 48, 144], None, SEG, SEG),
+    "packed-144-sbhd": (144, dict(qkv_format="sbhd"), [0, 48, 144], None, SEG, SEG),
+    "no-mask-144": (144, dict(attn_mask_type="no_mask"), None, None, set(), set()),
+}
+
+
+@pytest.mark.parametrize("D", [128, 64])
+@pytest.mark.parametrize("case", list(ROUTES))
+def test_dot_product_attention_route_table(dev, monkeypatch, case, D):
+    """Which kernels DotProductAttention launches, forward plus backward, for every kind of request at the lengths where the route
+    changes: exactly the attn_* kinds of ROUTES.  The result against the same module with every switch set on float32 copies of the
+    inputs (the SDPA route: no attn_* kind), by the criteria of the route tests above."""
+    from llm_fp8_amd.pytorch import attention as A
+    from llm_fp8_amd.pytorch.profiler import KernelTimer
+    S, kw, cu, switch, kinds128, kinds64 = ROUTES[case]
+    H, G = 2, 1
+    fmt = kw.get("qkv_format", "bshd")
+    core = A.DotProductAttention(H, D, G, attention_dropout=0.0, **{"attn_mask_type": "causal", "qkv_format": "bshd", **kw})
+    q, k, v, do = _inputs(dev, 1, S, H, G, D, seed=S + D, fused=True)
+    # bshd <-> the module's layout (thd: the one row; sbhd: the two leading axes swapped)
+    to_fmt = {"bshd": lambda t: t, "thd": lambda t: t[0], "sbhd": lambda t: t.transpose(0, 1)}[fmt]
+    to_bshd = {"bshd": lambda t: t, "thd": lambda t: t.unsqueeze(0), "sbhd": lambda t: t.transpose(0, 1)}[fmt]
+    packed = {} if cu is None else dict(cu_seqlens_q=torch.tensor(cu, dtype=torch.int32, device=dev))
+
+    def run(dtype):
+        ts = [t.to(dtype).detach().clone().requires_grad_() for t in (q, k, v)]  # bshd leaves; the module gets views of them
+        with KernelTimer().install() as timer:
+            out = core(*(to_fmt(t) for t in ts), **packed)
+            assert out.shape == to_fmt(do).shape[:-2] + (H * D,)
+            out.backward(to_fmt(do).flatten(-2).to(out.dtype))
+        torch.cuda.synchronize()
+        launched = {n for n in timer.summarize() if n.startswith("attn")}
+        return launched, [to_bshd(out.detach().unflatten(-1, (H, D))), None] + [t.grad for t in ts]
+
+    for name in SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    if switch is not None:
+        monkeypatch.setenv(switch, "1")
+    launched, got = run(torch.bfloat16)
+    assert launched == (kinds128 if D == 128 else kinds64), (case, D, sorted(launched))
+    for name in SWITCHES:
+        monkeypatch.setenv(name, "1")
+    launched, ref = run(torch.float32)
+    assert not launched, sorted(launched)
+    _check(got, [t if t is None else t.double().cpu().numpy() for t in ref], v, f"{case}, D {D}")
