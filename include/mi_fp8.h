@@ -79,9 +79,11 @@ extern "C" {
  *   9  mi_attn_fwd_win, mi_attn_bwd_win (sliding-window causal attention: band-limited forward, dQ and dK/dV kernels)
  *  10  mi_attn_fwd_seg, mi_attn_bwd_seg (packed-sequence causal attention: several documents in a row, each token attends
  *      inside its own; the same three kernels walk only the documents)
+ *  11  mi_act_cast, mi_dact_cast, mi_amax_act, mi_amax_dact (tanh-GELU and GeGLU fused with the FP8 cast of fc2's input and of
+ *      fc1's grad_output, and their current-scaling amax passes)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 10
+#define MI_ABI_REVISION 11
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -388,6 +390,30 @@ int mi_swiglu_cast_bias(const void* h_bf16, const void* bias_bf16, void* y_fp8, 
                         int64_t rows, int64_t F, int fmt, void* stream);
 int mi_dswiglu_cast_bias(const void* h_bf16, const void* bias_bf16, const void* dact_bf16, void* y_fp8, void* yT_fp8,
                          const float* scale, float* amax, float* colsum, int64_t rows, int64_t F, int fmt, void* stream);
+
+/*
+ * GELU and GeGLU fused with the FP8 cast (revision 11)  [TE LayerNormMLP activation="gelu" (its default) and "geglu"].  The two
+ * calls above with the activation as an argument and the fc1 bias nullable:
+ *   act = MI_ACT_GELU   h: bf16 [rows, F].   fwd: v = gelu(h);         bwd: v = dact * gelu'(h)                       [rows, F]
+ *   act = MI_ACT_GEGLU  h: bf16 [rows, 2F] (gate | up).
+ *                       fwd: v = gelu(g) * u [rows, F];   bwd: v = [dact * gelu'(g) * u | dact * gelu(g)]            [rows, 2F]
+ * gelu is the tanh form, evaluated in fp32 as x * s with s = sigmoid(2u), u = 0.7978845608 (x + 0.044715 x^3), and
+ * gelu'(x) = s + x * s(1 - s) * 2u', u' = 0.7978845608 (1 + 0.134145 x^2); s(1 - s) underflows to exactly 0, so a finite h of any
+ * magnitude gives a finite result.  `bias` (nullable, bf16 [F] / [2F], 16-byte aligned) is added to h in fp32 first: h is then the
+ * fc1 GEMM's output WITHOUT its bias.  y = sat_cast(v * *scale), yT its transpose, *amax = max(*amax, max|v|); colsum (nullable)
+ * fp32 [ceil(rows/128), cols of v] as for mi_dswiglu_cast.  rows, F multiples of 8, `dact` bf16 [rows, F]; any other `act` is
+ * MI_ERR_ARG.  mi_amax_act / mi_amax_dact are the amax passes of the two (see "Current scaling" below): max|v| into `partial`.
+ */
+#define MI_ACT_GELU 1
+#define MI_ACT_GEGLU 2
+int mi_act_cast(const void* h_bf16, const void* bias_bf16, void* y_fp8, void* yT_fp8, const float* scale, float* amax,
+                int64_t rows, int64_t F, int act, int fmt, void* stream);
+int mi_dact_cast(const void* h_bf16, const void* bias_bf16, const void* dact_bf16, void* y_fp8, void* yT_fp8, const float* scale,
+                 float* amax, float* colsum, int64_t rows, int64_t F, int act, int fmt, void* stream);
+int mi_amax_act(const void* h_bf16, const void* bias_bf16, float* partial, int n_partial, int64_t rows, int64_t F, int act,
+                void* stream);
+int mi_amax_dact(const void* h_bf16, const void* bias_bf16, const void* dact_bf16, float* partial, int n_partial, int64_t rows,
+                 int64_t F, int act, void* stream);
 
 /*
  * K9  RMSNorm fused with the FP8 cast of the following GEMM's input  [TE LayerNormLinear / LayerNormMLP with

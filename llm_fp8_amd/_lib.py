@@ -13,7 +13,7 @@ LAB_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "bin", "libmi_fp8_l
 MI_FMT_E4M3 = 0
 MI_FMT_E5M2 = 1
 ABI_VERSION = 5
-ABI_REVISION = 10  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
+ABI_REVISION = 11  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
 # revision 5 adds no symbol: from it on every mi_adamw_* entry point reads a non-finite *grad_scale as "skip the step" (optim.py)
 
 _c_i64 = ctypes.c_int64
@@ -127,6 +127,11 @@ REVISION_SIGNATURES = {
     # revision 10: packed-sequence causal attention (the same argument lists + `seg_start, seg_end` before the stream)
     "mi_attn_fwd_seg": [_p] * 5 + [_c_int] * 5 + [_c_i64] * 4 + [ctypes.c_float, _c_int, _p, _p, _p],
     "mi_attn_bwd_seg": [_p] * 10 + [_c_int] * 5 + [_c_i64] * 8 + [ctypes.c_float, _c_int, _p, _p, _p],
+    # revision 11: GELU / GeGLU fused with the FP8 cast (the SwiGLU argument lists with a nullable bias and `act` behind F)
+    "mi_act_cast": [_p, _p, _p, _p, _p, _p, _c_i64, _c_i64, _c_int, _c_int, _p],
+    "mi_dact_cast": [_p, _p, _p, _p, _p, _p, _p, _p, _c_i64, _c_i64, _c_int, _c_int, _p],
+    "mi_amax_act": [_p, _p, _p, _c_int, _c_i64, _c_i64, _c_int, _p],
+    "mi_amax_dact": [_p, _p, _p, _p, _c_int, _c_i64, _c_i64, _c_int, _p],
 }
 SIGNATURES.update(REVISION_SIGNATURES)
 # entry points only the lab build exports (#ifdef MI_DIAG in include/mi_fp8.h)

@@ -190,6 +190,76 @@ __device__ __forceinline__ void swiglu_value2(u32 wg, u32 wu, u32 wd, bool has_b
   }
 }
 
+// ---- tanh-GELU (mi_act_cast / mi_dact_cast and their amax passes): gelu(x) = x * s, s = sigmoid(2u), u = k (x + 0.044715 x^3),
+// k = sqrt(2/pi); gelu'(x) = s + x * s(1 - s) * 2u', u' = k (1 + 0.134145 x^2).  One v_exp_f32 and one v_rcp_f32 per element:
+// with t = exp(-|2u|) in [0, 1] and r = 1 / (1 + t) in [1/2, 1], sigmoid(|2u|) = r, sigmoid(-|2u|) = t r and s(1 - s) = t r r -- a
+// product of bounded factors that underflows to exactly 0, never inf * 0.  The polynomial is evaluated at x clamped to +-16: from
+// |x| = 12 on t is exactly 0 (2u > 142), so s is exactly 0 or 1 and the derivative term exactly 0 either way, and x^2, x^3 of a
+// huge finite x cannot overflow into 0 * inf.  gelu itself multiplies the unclamped x.
+struct gelu_parts {
+  float s, p, xc;  // sigmoid(2u), s (1 - s), the clamped x
+};
+__device__ __forceinline__ gelu_parts gelu_eval(float x) {
+  gelu_parts o;
+  o.xc = __builtin_amdgcn_fmed3f(x, -16.0f, 16.0f);
+  const float x2 = o.xc * o.xc;
+  const float u2 = (2.0f * 0.7978845608f) * (o.xc + 0.044715f * (x2 * o.xc));  // 2u
+  const float t = __builtin_amdgcn_exp2f(-1.4426950409f * fabsf(u2));
+  const float r = __builtin_amdgcn_rcpf(1.0f + t);
+  const float tr = t * r;
+  o.s = u2 >= 0.0f ? r : tr;
+  o.p = tr * r;
+  return o;
+}
+__device__ __forceinline__ float gelu_fwd(float x) { return x * gelu_eval(x).s; }
+__device__ __forceinline__ float gelu_grad(const gelu_parts& e) {
+  return e.s + e.xc * e.p * ((2.0f * 0.7978845608f) * (1.0f + 0.134145f * (e.xc * e.xc)));
+}
+
+// mi_act_cast / mi_dact_cast, act = gelu (ungated: one input column per output column).  MODE 0: v = gelu(x); MODE 1: v = d * gelu'(x),
+// for the two bf16 halves of the packed words wx (h) and wd (dact); `has_bias` (wave-uniform): bx[0..1] is added to x first, in fp32.
+template <int MODE>
+__device__ __forceinline__ void gelu_value2(u32 wx, u32 wd, bool has_bias, const float* bx, float* v) {
+  float x2[2] = {__uint_as_float(wx << 16), __uint_as_float(wx & 0xFFFF0000u)};
+  const float d2[2] = {__uint_as_float(wd << 16), __uint_as_float(wd & 0xFFFF0000u)};
+  if (has_bias) {
+    x2[0] += bx[0];
+    x2[1] += bx[1];
+  }
+#pragma unroll
+  for (int e = 0; e < 2; ++e) v[e] = MODE == 0 ? gelu_fwd(x2[e]) : d2[e] * gelu_grad(gelu_eval(x2[e]));
+}
+
+// The gated kernels' value, swiglu_value2's argument list: ACT 0 = SwiGLU (above), MI_ACT_GEGLU = GeGLU -- MODE 0: v0 = gelu(g) * u;
+// MODE 1: v0 = d * gelu'(g) * u (gate half), v1 = d * gelu(g) (up half).
+template <int ACT, int MODE>
+__device__ __forceinline__ void gated_value2(u32 wg, u32 wu, u32 wd, bool has_bias, const float* bg, const float* bu, float* v0,
+                                             float* v1) {
+  if (ACT != MI_ACT_GEGLU) {
+    swiglu_value2<MODE>(wg, wu, wd, has_bias, bg, bu, v0, v1);
+    return;
+  }
+  float g2[2] = {__uint_as_float(wg << 16), __uint_as_float(wg & 0xFFFF0000u)};
+  float u2[2] = {__uint_as_float(wu << 16), __uint_as_float(wu & 0xFFFF0000u)};
+  const float d2[2] = {__uint_as_float(wd << 16), __uint_as_float(wd & 0xFFFF0000u)};
+  if (has_bias) {
+    g2[0] += bg[0];
+    g2[1] += bg[1];
+    u2[0] += bu[0];
+    u2[1] += bu[1];
+  }
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const gelu_parts ge = gelu_eval(g2[e]);
+    if (MODE == 0) {
+      v0[e] = (g2[e] * ge.s) * u2[e];
+    } else {
+      v0[e] = (d2[e] * u2[e]) * gelu_grad(ge);
+      v1[e] = d2[e] * (g2[e] * ge.s);
+    }
+  }
+}
+
 }  // namespace mi
 // 8-byte FP8 stores of the cast / quantise kernels (one 8 x 8 block per lane: 8 lanes = one 64-byte row segment).
 // MI_NT_Y / MI_NT_YT (build-time, timing experiments): nontemporal stores for the row-major / the transposed copy.

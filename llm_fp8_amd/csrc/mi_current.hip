@@ -10,6 +10,10 @@
 //                MODE 1  |(x * rstd[r]) * gamma[c]|           (mi_norm_cast; norm_value2)
 //                MODE 2  |silu(g) * u|                        (mi_swiglu_cast(_bias); swiglu_value2<0>)
 //                MODE 3  |d * dsilu(g) * u|, |d * silu(g)|    (mi_dswiglu_cast(_bias); swiglu_value2<1>)
+//                MODE 4  |gelu(x)|                            (mi_act_cast, gelu; gelu_value2<0>)
+//                MODE 5  |d * gelu'(x)|                       (mi_dact_cast, gelu; gelu_value2<1>)
+//                MODE 6  |gelu(g) * u|                        (mi_act_cast, geglu; gated_value2<MI_ACT_GEGLU, 0>)
+//                MODE 7  |d * gelu'(g) * u|, |d * gelu(g)|    (mi_dact_cast, geglu; gated_value2<MI_ACT_GEGLU, 1>)
 //                The fused modes call the value helpers of mi_common.h that the cast kernels call: the bf16 value is never
 //                materialised, so the pass recomputes exactly what the cast will see.  NaN elements are ignored and Inf gives Inf,
 //                as in the cast kernels' own amax.
@@ -36,19 +40,22 @@ __device__ __forceinline__ float amax_acc(float amax, float v) { return fmaxf(am
 
 // A lane owns RPL rows x 8 columns of a tile of (8 * RPL) rows x 64 columns (8 lanes cover one 128-byte line of a row).  RPL = 8
 // for the one-input modes (the cast kernels' 64 x 64 tile) and 4 where a tile has two or three inputs, so that the current tile and
-// the prefetched one stay inside 128 VGPRs.  `cols` is the width of the walked space: the gate space [rows, F] for MODE 2 / 3.
+// the prefetched one stay inside 128 VGPRs.  `cols` is the width of the walked space: the gate space [rows, F] for the gated modes
+// (2, 3, 6, 7: h is [rows, 2F]); the ungated GELU modes 4 / 5 walk h [rows, F] itself.
 template <int MODE, bool NT>
 __global__ __launch_bounds__(256) void amax_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ d,
                                                    const float* __restrict__ rstd, const uint16_t* __restrict__ vec,
                                                    float* __restrict__ partial, int rows, int cols, int tiles_c) {
-  constexpr int RPL = MODE <= 1 ? 8 : 4;
+  constexpr bool GATED = MODE == 2 || MODE == 3 || MODE == 6 || MODE == 7;  // inputs gate | up
+  constexpr bool HAS_D = MODE == 3 || MODE == 5 || MODE == 7;                // backward: dact is the last input
+  constexpr int NIN = 1 + (GATED ? 1 : 0) + (HAS_D ? 1 : 0);
+  constexpr int RPL = NIN == 1 ? 8 : 4;
   constexpr int TR = 8 * RPL;
-  constexpr int NIN = MODE == 3 ? 3 : (MODE == 2 ? 2 : 1);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntiles = ((rows + TR - 1) / TR) * tiles_c;
   const int stride = gridDim.x * 4;
   const int lr = (lane >> 3) * RPL, lc = (lane & 7) * 8;
-  const int64_t ldx = MODE >= 2 ? 2 * (int64_t)cols : (int64_t)cols;  // h is [rows, 2F]
+  const int64_t ldx = GATED ? 2 * (int64_t)cols : (int64_t)cols;  // h is [rows, 2F]
   float amax = 0.0f;
   int t = blockIdx.x * 4 + wave;
   v4i nxt[NIN][RPL], nxt_v[2];
@@ -60,8 +67,8 @@ __global__ __launch_bounds__(256) void amax_kernel(const uint16_t* __restrict__ 
 #pragma unroll
       for (int i = 0; i < RPL; ++i) {
         raw[0][i] = ld16<NT>(src + (int64_t)i * ldx);
-        if (MODE >= 2) raw[1][i] = ld16<NT>(src + (int64_t)i * ldx + cols);
-        if (MODE == 3) raw[NIN - 1][i] = ld16<NT>(d + ((int64_t)r0 + i) * cols + c0);
+        if (GATED) raw[1][i] = ld16<NT>(src + (int64_t)i * ldx + cols);
+        if (HAS_D) raw[NIN - 1][i] = ld16<NT>(d + ((int64_t)r0 + i) * cols + c0);
       }
       if (MODE == 1) {  // gamma slice and the 8 row statistics
         vv[0] = *reinterpret_cast<const v4i*>(vec + c0);
@@ -70,7 +77,7 @@ __global__ __launch_bounds__(256) void amax_kernel(const uint16_t* __restrict__ 
       }
       if (MODE >= 2 && vec != nullptr) {  // fc1 bias: gate slice, up slice
         vv[0] = *reinterpret_cast<const v4i*>(vec + c0);
-        vv[1] = *reinterpret_cast<const v4i*>(vec + cols + c0);
+        if (GATED) vv[1] = *reinterpret_cast<const v4i*>(vec + cols + c0);
       }
     } else {
 #pragma unroll
@@ -116,7 +123,7 @@ __global__ __launch_bounds__(256) void amax_kernel(const uint16_t* __restrict__ 
     } else {
       const int r0 = (t / tiles_c) * TR + lr, c0 = (t % tiles_c) * 64 + lc;
       if (r0 < rows && c0 < cols) {
-        float a[8], b[8];  // MODE 1: gamma; MODE 2 / 3: bias of the gate half, of the up half
+        float a[8], b[8];  // MODE 1: gamma; MODE >= 2: bias of the gate half (of h, ungated), of the up half
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           a[2 * j] = __uint_as_float((u32)v0[j] << 16);
@@ -134,14 +141,21 @@ __global__ __launch_bounds__(256) void amax_kernel(const uint16_t* __restrict__ 
               norm_value2((u32)raw[0][i][j], rs, a[2 * j], a[2 * j + 1], f0, f1);
               amax = amax_acc(amax_acc(amax, f0), f1);
             }
+          } else if (!GATED) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              float f[2];
+              gelu_value2<(HAS_D ? 1 : 0)>((u32)raw[0][i][j], (u32)raw[NIN - 1][i][j], vec != nullptr, a + 2 * j, f);
+              amax = amax_acc(amax_acc(amax, f[0]), f[1]);
+            }
           } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const u32 wg = (u32)raw[0][i][j], wu = (u32)raw[NIN > 1 ? 1 : 0][i][j], wd = (u32)raw[NIN - 1][i][j];
               float f0[2] = {0.0f, 0.0f}, f1[2] = {0.0f, 0.0f};
-              swiglu_value2<(MODE == 3 ? 1 : 0)>(wg, wu, wd, vec != nullptr, a + 2 * j, b + 2 * j, f0, f1);
+              gated_value2<(MODE >= 6 ? MI_ACT_GEGLU : 0), (HAS_D ? 1 : 0)>(wg, wu, wd, vec != nullptr, a + 2 * j, b + 2 * j, f0, f1);
               amax = amax_acc(amax_acc(amax, f0[0]), f0[1]);
-              if (MODE == 3) amax = amax_acc(amax_acc(amax, f1[0]), f1[1]);
+              if (HAS_D) amax = amax_acc(amax_acc(amax, f1[0]), f1[1]);
             }
           }
         }
@@ -171,7 +185,7 @@ __global__ __launch_bounds__(256) void current_scale_kernel(const float* __restr
 template <int MODE>
 static int launch_amax(const char* who, const void* x, const void* d, const float* rstd, const void* vec, float* partial,
                        int n_partial, int64_t rows, int64_t cols, hipStream_t st) {
-  constexpr int TR = MODE <= 1 ? 64 : 32;
+  constexpr int TR = (MODE <= 1 || MODE == 4) ? 64 : 32;  // 8 * RPL of amax_kernel
   const int64_t tiles_c = (cols + 63) / 64;
   MI_CHECK_ARG(((rows + TR - 1) / TR) * tiles_c < (1LL << 31) - 4 * 1024, "%s: shape too large", who);
   hipLaunchKernelGGL((amax_kernel<MODE, MI_AMAX_NT != 0>), dim3((unsigned)n_partial), dim3(256), 0, st, (const uint16_t*)x,
@@ -224,6 +238,30 @@ extern "C" int mi_amax_dswiglu(const void* h_bf16, const void* bias_bf16, const 
   MI_CHECK_ARG(dact_bf16 && ((uintptr_t)dact_bf16 % 16) == 0, "mi_amax_dswiglu: dact must be non-null and 16-byte aligned");
   MI_CHECK_ARG(((uintptr_t)bias_bf16 % 16) == 0, "mi_amax_dswiglu: bias must be 16-byte aligned");
   return mi::launch_amax<3>("mi_amax_dswiglu", h_bf16, dact_bf16, nullptr, bias_bf16, partial, n_partial, rows, F, (hipStream_t)stream);
+}
+
+// the passes of mi_act_cast / mi_dact_cast: `act` picks the mode, the checks are those of the SwiGLU passes
+extern "C" int mi_amax_act(const void* h_bf16, const void* bias_bf16, float* partial, int n_partial, int64_t rows, int64_t F, int act,
+                           void* stream) {
+  MI_CHECK_ARG(act == MI_ACT_GELU || act == MI_ACT_GEGLU, "mi_amax_act: bad act %d (1 = gelu, 2 = geglu)", act);
+  int rc = mi::amax_common_check("mi_amax_act", h_bf16, partial, n_partial, rows, F, act == MI_ACT_GEGLU ? 2 : 1);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(((uintptr_t)bias_bf16 % 16) == 0, "mi_amax_act: bias must be 16-byte aligned");
+  if (act == MI_ACT_GELU)
+    return mi::launch_amax<4>("mi_amax_act", h_bf16, nullptr, nullptr, bias_bf16, partial, n_partial, rows, F, (hipStream_t)stream);
+  return mi::launch_amax<6>("mi_amax_act", h_bf16, nullptr, nullptr, bias_bf16, partial, n_partial, rows, F, (hipStream_t)stream);
+}
+
+extern "C" int mi_amax_dact(const void* h_bf16, const void* bias_bf16, const void* dact_bf16, float* partial, int n_partial,
+                            int64_t rows, int64_t F, int act, void* stream) {
+  MI_CHECK_ARG(act == MI_ACT_GELU || act == MI_ACT_GEGLU, "mi_amax_dact: bad act %d (1 = gelu, 2 = geglu)", act);
+  int rc = mi::amax_common_check("mi_amax_dact", h_bf16, partial, n_partial, rows, F, act == MI_ACT_GEGLU ? 2 : 1);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(dact_bf16 && ((uintptr_t)dact_bf16 % 16) == 0, "mi_amax_dact: dact must be non-null and 16-byte aligned");
+  MI_CHECK_ARG(((uintptr_t)bias_bf16 % 16) == 0, "mi_amax_dact: bias must be 16-byte aligned");
+  if (act == MI_ACT_GELU)
+    return mi::launch_amax<5>("mi_amax_dact", h_bf16, dact_bf16, nullptr, bias_bf16, partial, n_partial, rows, F, (hipStream_t)stream);
+  return mi::launch_amax<7>("mi_amax_dact", h_bf16, dact_bf16, nullptr, bias_bf16, partial, n_partial, rows, F, (hipStream_t)stream);
 }
 
 extern "C" int mi_current_scale(const float* partial, int n_partial, float fp8_max, float amax_epsilon, int pow2, float* out3,

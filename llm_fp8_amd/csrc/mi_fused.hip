@@ -9,6 +9,8 @@
 //                       (the normalised bf16 activation is never materialised) and its backward.
 //   mi_dswiglu_cast     K10 bwd: dh = [dact * dsilu(g) * u | dact * silu(g)] in fp32 -> FP8 (+T) + amax,
 //                       plus deterministic per-row-block column sums for the fc1 bias gradient.
+//   mi_act_cast / mi_dact_cast   the same two steps for tanh-GELU (ungated, a kernel of its own: gelu_cast_kernel) and GeGLU (the
+//                       SwiGLU kernel with gelu in silu's place), fc1 bias nullable (TE LayerNormMLP activation="gelu" / "geglu").
 #include "mi_common.h"
 
 namespace mi {
@@ -197,7 +199,9 @@ __global__ __launch_bounds__(256) void rope_bwd_cast_kernel(const uint16_t* __re
 //               `bias` (optional, bf16 [2F]): h holds the fc1 GEMM's output WITHOUT its bias and the bias is added here, in fp32,
 //               to the unpacked gate / up values (TE's bias + activation fusion: the add rides in an HBM-bound kernel whose VALU
 //               is idle instead of in the GEMM epilogue, where it costs 12 % of the K = 3072 GEMM).
-template <int FMT, int MODE, bool WRITE_Y, bool WRITE_T>
+//               ACT (behind the flags): 0 = SwiGLU; MI_ACT_GEGLU = the same walk with gelu_tanh in silu's place (mi_act_cast /
+//               mi_dact_cast, act = geglu): only the per-element value differs (gated_value2, mi_common.h).
+template <int FMT, int MODE, bool WRITE_Y, bool WRITE_T, int ACT = 0>
 __global__ __launch_bounds__(256) void swiglu_cast_kernel(const uint16_t* __restrict__ h, const uint16_t* __restrict__ d,
                                                           uint8_t* __restrict__ y, uint8_t* __restrict__ yT,
                                                           const float* __restrict__ scale_p, float* amax_out,
@@ -247,7 +251,7 @@ __global__ __launch_bounds__(256) void swiglu_cast_kernel(const uint16_t* __rest
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const u32 wg = (u32)gv[i][j], wu = (u32)uv[i][j], wd = (u32)dv[i][j];
-          swiglu_value2<MODE>(wg, wu, wd, bias != nullptr, bg + 2 * j, bu + 2 * j, f[0] + 2 * j, f[NOUT - 1] + 2 * j);
+          gated_value2<ACT, MODE>(wg, wu, wd, bias != nullptr, bg + 2 * j, bu + 2 * j, f[0] + 2 * j, f[NOUT - 1] + 2 * j);
         }
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) {
@@ -289,15 +293,131 @@ __global__ __launch_bounds__(256) void swiglu_cast_kernel(const uint16_t* __rest
   publish_amax(amax, amax_out);
 }
 
-template <int MODE>
+template <int MODE, int ACT = 0>
 static int launch_swiglu(int fmt, const void* h, const void* d, void* y, void* yT, const float* scale, float* amax, float* colsum,
                          int64_t rows, int64_t F, void* stream, const void* bias = nullptr) {
   const int tiles_r = (int)((rows + 127) / 128), tiles_c = (int)((F + 127) / 128);  // tiles of the [rows, F] gate space
   dim3 grid((unsigned)(tiles_r * tiles_c)), block(256);
-  MI_LAUNCH_FMT_YT(fmt, y, yT, swiglu_cast_kernel, (MODE, ), (), grid, block, 0, (hipStream_t)stream, (const uint16_t*)h,
+  MI_LAUNCH_FMT_YT(fmt, y, yT, swiglu_cast_kernel, (MODE, ), (, ACT), grid, block, 0, (hipStream_t)stream, (const uint16_t*)h,
                    (const uint16_t*)d, (uint8_t*)y, (uint8_t*)yT, scale, amax, colsum, (int)rows, (int)F, tiles_c,
                    (const uint16_t*)bias);
-  MI_CHECK_LAUNCH("mi_swiglu_cast launch");
+  MI_CHECK_LAUNCH(ACT == 0 ? "mi_swiglu_cast launch" : "mi_act_cast launch");
+  return MI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ GELU (+cast), ungated
+// mi_act_cast / mi_dact_cast with act = gelu: ONE input column per output column (gelu_value2, mi_common.h), so an 8 x 8 output
+// block costs 8 (fwd) or 16 (bwd) 16-byte loads where the gated kernel above spends 16 or 24 on it.  With the gated kernel's split (an
+// 8 x 8 block per lane) a forward wave would have half as many loads in flight.  Chosen instead: a lane owns 8 rows x 16 CONTIGUOUS
+// columns -- two neighbouring 8 x 8 blocks, each emitted through store_rows8 / store_cols8 -- so a wave covers 64 rows x 128 columns
+// and a workgroup 128 rows x 256 columns (2 x 2 waves).  Per row a wave then reads 256 contiguous bytes of bf16 (two whole 128-byte
+// lines, 32 bytes per lane) and writes 128 contiguous bytes of the row-major FP8 copy (a whole line; the 8-column split fills half
+// a line per row), the loads in flight per lane are back at 16, and the tile keeps 128 rows, so colsum has mi_dswiglu_cast's
+// [ceil(rows/128), F] layout.  The transposed copy is unchanged: 8 lanes fill 64 contiguous bytes of a yT row.
+// MODE 0 (fwd): all 8 rows in one pass (16 loads per lane).  MODE 1 (bwd, in = h and d): two passes of 4 rows, pinned with
+// sched_barrier as in the gated kernel (16 loads per pass); colsum[tile_r, c] = sum over the tile's 128 rows of val (fp32, fixed order).
+// F is a multiple of 8, not of 16: a lane's second block may lie outside the tensor on its own.
+template <int FMT, int MODE, bool WRITE_Y, bool WRITE_T>
+__global__ __launch_bounds__(256) void gelu_cast_kernel(const uint16_t* __restrict__ h, const uint16_t* __restrict__ d,
+                                                        uint8_t* __restrict__ y, uint8_t* __restrict__ yT,
+                                                        const float* __restrict__ scale_p, float* amax_out,
+                                                        float* __restrict__ colsum, int rows, int F, int tiles_c,
+                                                        const uint16_t* __restrict__ bias) {
+  __shared__ float s_col[2][256];  // MODE 1: [wave row][column of the tile]
+  constexpr int PASSES = MODE == 0 ? 1 : 2, RP = 8 / PASSES;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tile_r = blockIdx.x / tiles_c, tile_c = blockIdx.x % tiles_c;
+  const int r0 = tile_r * 128 + (wave >> 1) * 64 + (lane >> 3) * 8;
+  const int c0 = tile_c * 256 + (wave & 1) * 128 + (lane & 7) * 16;
+  const float scale = *scale_p;
+  float amax = 0.0f;
+  float csum[2][8];
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) csum[k][j] = 0.0f;
+  // rows and F are multiples of 8: a block is all-in or all-out, and block 1 is in only if block 0 is
+  const bool in0 = (r0 < rows) && (c0 < F), in1 = (r0 < rows) && (c0 + 8 < F);
+  if (in0) {
+    u32 lo[2][8], hi[2][8];
+    float b[2][8];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      v4i vb = {0, 0, 0, 0};
+      if (bias != nullptr && (k == 0 || in1)) vb = *reinterpret_cast<const v4i*>(bias + c0 + 8 * k);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        b[k][2 * j] = __uint_as_float((u32)vb[j] << 16);
+        b[k][2 * j + 1] = __uint_as_float((u32)vb[j] & 0xFFFF0000u);
+      }
+    }
+#pragma unroll
+    for (int pass = 0; pass < PASSES; ++pass) {
+      v4i hv[2][RP], dv[2][RP];
+#pragma unroll
+      for (int i = 0; i < RP; ++i) {
+        const int64_t off = (int64_t)(r0 + RP * pass + i) * F + c0;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const bool in = k == 0 || in1;
+          hv[k][i] = in ? __builtin_nontemporal_load(reinterpret_cast<const v4i*>(h + off + 8 * k)) : (v4i){0, 0, 0, 0};
+          dv[k][i] = (MODE == 1 && in) ? __builtin_nontemporal_load(reinterpret_cast<const v4i*>(d + off + 8 * k)) : (v4i){0, 0, 0, 0};
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < RP; ++i)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          if (k == 1 && !in1) continue;
+          float f[8];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) gelu_value2<MODE>((u32)hv[k][i][j], (u32)dv[k][i][j], bias != nullptr, b[k] + 2 * j, f + 2 * j);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            amax = fmaxf(amax, (f[j] != f[j]) ? 0.0f : fabsf(f[j]));
+            if (MODE == 1) csum[k][j] += f[j];
+          }
+          lo[k][RP * pass + i] = cvt4_fp8<FMT>(f[0] * scale, f[1] * scale, f[2] * scale, f[3] * scale);
+          hi[k][RP * pass + i] = cvt4_fp8<FMT>(f[4] * scale, f[5] * scale, f[6] * scale, f[7] * scale);
+        }
+      if (MODE == 1) __builtin_amdgcn_sched_barrier(0);  // keep the second pass's loads behind the first pass's arithmetic
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (k == 1 && !in1) continue;
+      const int c = c0 + 8 * k;
+      if (WRITE_Y) store_rows8<MI_NT_Y>(y + (int64_t)r0 * F + c, F, lo[k], hi[k]);
+      if (WRITE_T) store_cols8<MI_NT_YT>(yT + (int64_t)c * rows + r0, rows, lo[k], hi[k]);
+    }
+  }
+  if (MODE == 1 && colsum != nullptr) {
+    // the 8 row-blocks of a wave (lanes differing in lane >> 3), then the 2 wave rows through LDS: a fixed order
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float v = csum[k][j];
+        v += __shfl_xor(v, 8);
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        if ((lane >> 3) == 0) s_col[wave >> 1][(wave & 1) * 128 + (lane & 7) * 16 + 8 * k + j] = v;
+      }
+    __syncthreads();
+    const int c = tile_c * 256 + tid;
+    if (c < F) colsum[(int64_t)tile_r * F + c] = s_col[0][tid] + s_col[1][tid];
+  }
+  publish_amax(amax, amax_out);
+}
+
+template <int MODE>
+static int launch_gelu(int fmt, const void* h, const void* d, void* y, void* yT, const float* scale, float* amax, float* colsum,
+                       int64_t rows, int64_t F, void* stream, const void* bias) {
+  const int tiles_r = (int)((rows + 127) / 128), tiles_c = (int)((F + 255) / 256);
+  dim3 grid((unsigned)(tiles_r * tiles_c)), block(256);
+  MI_LAUNCH_FMT_YT(fmt, y, yT, gelu_cast_kernel, (MODE, ), (), grid, block, 0, (hipStream_t)stream, (const uint16_t*)h,
+                   (const uint16_t*)d, (uint8_t*)y, (uint8_t*)yT, scale, amax, colsum, (int)rows, (int)F, tiles_c,
+                   (const uint16_t*)bias);
+  MI_CHECK_LAUNCH("mi_act_cast launch");
   return MI_OK;
 }
 
@@ -724,6 +844,37 @@ extern "C" int mi_dswiglu_cast_bias(const void* h_bf16, const void* bias_bf16, c
   MI_CHECK_ARG(bias_bf16 && ((uintptr_t)bias_bf16 % 16) == 0, "mi_dswiglu_cast_bias: bias must be non-null and 16-byte aligned");
   if (rows == 0 || F == 0) return MI_OK;
   return mi::launch_swiglu<1>(fmt, h_bf16, dact_bf16, y_fp8, yT_fp8, scale, amax, colsum, rows, F, stream, bias_bf16);
+}
+
+// GELU / GeGLU fused with the FP8 cast: the SwiGLU entry points' shapes and checks, the activation as an argument, the fc1 bias
+// nullable.  `F` is the OUTPUT width of the forward: h is [rows, F] for gelu and [rows, 2F] for geglu.
+static int act_common_check(const char* who, const void* h, const void* bias, const void* y, const void* yT, const float* scale,
+                            int64_t rows, int64_t F, int act, int fmt) {
+  MI_CHECK_ARG(act == MI_ACT_GELU || act == MI_ACT_GEGLU, "%s: bad act %d (1 = gelu, 2 = geglu)", who, act);
+  int rc = swiglu_common_check(who, h, y, yT, scale, rows, F, fmt);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(((uintptr_t)bias % 16) == 0, "%s: bias must be 16-byte aligned", who);
+  MI_CHECK_ARG(((rows + 127) / 128) * ((F + 127) / 128) < (1LL << 31), "%s: shape too large", who);
+  return MI_OK;
+}
+
+extern "C" int mi_act_cast(const void* h_bf16, const void* bias_bf16, void* y_fp8, void* yT_fp8, const float* scale, float* amax,
+                           int64_t rows, int64_t F, int act, int fmt, void* stream) {
+  int rc = act_common_check("mi_act_cast", h_bf16, bias_bf16, y_fp8, yT_fp8, scale, rows, F, act, fmt);
+  if (rc != MI_OK) return rc;
+  if (rows == 0 || F == 0) return MI_OK;
+  if (act == MI_ACT_GELU) return mi::launch_gelu<0>(fmt, h_bf16, nullptr, y_fp8, yT_fp8, scale, amax, nullptr, rows, F, stream, bias_bf16);
+  return mi::launch_swiglu<0, MI_ACT_GEGLU>(fmt, h_bf16, nullptr, y_fp8, yT_fp8, scale, amax, nullptr, rows, F, stream, bias_bf16);
+}
+
+extern "C" int mi_dact_cast(const void* h_bf16, const void* bias_bf16, const void* dact_bf16, void* y_fp8, void* yT_fp8,
+                            const float* scale, float* amax, float* colsum, int64_t rows, int64_t F, int act, int fmt, void* stream) {
+  int rc = act_common_check("mi_dact_cast", h_bf16, bias_bf16, y_fp8, yT_fp8, scale, rows, F, act, fmt);
+  if (rc != MI_OK) return rc;
+  MI_CHECK_ARG(dact_bf16 && ((uintptr_t)dact_bf16 % 16) == 0, "mi_dact_cast: dact must be non-null and 16-byte aligned");
+  if (rows == 0 || F == 0) return MI_OK;
+  if (act == MI_ACT_GELU) return mi::launch_gelu<1>(fmt, h_bf16, dact_bf16, y_fp8, yT_fp8, scale, amax, colsum, rows, F, stream, bias_bf16);
+  return mi::launch_swiglu<1, MI_ACT_GEGLU>(fmt, h_bf16, dact_bf16, y_fp8, yT_fp8, scale, amax, colsum, rows, F, stream, bias_bf16);
 }
 
 namespace mi {

@@ -89,11 +89,12 @@ def handoff_readers(t) -> bool:
 class _GemmSpec:
     """Everything non-tensor a GEMM site needs: recipe, meta windows, slot base, update trigger."""
     __slots__ = ("recipe", "meta_fwd", "meta_bwd", "g", "fmt_fwd", "fmt_bwd", "trigger_bwd_update", "training", "eps",
-                 "wcache", "first_mb", "with_skip", "rstd", "dy_handoff", "defer_bias", "q")
+                 "wcache", "first_mb", "with_skip", "rstd", "dy_handoff", "defer_bias", "q", "act")
 
     def __init__(self, recipe, meta_fwd, meta_bwd, g, trigger_bwd_update, training, eps=1e-5, wcache=None, first_mb=None,
-                 with_skip=False, rstd=None, dy_handoff=None, defer_bias=False):
+                 with_skip=False, rstd=None, dy_handoff=None, defer_bias=False, act="swiglu"):
         self.dy_handoff = dy_handoff
+        self.act = act  # the fused MLP node's activation: "swiglu", "gelu" or "geglu"
         # LayerNormMLP (fused SwiGLU): under delayed scaling the fc1 bias is added inside the SwiGLU kernels (always, when there
         # is one) and -- defer_bias, both recipes -- the fc2 bias is left to the caller's residual add (residual_add_stats(..., bias=...)): TE's
         # bias + activation fusion.  The bias add costs 12 % of a K = 3072 GEMM in its epilogue and nothing in an HBM-bound kernel.
@@ -302,9 +303,15 @@ class _TensorQ:
             y, yT = ops.norm_cast(x2, norm[0], norm[1], scale, amax, self.fmt_f, want_t=want_t)
         return self._pairs("x", g, own, y, yT)
 
-    def swiglu(self, h, g: int, want_t: bool, bias):
-        scale, amax, own = self._scale("x", g, self._amax_pass(ops.amax_swiglu, h.device, (h.shape[0], h.shape[1] // 2, 32), h, bias))
-        y, yT = ops.swiglu_cast(h, scale, amax, self.fmt_f, want_t=want_t, bias=bias)
+    def swiglu(self, h, g: int, want_t: bool, bias, act: str = "swiglu"):
+        """The fused MLP's activation + cast; `act` "gelu" / "geglu": the same step through ops.act_cast."""
+        if act == "swiglu":
+            scale, amax, own = self._scale("x", g, self._amax_pass(ops.amax_swiglu, h.device, (h.shape[0], h.shape[1] // 2, 32), h, bias))
+            y, yT = ops.swiglu_cast(h, scale, amax, self.fmt_f, want_t=want_t, bias=bias)
+        else:
+            grid = (h.shape[0], h.shape[1] // ops.ACT_CODES[act], 64 if act == "gelu" else 32)
+            scale, amax, own = self._scale("x", g, self._amax_pass(ops.amax_act, h.device, grid, h, act, bias))
+            y, yT = ops.act_cast(h, act, scale, amax, self.fmt_f, want_t=want_t, bias=bias)
         return self._pairs("x", g, own, y, yT)
 
     def quantize_grad(self, g2, g: int, want_y: bool, want_t: bool, colsum: bool = False):
@@ -313,10 +320,15 @@ class _TensorQ:
         out = ops.cast_amax(g2, scale, amax, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum)
         return (*self._pairs("grad", g, own, out[0], out[1]), out[2] if colsum else None)
 
-    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
-        scale, amax, own = self._scale("grad", g, self._amax_pass(ops.amax_dswiglu, h.device, (h.shape[0], h.shape[1] // 2, 32),
-                                                                   h, bias, dact))
-        y, yT, cs = ops.dswiglu_cast(h, dact, scale, amax, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum, bias=bias)
+    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias, act: str = "swiglu"):
+        if act == "swiglu":
+            scale, amax, own = self._scale("grad", g, self._amax_pass(ops.amax_dswiglu, h.device, (h.shape[0], h.shape[1] // 2, 32),
+                                                                       h, bias, dact))
+            y, yT, cs = ops.dswiglu_cast(h, dact, scale, amax, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum, bias=bias)
+        else:
+            grid = (h.shape[0], h.shape[1] // ops.ACT_CODES[act], 32)
+            scale, amax, own = self._scale("grad", g, self._amax_pass(ops.amax_dact, h.device, grid, h, act, bias, dact))
+            y, yT, cs = ops.dact_cast(h, dact, act, scale, amax, self.fmt_b, want_y=want_y, want_t=want_t, want_colsum=colsum, bias=bias)
         return (*self._pairs("grad", g, own, y, yT), cs)
 
     def operands(self, a, b):
@@ -442,8 +454,8 @@ class _MXQ:
             q = ops._norm_quantize(x2, norm[0], norm[1], self.fmt_f, True, want_t, self._gran("x"))
         return q[:2], q[2:]
 
-    def swiglu(self, h, g: int, want_t: bool, bias):
-        assert bias is None
+    def swiglu(self, h, g: int, want_t: bool, bias, act: str = "swiglu"):
+        assert bias is None and act == "swiglu"  # the block-scaled recipes have no GELU / GeGLU kernels
         q = ops._swiglu_quantize(h, self.fmt_f, True, want_t, self._gran("x"))
         return q[:2], q[2:]
 
@@ -451,8 +463,8 @@ class _MXQ:
         q = self._plain("grad", g2, self.fmt_b, rowwise=want_y, colwise=want_t, want_colsum=colsum)
         return q[:2], q[2:4], q[4] if colsum else None
 
-    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias):
-        assert bias is None
+    def dswiglu(self, h, dact, g: int, want_y: bool, want_t: bool, colsum: bool, bias, act: str = "swiglu"):
+        assert bias is None and act == "swiglu"
         q = ops._dswiglu_quantize(h, dact, self.fmt_b, want_y, want_t, colsum, self._gran("grad"))
         return q[:2], q[2:4], q[4]
 
@@ -882,7 +894,8 @@ class _FP8LinearFn(torch.autograd.Function):
 class _FP8SwiGLUMLPFn(torch.autograd.Function):
     """fc1 (FP8) -> SwiGLU fused with the FP8 quantisation of fc2's input -> fc2 (FP8): TE's LayerNormMLP structure
     (te_llama.py:58-63).  The bf16 activation is never materialised; backward fuses dSwiGLU with the quantisation of fc1's
-    grad_output and returns the fc1 bias gradient from the same pass."""
+    grad_output and returns the fc1 bias gradient from the same pass.  spec.act "gelu" / "geglu" (per-tensor recipes): the same
+    node with GELU / GeGLU in SwiGLU's place; fc1 is then [ffn, hidden] / [2 ffn, hidden]."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, spec: _GemmSpec, ln_w=None):
@@ -902,7 +915,7 @@ class _FP8SwiGLUMLPFn(torch.autograd.Function):
         b1_bf = None if b1 is None else b1.detach().to(torch.bfloat16).contiguous()
         fuse_b1 = b1_bf is not None and q.swiglu_adds_bias and _FUSE_MLP_BIAS and (b1_bf.data_ptr() % 16 == 0)
         h = q.gemm(x8[0], w1_8[0], None if fuse_b1 else b1_bf)
-        a8 = q.swiglu(h, 1, plan.a_col, b1_bf if fuse_b1 else None)
+        a8 = q.swiglu(h, 1, plan.a_col, b1_bf if fuse_b1 else None, spec.act)
         ctx.b1_fused = b1_bf if fuse_b1 else None
         w2_8 = _weight_operand(spec, 1, (w2,), [w2.shape[0]], w2.shape[0], w2.shape[1], dev, plan.w2_col)
         # fc2: with defer_bias the caller adds the bias in its residual add (LayerNormMLP.forward hands it over)
@@ -934,7 +947,7 @@ class _FP8SwiGLUMLPFn(torch.autograd.Function):
                                         plan.dact, plan.w2)
         if plan.dact:
             # dSwiGLU + quantisation of fc1's grad_output (GEMM 0) + fc1 bias gradient
-            grad = q.dswiglu(h, dact, 0, *grad_copies(plan.dgrad, plan.w1, plan.b1), plan.b1, ctx.b1_fused)
+            grad = q.dswiglu(h, dact, 0, *grad_copies(plan.dgrad, plan.w1, plan.b1), plan.b1, ctx.b1_fused, ctx.spec.act)
             if plan.b1:
                 db1 = (grad[2], dt_b1)
             if plan.dgrad or plan.w1:
@@ -1215,7 +1228,11 @@ _ACTS = {
 class LayerNormMLP(_FP8Module):
     """Norm -> fc1 (FP8) -> activation -> fc2 (FP8); parameters `layer_norm_weight`, `fc1_weight`
     [gate|up stacked: 2*ffn, hidden], `fc1_bias`, `fc2_weight`, `fc2_bias` (te_llama.py:58-63,219-238).
-    `bias=True` is TE's default and the reference does not override it."""
+    `bias=True` is TE's default and the reference does not override it.
+    `swiglu` under every recipe, and `gelu` / `geglu` under DelayedScaling and Float8CurrentScaling, run fc1 -> activation + FP8
+    cast -> fc2 as one node on the HIP path (with RMSNorm at the widths _can_fuse_norm admits the norm -> cast front joins it; a
+    LayerNorm stays in torch and the node starts at fc1).  `gelu` / `geglu` under MXFP8BlockScaling and Float8BlockScaling, `relu`,
+    `silu` and `fused_swiglu = False` take two FP8 Linears around the torch activation; there is no fused LayerNorm."""
 
     num_gemms = 2
 
@@ -1237,20 +1254,26 @@ class LayerNormMLP(_FP8Module):
         self.use_bias = bias
         self.fc1_bias = torch.nn.Parameter(torch.zeros(mult * ffn_hidden_size, dtype=dt, device=device)) if bias else None
         self.fc2_bias = torch.nn.Parameter(torch.zeros(hidden_size, dtype=dt, device=device)) if bias else None
-        self.fused_swiglu = True  # K10: SwiGLU fused with the FP8 cast (delayed scaling); False -> two Linears + torch ops
+        self.fused_swiglu = True  # K10: the activation fused with the FP8 cast (_fused_act); False -> two Linears + torch ops
+
+    def _fused_act(self, recipe) -> bool:
+        """The activation has a fused cast kernel under `recipe`: SwiGLU everywhere, GELU and GeGLU under the per-tensor recipes."""
+        if not self.fused_swiglu:
+            return False
+        return self.activation == "swiglu" or (self.activation in ops.ACT_CODES and (recipe.delayed() or recipe.current()))
 
     def forward(self, inp: torch.Tensor, is_first_microbatch=None, _with_skip: bool = False, _rstd=None, _defer_bias: bool = False):
         """`_defer_bias` (extension, with `_with_skip`): returns (out, skip, bias) where `out` lacks the fc2 bias and `bias` is the
         tensor the caller must add (residual_add_stats(skip, out, eps, bias=bias)), or None when nothing was deferred."""
         st = self._prepare(inp.device)
-        if (st is not None and self.activation == "swiglu" and self.fused_swiglu and _can_fuse_norm(self, st[0], inp)):
+        if (st is not None and self._fused_act(st[0]) and _can_fuse_norm(self, st[0], inp)):
             # K9 + K10: norm -> cast, fc1, SwiGLU -> cast, fc2 in one autograd node
             # (the residual add that takes the deferred fc2 bias is recipe-independent: MXFP8 defers too; the fc1 bias stays in the
             # MXFP8 GEMM's epilogue, its quantising SwiGLU kernels have no bias form)
             defer = bool(_defer_bias and _with_skip and _FUSE_MLP_BIAS and self.fc2_bias is not None)
             res = _FP8SwiGLUMLPFn.apply(inp, self.fc1_weight, self.fc1_bias, self.fc2_weight, self.fc2_bias,
                                         self._spec(st, is_first_microbatch, eps=self.eps, with_skip=_with_skip,
-                                                   rstd=_usable_rstd(_rstd, inp, self.eps), defer_bias=defer),
+                                                   rstd=_usable_rstd(_rstd, inp, self.eps), defer_bias=defer, act=self.activation),
                                         self.layer_norm_weight)
             if _defer_bias and _with_skip:
                 return res[0], res[1], (self.fc2_bias if defer else None)
@@ -1267,8 +1290,8 @@ class LayerNormMLP(_FP8Module):
             return F.linear(self.act_fn(h), _master(self.fc2_weight).to(ln.dtype),
                             None if self.fc2_bias is None else self.fc2_bias.to(ln.dtype))
         recipe = st[0]
-        if self.activation == "swiglu" and self.fused_swiglu and (not (recipe.mxfp8() or recipe.block()) or inp.numel() // inp.shape[-1] % 32 == 0):
+        if self._fused_act(recipe) and (not (recipe.mxfp8() or recipe.block()) or inp.numel() // inp.shape[-1] % 32 == 0):
             return _FP8SwiGLUMLPFn.apply(ln, self.fc1_weight, self.fc1_bias, self.fc2_weight, self.fc2_bias,
-                                         self._spec(st, is_first_microbatch))
+                                         self._spec(st, is_first_microbatch, act=self.activation))
         h = _FP8LinearFn.apply(ln, self.fc1_bias, self._spec(st, is_first_microbatch), None, self.fc1_weight)
         return _FP8LinearFn.apply(self.act_fn(h), self.fc2_bias, self._spec(st, is_first_microbatch, 1), None, self.fc2_weight)

@@ -706,6 +706,62 @@ def dswiglu_cast(h: torch.Tensor, dact: torch.Tensor, scale: torch.Tensor, amax:
     return y, yT, cs
 
 
+ACT_CODES = {"gelu": 1, "geglu": 2}  # include/mi_fp8.h MI_ACT_*; the value is also h's width in units of F
+
+
+def _act_shapes(h: torch.Tensor, act: str, bias: Optional[torch.Tensor], dact: Optional[torch.Tensor] = None):
+    """(code, R, F) of an act_cast / dact_cast / amax_act / amax_dact call: h bf16 [R, F] (gelu) or [R, 2F] (geglu)."""
+    code = ACT_CODES[act]
+    _dev(h, bias, dact)
+    assert h.dtype == torch.bfloat16 and h.dim() == 2 and h.is_contiguous() and h.shape[1] % code == 0
+    R, F = h.shape[0], h.shape[1] // code
+    assert bias is None or (bias.dtype == torch.bfloat16 and bias.numel() == h.shape[1] and bias.is_contiguous())
+    assert dact is None or (dact.dtype == torch.bfloat16 and dact.shape == (R, F) and dact.is_contiguous())
+    return code, R, F
+
+
+def act_cast(h: torch.Tensor, act: str, scale: torch.Tensor, amax: Optional[torch.Tensor], fmt: int, want_y: bool = True,
+             want_t: bool = True, bias: Optional[torch.Tensor] = None):
+    """swiglu_cast for act = "gelu" (h bf16 [R, F]: gelu_tanh(h)) or "geglu" (h [R, 2F]: gelu_tanh(gate) * up), in fp32
+    -> (act8 [R, F], act8T [F, R]).  `bias` (bf16, h's width): as swiglu_cast."""
+    code, R, F = _act_shapes(h, act, bias)
+    _dev(scale, amax)
+    y, yT = _u8_pair(R, F, h.device, want_y, want_t)
+    args = (h.data_ptr(), _ptr(bias), _ptr(y), _ptr(yT), scale.data_ptr(), _ptr(amax), R, F, code, fmt, _stream())
+    _launch(_lib.require("mi_act_cast", f"LayerNormMLP activation={act!r}"), args, "mi_act_cast", "act_cast",
+            lambda: (f"{act} {R}x{F}", float(R * F), float(R * F * (2 * code + int(want_y) + int(want_t)))))
+    return y, yT
+
+
+def dact_cast(h: torch.Tensor, dact: torch.Tensor, act: str, scale: torch.Tensor, amax: Optional[torch.Tensor], fmt: int,
+              want_y: bool = True, want_t: bool = True, want_colsum: bool = False, bias: Optional[torch.Tensor] = None):
+    """dswiglu_cast for act = "gelu" (dh = dact * gelu'(h), [R, F]) or "geglu" (dh = [dact * gelu'(g) * u | dact * gelu(g)], [R, 2F])
+    -> (dh8, dh8T, colsum fp32 [ceil(R/128), dh's width] or None)."""
+    code, R, F = _act_shapes(h, act, bias, dact)
+    _dev(scale, amax)
+    C = code * F
+    y, yT = _u8_pair(R, C, h.device, want_y, want_t)
+    cs = torch.empty(((R + 127) // 128, C), dtype=torch.float32, device=h.device) if want_colsum else None
+    args = (h.data_ptr(), _ptr(bias), dact.data_ptr(), _ptr(y), _ptr(yT), scale.data_ptr(), _ptr(amax), _ptr(cs), R, F, code, fmt, _stream())
+    _launch(_lib.require("mi_dact_cast", f"LayerNormMLP activation={act!r}"), args, "mi_dact_cast", "dact_cast",
+            lambda: (f"{act} {R}x{F}", float(R * C), float(R * F * (2 * code + 2) + R * C * (int(want_y) + int(want_t)))))
+    return y, yT, cs
+
+
+def amax_act(h: torch.Tensor, act: str, bias: Optional[torch.Tensor], partial: torch.Tensor) -> None:
+    """amax_bf16 of the value act_cast quantises."""
+    code, R, F = _act_shapes(h, act, bias)
+    _amax_call("mi_amax_act", (h.data_ptr(), _ptr(bias), partial.data_ptr(), _partial_ok(partial), R, F, code, _stream()),
+               f"{act} {R}x{F}", float(R * F), 2.0 * code * R * F)
+
+
+def amax_dact(h: torch.Tensor, act: str, bias: Optional[torch.Tensor], dact: torch.Tensor, partial: torch.Tensor) -> None:
+    """amax_bf16 of the value dact_cast quantises (both halves of dh for geglu)."""
+    code, R, F = _act_shapes(h, act, bias, dact)
+    _amax_call("mi_amax_dact", (h.data_ptr(), _ptr(bias), dact.data_ptr(), partial.data_ptr(), _partial_ok(partial), R, F, code, _stream()),
+               f"d{act} {R}x{F}", float(code * R * F), (2.0 * code + 2.0) * R * F)
+
+
 def rmsnorm_stats(x: torch.Tensor, eps: float) -> torch.Tensor:
     """K9: rstd[r] = rsqrt(mean(x[r]^2) + eps), fp32 [R]."""
     _dev(x)
