@@ -81,9 +81,11 @@ extern "C" {
  *      inside its own; the same three kernels walk only the documents)
  *  11  mi_act_cast, mi_dact_cast, mi_amax_act, mi_amax_dact (tanh-GELU and GeGLU fused with the FP8 cast of fc2's input and of
  *      fc1's grad_output, and their current-scaling amax passes)
+ *  12  mi_layernorm_stats, mi_ln_cast, mi_amax_ln, mi_layernorm_bwd (LayerNorm fused with the FP8 cast of the following GEMM's
+ *      input, its current-scaling amax pass and its backward, at any width that is a multiple of 8 up to 8192)
  */
 #define MI_ABI_VERSION 5
-#define MI_ABI_REVISION 11
+#define MI_ABI_REVISION 12
 int mi_abi_version(void);
 int mi_abi_revision(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -438,6 +440,32 @@ int mi_norm_cast(const void* x_bf16, const float* rstd, const void* gamma_bf16, 
 int mi_rmsnorm_bwd(const void* dy_bf16, const void* x_bf16, const float* rstd, const void* gamma_bf16,
                    const void* dres_bf16, void* dx_bf16, float* dgamma_partial, int n_partials, int64_t rows,
                    int64_t cols, void* stream);
+
+/*
+ * LayerNorm fused with the FP8 cast of the following GEMM's input (revision 12)  [TE LayerNormLinear / LayerNormMLP with
+ *     normalization="LayerNorm", their default].  K9 with a mean and a bias; g[c] = gamma[c], or 1 + gamma[c] (fp32) when
+ *     zero_centered != 0.  Every width that is a multiple of 8 runs (768, 1280, 1600, 2560 ...): lanes past a row's end are off.
+ *   mi_layernorm_stats: mean[r] = mean_c x[r,c]; rstd[r] = rsqrt(mean_c (x[r,c] - mean[r])^2 + eps), the biased variance taken in
+ *                       a second pass over the row held in registers (fp32, one wave per row, fixed order).  cols <= 8192.
+ *   mi_ln_cast:         v = ((x[r,c] - mean[r]) * rstd[r]) * g[c] + beta[c] in fp32; y = sat_cast(v * *scale), yT,
+ *                       *amax = max(*amax, max|v|), NaN ignored; y or yT may be NULL.  rows, cols multiples of 8.
+ *   mi_amax_ln:         the amax pass of mi_ln_cast under the contract of "Current scaling" below (n_partial workgroups, every
+ *                       partial written, no atomics, the cast's own value code).
+ *   mi_layernorm_bwd:   xhat = (x - mean) * rstd, dyg = dy * g:  dx = rstd * (dyg - mean_c(dyg) - xhat * mean_c(dyg * xhat)) (+ dres);
+ *                       dgamma_partial[b, c] = sum over block b's rows of dy * xhat, dbeta_partial[b, c] = sum of dy (fp32
+ *                       [n_partials, cols] each, fixed order, every entry written; mi_colsum_finish(_multi) adds the blocks).
+ *                       cols <= 8192; dres nullable.
+ * Inputs (x, dy, dres, dx, gamma, beta: bf16; mean, rstd, partials: fp32) are 16-byte aligned, y / yT 8-byte; a violation is
+ * MI_ERR_ARG under the entry point's name and nothing is launched.
+ */
+int mi_layernorm_stats(const void* x_bf16, float* mean, float* rstd, int64_t rows, int64_t cols, float eps, void* stream);
+int mi_ln_cast(const void* x_bf16, const float* mean, const float* rstd, const void* gamma_bf16, const void* beta_bf16, void* y_fp8,
+               void* yT_fp8, const float* scale, float* amax, int64_t rows, int64_t cols, int zero_centered, int fmt, void* stream);
+int mi_amax_ln(const void* x_bf16, const float* mean, const float* rstd, const void* gamma_bf16, const void* beta_bf16,
+               float* partial, int n_partial, int64_t rows, int64_t cols, int zero_centered, void* stream);
+int mi_layernorm_bwd(const void* dy_bf16, const void* x_bf16, const float* mean, const float* rstd, const void* gamma_bf16,
+                     const void* dres_bf16, void* dx_bf16, float* dgamma_partial, float* dbeta_partial, int n_partials,
+                     int64_t rows, int64_t cols, int zero_centered, void* stream);
 
 /*
  * Current scaling (ABI 5 revision 2; TE's Float8CurrentScaling): a tensor is quantised with a scale computed from its OWN amax, so

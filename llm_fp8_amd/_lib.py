@@ -13,7 +13,7 @@ LAB_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "bin", "libmi_fp8_l
 MI_FMT_E4M3 = 0
 MI_FMT_E5M2 = 1
 ABI_VERSION = 5
-ABI_REVISION = 11  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
+ABI_REVISION = 12  # include/mi_fp8.h MI_ABI_REVISION: entry points added since ABI_VERSION (REVISION_SIGNATURES below)
 # revision 5 adds no symbol: from it on every mi_adamw_* entry point reads a non-finite *grad_scale as "skip the step" (optim.py)
 
 _c_i64 = ctypes.c_int64
@@ -132,6 +132,11 @@ REVISION_SIGNATURES = {
     "mi_dact_cast": [_p, _p, _p, _p, _p, _p, _p, _p, _c_i64, _c_i64, _c_int, _c_int, _p],
     "mi_amax_act": [_p, _p, _p, _c_int, _c_i64, _c_i64, _c_int, _p],
     "mi_amax_dact": [_p, _p, _p, _p, _c_int, _c_i64, _c_i64, _c_int, _p],
+    # revision 12: LayerNorm fused with the FP8 cast (the RMSNorm argument lists + mean, beta, the dbeta partials and `zero_centered`)
+    "mi_layernorm_stats": [_p, _p, _p, _c_i64, _c_i64, ctypes.c_float, _p],
+    "mi_ln_cast": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _c_i64, _c_i64, _c_int, _c_int, _p],
+    "mi_amax_ln": [_p, _p, _p, _p, _p, _p, _c_int, _c_i64, _c_i64, _c_int, _p],
+    "mi_layernorm_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _c_int, _c_i64, _c_i64, _c_int, _p],
 }
 SIGNATURES.update(REVISION_SIGNATURES)
 # entry points only the lab build exports (#ifdef MI_DIAG in include/mi_fp8.h)

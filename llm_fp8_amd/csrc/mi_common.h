@@ -163,6 +163,12 @@ __device__ __forceinline__ void norm_value2(u32 w, float rs, float g0, float g1,
   v1 = (__uint_as_float(w & 0xFFFF0000u) * rs) * g1;
 }
 
+// mi_ln_cast / mi_amax_ln: the same for LayerNorm -- (x - mean) * rstd, times g (gamma, or 1 + gamma when zero-centred), plus beta
+__device__ __forceinline__ void ln_value2(u32 w, float mu, float rs, float g0, float g1, float b0, float b1, float& v0, float& v1) {
+  v0 = ((__uint_as_float(w << 16) - mu) * rs) * g0 + b0;
+  v1 = ((__uint_as_float(w & 0xFFFF0000u) - mu) * rs) * g1 + b1;
+}
+
 // mi_swiglu_cast(_bias) (MODE 0): v0 = silu(g) * u.  mi_dswiglu_cast(_bias) (MODE 1): v0 = d * dsilu(g) * u (gate half),
 // v1 = d * silu(g) (up half).  For the two bf16 halves of the packed words wg (gate), wu (up), wd (dact); `has_bias` (wave-uniform):
 // the fc1 bias bg[0..1] / bu[0..1] is added, in fp32, to the unpacked gate / up values first.  MODE 0 leaves v1 alone.

@@ -89,11 +89,14 @@ def handoff_readers(t) -> bool:
 class _GemmSpec:
     """Everything non-tensor a GEMM site needs: recipe, meta windows, slot base, update trigger."""
     __slots__ = ("recipe", "meta_fwd", "meta_bwd", "g", "fmt_fwd", "fmt_bwd", "trigger_bwd_update", "training", "eps",
-                 "wcache", "first_mb", "with_skip", "rstd", "dy_handoff", "defer_bias", "q", "act")
+                 "wcache", "first_mb", "with_skip", "rstd", "dy_handoff", "defer_bias", "q", "act", "ln_bias", "zero_centered")
 
     def __init__(self, recipe, meta_fwd, meta_bwd, g, trigger_bwd_update, training, eps=1e-5, wcache=None, first_mb=None,
-                 with_skip=False, rstd=None, dy_handoff=None, defer_bias=False, act="swiglu"):
+                 with_skip=False, rstd=None, dy_handoff=None, defer_bias=False, act="swiglu", ln_bias=False, zero_centered=False):
         self.dy_handoff = dy_handoff
+        # ln_bias: the fused norm is a LayerNorm -- _FP8LinearFn then finds its bias behind the weight parts (the last of `*weights`);
+        # zero_centered: its weight is stored as gamma - 1 (LayerNorm only: the fused RMSNorm is refused zero-centred)
+        self.ln_bias, self.zero_centered = ln_bias, zero_centered
         self.act = act  # the fused MLP node's activation: "swiglu", "gelu" or "geglu"
         # LayerNormMLP (fused SwiGLU): under delayed scaling the fc1 bias is added inside the SwiGLU kernels (always, when there
         # is one) and -- defer_bias, both recipes -- the fc2 bias is left to the caller's residual add (residual_add_stats(..., bias=...)): TE's
@@ -294,10 +297,15 @@ class _TensorQ:
         return (y, si), (yT, si_t)
 
     def quantize(self, x2, g: int, want_t: bool, norm=None):
-        """`norm` = (rstd, gamma): x2 is un-normalised and RMSNorm is fused into the cast."""
+        """`norm` = (rstd, gamma): x2 is un-normalised and RMSNorm is fused into the cast.  `norm` = (rstd, gamma, mean, beta,
+        zero_centered): the same for LayerNorm (ops.ln_cast)."""
         if norm is None:
             scale, amax, own = self._scale("x", g, self._amax_pass(ops.amax_bf16, x2.device, x2.shape, x2))
             y, yT = ops.cast_amax(x2, scale, amax, self.fmt_f, want_t=want_t)
+        elif len(norm) == 5:
+            rstd, gam, mean, beta, zc = norm
+            scale, amax, own = self._scale("x", g, self._amax_pass(ops.amax_ln, x2.device, x2.shape, x2, mean, rstd, gam, beta, zc))
+            y, yT = ops.ln_cast(x2, mean, rstd, gam, beta, scale, amax, self.fmt_f, zero_centered=zc, want_t=want_t)
         else:
             scale, amax, own = self._scale("x", g, self._amax_pass(ops.amax_norm, x2.device, x2.shape, x2, norm[0], norm[1]))
             y, yT = ops.norm_cast(x2, norm[0], norm[1], scale, amax, self.fmt_f, want_t=want_t)
@@ -781,13 +789,20 @@ def _claim_bwd_update(ctx, spec: _GemmSpec) -> None:
         spec.trigger_bwd_update = FP8GlobalStateManager.is_first_fp8_module()
 
 
-def _quantize_input(ctx, spec: _GemmSpec, x2, ln_w, want_t: bool, need_dgrad: bool):
+def _quantize_input(ctx, spec: _GemmSpec, x2, ln_w, want_t: bool, need_dgrad: bool, ln_b=None):
     """The input of GEMM spec.g as an FP8 operand.  `ln_w` (with spec.eps): K9 -- x2 is the UN-normalised input and RMSNorm is
-    fused into its quantisation; ctx.norm keeps what the RMSNorm backward needs."""
+    fused into its quantisation; ctx.norm keeps what the RMSNorm backward needs.  `ln_b`: the norm is a LayerNorm (statistics,
+    cast and backward of mi_layernorm.hip; spec.rstd, an RMSNorm statistic, is not used)."""
     ctx.norm = None
     if ln_w is None:
         return spec.q.quantize(x2, spec.g, want_t)
     gam = (ln_w if ln_w.dtype == torch.bfloat16 else ln_w.to(torch.bfloat16)).contiguous()
+    if ln_b is not None:
+        beta = (ln_b if ln_b.dtype == torch.bfloat16 else ln_b.to(torch.bfloat16)).contiguous()
+        mean, rstd = ops.layernorm_stats(x2, spec.eps)
+        if need_dgrad:
+            ctx.norm = (x2, rstd, gam, ln_w.dtype, mean, ln_b.dtype, spec.zero_centered)
+        return spec.q.quantize(x2, spec.g, want_t, (rstd, gam, mean, beta, spec.zero_centered))
     # spec.rstd: the statistics came with the input (residual_add_stats)
     rstd = spec.rstd if spec.rstd is not None else ops.rmsnorm_stats(x2, spec.eps)
     if need_dgrad:
@@ -799,21 +814,27 @@ def _finish_dx(ctx, dx, dskip, colsums=None):
     """The end of a GEMM Function's backward: RMSNorm backward of a fused norm with the residual-branch gradient added in the
     kernel, the update trigger, dx in the input's shape and dtype, `dskip` added where no kernel took it.
     `colsums`: the caller's bias gradients as (partial column sums, dtype) or None each -- ONE launch finishes them together
-    with the RMSNorm weight gradient.  Returns (dx, dln, finished colsums)."""
-    dln = None
+    with the norm's weight (and, LayerNorm, bias) gradient.  Returns (dx, dln, dlb, finished colsums); dlb is None for RMSNorm."""
+    dln = dlb = None
     if ctx.norm is not None and dx is not None:
-        xin, rstd, gam, ln_dtype = ctx.norm
+        xin, rstd, gam, ln_dtype, *ln = ctx.norm
         ctx.norm = None
-        dx, dln = ops.rmsnorm_bwd(dx, xin, rstd, gam, dres=_skip_2d(dskip, dx), dgamma_dtype=ln_dtype, finish=colsums is None)
+        if ln:
+            mean, lb_dtype, zc = ln
+            dx, dln, dlb = ops.layernorm_bwd(dx, xin, mean, rstd, gam, dres=_skip_2d(dskip, dx), zero_centered=zc, dgamma_dtype=ln_dtype,
+                                             dbeta_dtype=lb_dtype, finish=colsums is None)
+        else:
+            dx, dln = ops.rmsnorm_bwd(dx, xin, rstd, gam, dres=_skip_2d(dskip, dx), dgamma_dtype=ln_dtype, finish=colsums is None)
         dskip = None
         if colsums is not None:
-            dln = (dln, ln_dtype)
+            dln, dlb = (dln, ln_dtype), (None if dlb is None else (dlb, lb_dtype))
     if colsums is not None:
-        pend = [t for t in (*colsums, dln) if t is not None]
+        pend = [t for t in (*colsums, dln, dlb) if t is not None]
         if pend:
             done = iter(ops.colsum_finish_multi(pend))
             colsums = [None if t is None else next(done) for t in colsums]
             dln = None if dln is None else next(done)
+            dlb = None if dlb is None else next(done)
     if ctx.spec.trigger_bwd_update:
         # this is the first GEMM Function of the outermost autocast that has a backward (_claim_bwd_update): its backward is the last
         FP8GlobalStateManager.reduce_and_update_fp8_tensors(forward=False)
@@ -821,7 +842,7 @@ def _finish_dx(ctx, dx, dskip, colsums=None):
         dx = dx.view(ctx.x_shape).to(ctx.x_dtype)
     if dskip is not None:
         dx = dskip if dx is None else dx + dskip
-    return dx, dln, colsums
+    return dx, dln, dlb, colsums
 
 
 class _FP8LinearFn(torch.autograd.Function):
@@ -830,7 +851,10 @@ class _FP8LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, bias: Optional[torch.Tensor], spec: _GemmSpec, ln_w: Optional[torch.Tensor],
                 *weights: torch.Tensor):
-        """`ln_w`: see _quantize_input."""
+        """`ln_w`: see _quantize_input.  With spec.ln_bias the last of `weights` is the LayerNorm bias."""
+        ln_b = None
+        if spec.ln_bias:
+            *weights, ln_b = weights
         x2 = _as_bf16_2d(x)
         M, K = x2.shape
         if M % 8 or K % 16:
@@ -840,10 +864,10 @@ class _FP8LinearFn(torch.autograd.Function):
         q, g = spec.q, spec.g
         # (forward runs in no-grad mode; needs_input_grad is all-False when grad was disabled at apply time)
         nig = ctx.needs_input_grad
-        plan = linear_plan(nig[0], nig[1], nig[3], any(nig[4:]))
+        plan = linear_plan(nig[0], nig[1], nig[3] or (ln_b is not None and nig[-1]), any(nig[4:4 + len(weights)]))
         need_dgrad, need_wgrad = plan.dgrad, plan.wgrad
         _claim_bwd_update(ctx, spec)
-        x8 = _quantize_input(ctx, spec, x2, ln_w, plan.x_col, need_dgrad)
+        x8 = _quantize_input(ctx, spec, x2, ln_w, plan.x_col, need_dgrad, ln_b)
         w8 = _weight_operand(spec, g, weights, ns, N, K, x2.device, plan.w_col)
         y = q.gemm(x8[0], w8[0], None if bias is None else bias.to(torch.bfloat16).contiguous())
         ctx.saved_fp8 = (x8[1], w8[1])
@@ -883,12 +907,12 @@ class _FP8LinearFn(torch.autograd.Function):
                                      plan.dgrad, plan.wgrad)
         if plan.dbias and db is None:
             db = g2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
-        dx, dln, _ = _finish_dx(ctx, dx, dskip)
+        dx, dln, dlb, _ = _finish_dx(ctx, dx, dskip)
         dws: List[Optional[torch.Tensor]] = [None] * len(ctx.ns)
         if dw is not None:
             parts = torch.split(dw, ctx.ns, dim=0)
             dws = [p if p.dtype == dt else p.to(dt) for p, dt in zip(parts, ctx.w_dtypes)]
-        return (dx, db, None, dln, *dws)
+        return (dx, db, None, dln, *dws, *((dlb,) if spec.ln_bias else ()))
 
 
 class _FP8SwiGLUMLPFn(torch.autograd.Function):
@@ -898,17 +922,17 @@ class _FP8SwiGLUMLPFn(torch.autograd.Function):
     node with GELU / GeGLU in SwiGLU's place; fc1 is then [ffn, hidden] / [2 ffn, hidden]."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, spec: _GemmSpec, ln_w=None):
+    def forward(ctx, x, w1, b1, w2, b2, spec: _GemmSpec, ln_w=None, ln_b=None):
         x2 = _as_bf16_2d(x)
         M, K = x2.shape
         if M % 8 or K % 16:
             raise RuntimeError(f"FP8 LayerNormMLP needs tokens % 8 == 0 and hidden % 16 == 0, got {M} x {K}")
         q, dev = spec.q, x2.device
         nig = ctx.needs_input_grad
-        # (the unfused route applies this Function without `ln_w`: needs_input_grad then has six entries)
-        plan = mlp_plan(nig[0], nig[1], nig[2], nig[3], nig[4], len(nig) > 6 and nig[6])
+        # (the unfused route applies this Function without `ln_w`: needs_input_grad then has six entries; `ln_b`: a fused LayerNorm)
+        plan = mlp_plan(nig[0], nig[1], nig[2], nig[3], nig[4], any(nig[6:]))
         _claim_bwd_update(ctx, spec)
-        x8 = _quantize_input(ctx, spec, x2, ln_w, plan.x_col, plan.dgrad)
+        x8 = _quantize_input(ctx, spec, x2, ln_w, plan.x_col, plan.dgrad, ln_b)
         w1_8 = _weight_operand(spec, 0, (w1,), [w1.shape[0]], w1.shape[0], K, dev, plan.w1_col)
         # fc1: where the SwiGLU kernels take a bias the GEMM leaves it out and they add it (fp32) to the gate / up values they
         # unpack anyway; else it stays in the GEMM's epilogue
@@ -953,12 +977,12 @@ class _FP8SwiGLUMLPFn(torch.autograd.Function):
             if plan.dgrad or plan.w1:
                 dx, dw1 = _grouped_or_two(q, grad, w1_col, x_col, _wgrad_out(ctx.w_refs[:1], x_col[0].shape[0]) if plan.w1 else None,
                                           plan.dgrad, plan.w1)
-        dx, dln, (db1, db2) = _finish_dx(ctx, dx, dskip, (db1, db2))
+        dx, dln, dlb, (db1, db2) = _finish_dx(ctx, dx, dskip, (db1, db2))
         if dw1 is not None and dw1.dtype != dt_w1:
             dw1 = dw1.to(dt_w1)
         if dw2 is not None and dw2.dtype != dt_w2:
             dw2 = dw2.to(dt_w2)
-        return dx, dw1, db1, dw2, db2, None, dln
+        return dx, dw1, db1, dw2, db2, None, dln, dlb
 
 
 class _FP8Module(torch.nn.Module):
@@ -1182,6 +1206,10 @@ class LayerNormLinear(_FP8Module):
         st = self._prepare(inp.device)
         ws, b = self._weights(), self._bias()
         if st is not None and _can_fuse_norm(self, st[0], inp) and not self.return_layernorm_output:
+            if self.normalization == "LayerNorm":  # (`_rstd` is an RMSNorm statistic: not used)
+                return _FP8LinearFn.apply(inp, b, self._spec(st, is_first_microbatch, eps=self.eps, with_skip=_with_skip,
+                                                             dy_handoff=_dy_handoff, ln_bias=True, zero_centered=self.zero_centered_gamma),
+                                          self.layer_norm_weight, *ws, self.layer_norm_bias)
             return _FP8LinearFn.apply(inp, b, self._spec(st, is_first_microbatch, eps=self.eps, with_skip=_with_skip,
                                                          rstd=_usable_rstd(_rstd, inp, self.eps), dy_handoff=_dy_handoff),
                                       self.layer_norm_weight, *ws)
@@ -1207,8 +1235,11 @@ def _usable_rstd(handoff, inp: torch.Tensor, eps: float):
 
 
 def _can_fuse_norm(mod, recipe, inp) -> bool:
-    """K9 applies to RMSNorm (every recipe); the backward kernel keeps a whole row per wave (cols % 512, <= 8192)."""
+    """K9 applies to RMSNorm (every recipe); the backward kernel keeps a whole row per wave (cols % 512, <= 8192).  LayerNorm
+    (mi_layernorm.hip) fuses under the two per-tensor recipes at every hidden % 16 == 0 up to 8192, zero-centred or not."""
     h = inp.shape[-1]
+    if mod.normalization == "LayerNorm":
+        return bool(getattr(mod, "fused_norm", True) and (recipe.delayed() or recipe.current()) and h % 16 == 0 and h <= 8192)
     return (getattr(mod, "fused_norm", True) and mod.normalization == "RMSNorm" and not mod.zero_centered_gamma
             and (recipe.delayed() or recipe.mxfp8() or recipe.current() or recipe.block()) and h % 512 == 0 and h // 512 in (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16))
 
@@ -1230,9 +1261,11 @@ class LayerNormMLP(_FP8Module):
     [gate|up stacked: 2*ffn, hidden], `fc1_bias`, `fc2_weight`, `fc2_bias` (te_llama.py:58-63,219-238).
     `bias=True` is TE's default and the reference does not override it.
     `swiglu` under every recipe, and `gelu` / `geglu` under DelayedScaling and Float8CurrentScaling, run fc1 -> activation + FP8
-    cast -> fc2 as one node on the HIP path (with RMSNorm at the widths _can_fuse_norm admits the norm -> cast front joins it; a
-    LayerNorm stays in torch and the node starts at fc1).  `gelu` / `geglu` under MXFP8BlockScaling and Float8BlockScaling, `relu`,
-    `silu` and `fused_swiglu = False` take two FP8 Linears around the torch activation; there is no fused LayerNorm."""
+    cast -> fc2 as one node on the HIP path, and where _can_fuse_norm admits the norm its norm -> cast front joins the node: RMSNorm
+    under every recipe at its widths, LayerNorm (zero-centred or not) under DelayedScaling and Float8CurrentScaling at any hidden
+    size that is a multiple of 16 up to 8192; elsewhere the norm runs in torch and the node starts at fc1.  `gelu` / `geglu` under
+    MXFP8BlockScaling and Float8BlockScaling, `relu`, `silu` and `fused_swiglu = False` take two FP8 Linears around the torch
+    activation."""
 
     num_gemms = 2
 
@@ -1271,10 +1304,12 @@ class LayerNormMLP(_FP8Module):
             # (the residual add that takes the deferred fc2 bias is recipe-independent: MXFP8 defers too; the fc1 bias stays in the
             # MXFP8 GEMM's epilogue, its quantising SwiGLU kernels have no bias form)
             defer = bool(_defer_bias and _with_skip and _FUSE_MLP_BIAS and self.fc2_bias is not None)
+            ln = self.normalization == "LayerNorm"  # (`_rstd` is an RMSNorm statistic: not used then)
             res = _FP8SwiGLUMLPFn.apply(inp, self.fc1_weight, self.fc1_bias, self.fc2_weight, self.fc2_bias,
                                         self._spec(st, is_first_microbatch, eps=self.eps, with_skip=_with_skip,
-                                                   rstd=_usable_rstd(_rstd, inp, self.eps), defer_bias=defer, act=self.activation),
-                                        self.layer_norm_weight)
+                                                   rstd=None if ln else _usable_rstd(_rstd, inp, self.eps), defer_bias=defer,
+                                                   act=self.activation, ln_bias=ln, zero_centered=ln and self.zero_centered_gamma),
+                                        self.layer_norm_weight, self.layer_norm_bias)
             if _defer_bias and _with_skip:
                 return res[0], res[1], (self.fc2_bias if defer else None)
             return res

@@ -821,6 +821,79 @@ def rmsnorm_bwd(dy: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, gamma: to
     return (dx, colsum_finish(part, dgamma_dtype)) if finish else (dx, part)
 
 
+# ---- LayerNorm fused with the FP8 cast (mi_layernorm.hip): the four ops above with a mean, a bias and `zero_centered` ----
+_LN_WHY = "the fused LayerNorm"
+
+
+def _ln_ok(x, mean, rstd, gamma, beta):
+    _dev(x, mean, rstd, gamma, beta)
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
+    R, C = x.shape
+    for s in (mean, rstd):
+        assert s.dtype == torch.float32 and s.is_contiguous() and s.numel() == R
+    for v in (gamma, beta):
+        assert v is None or (v.dtype == torch.bfloat16 and v.is_contiguous() and v.numel() == C)
+    return R, C
+
+
+def layernorm_stats(x: torch.Tensor, eps: float):
+    """(mean, rstd) of every row of x bf16 [R, C], fp32 [R] each: rstd = rsqrt(biased variance + eps), the variance from
+    sum (x - mean)^2 over the row kept in registers.  C % 8 == 0, C <= 8192."""
+    _dev(x)
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()
+    R, C = x.shape
+    mean = torch.empty(R, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(R, dtype=torch.float32, device=x.device)
+    fn = _lib.require("mi_layernorm_stats", _LN_WHY)
+    _lib.check(fn(x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), R, C, float(eps), _stream()), "mi_layernorm_stats")
+    return mean, rstd
+
+
+def ln_cast(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, scale: torch.Tensor,
+            amax: Optional[torch.Tensor], fmt: int, zero_centered: bool = False, want_y: bool = True, want_t: bool = True):
+    """((x - mean[:, None]) * rstd[:, None]) * g + beta in fp32 (g = gamma, or 1 + gamma when zero_centered) -> (y8 [R, C],
+    y8T [C, R]) + amax; no bf16 normalised tensor is written."""
+    R, C = _ln_ok(x, mean, rstd, gamma, beta)
+    _dev(scale, amax)
+    y, yT = _u8_pair(R, C, x.device, want_y, want_t)
+    args = (x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(y), _ptr(yT), scale.data_ptr(),
+            _ptr(amax), R, C, int(bool(zero_centered)), fmt, _stream())
+    _launch(_lib.require("mi_ln_cast", _LN_WHY), args, "mi_ln_cast", "ln_cast",
+            lambda: (f"{R}x{C}", float(R * C), float(R * C * (2 + int(want_y) + int(want_t)))))
+    return y, yT
+
+
+def amax_ln(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, zero_centered: bool,
+            partial: torch.Tensor) -> None:
+    """amax_bf16 of the value ln_cast quantises."""
+    R, C = _ln_ok(x, mean, rstd, gamma, beta)
+    _amax_call("mi_amax_ln", (x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), partial.data_ptr(),
+                              _partial_ok(partial), R, C, int(bool(zero_centered)), _stream()),
+               f"ln {R}x{C}", float(R * C), 2.0 * R * C)
+
+
+def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor,
+                  dres: Optional[torch.Tensor] = None, n_partials: int = 512, zero_centered: bool = False,
+                  dgamma_dtype: torch.dtype = torch.float32, dbeta_dtype: Optional[torch.dtype] = None, finish: bool = True):
+    """LayerNorm backward: (dx bf16 [R, C], dgamma [C], dbeta [C]).  dgamma and dbeta are the fixed-order sums of per-block partials
+    (`finish=False`: the fp32 [n_partials, C] partials themselves); `dres` (bf16 [R, C]) is added to dx."""
+    R, C = _ln_ok(x, mean, rstd, gamma, None)
+    _dev(dy, dres)
+    assert dy.dtype == torch.bfloat16 and dy.is_contiguous() and dy.shape == x.shape
+    assert dres is None or (dres.dtype == torch.bfloat16 and dres.is_contiguous() and dres.shape == x.shape)
+    n_partials = max(1, min(n_partials, (R + 3) // 4))
+    dx = torch.empty_like(x)
+    part = torch.empty((2, n_partials, C), dtype=torch.float32, device=x.device)
+    rc = _lib.require("mi_layernorm_bwd", _LN_WHY)(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+                                                   _ptr(dres), dx.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), n_partials, R, C,
+                                                   int(bool(zero_centered)), _stream())
+    _lib.check(rc, "mi_layernorm_bwd")
+    if not finish:
+        return dx, part[0], part[1]
+    dg, db = colsum_finish_multi([(part[0], dgamma_dtype), (part[1], dbeta_dtype or dgamma_dtype)])
+    return dx, dg, db
+
+
 # ---- The block-scaled quantisers: K7 and its fused producers, once for both families.  `gran` is None for MXFP8 (one E8M0 scale per
 # 32 elements) or (dim, amax_epsilon) for Float8BlockScaling: one power-of-two scale per 1 x 128 (dim 1) / 128 x 128 (dim 2) block,
 # stored as the block's E8M0 byte at every 32-group it covers -- the same tuples and operand layout, so gemm_mxfp8 reads either. ----
